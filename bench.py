@@ -11,6 +11,13 @@ every step.
     python bench.py --gpus 1 --steps 5 --warmup 1
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the headline line (metric, value, unit,
+ms_per_step, ...).  --full adds what needs runs or checks of its own: the stage groups' HIP events, the
+roofline and counter figures, solver statistics, parity against the CPU oracle, the size scan, the
+host-buffer legs, the other protocols and models and the CPU baselines.  --dump-outputs DIR writes the
+maps of the last timed step as DIR/estimates.npy; the synthetic inputs are seeded, so two builds run
+with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -722,6 +729,23 @@ def timed_steps(step, step_sync, steps, warmup, world, dev, per_step=None):
     return elapsed
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array (torch or numpy) as <dirname>/<name>.npy in float64.  When the arrays together exceed 64 MB
+    (the gathered maps of a multi-GPU run), each is cut to the same fixed sample of rows (numpy seed 0, row order kept), so that
+    two builds run with the same arguments can be compared output for output."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {name: np.asarray(a.cpu() if hasattr(a, 'cpu') else a, dtype=np.float64) for name, a in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    for name, a in host.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, len(a) * DUMP_LIMIT_BYTES // total)
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), np.ascontiguousarray(a))
+
+
 def rank_records(world, rank, dev):
     """who ran: backend, world size and each rank's device (gathered through the process group when there is one)"""
     import torch
@@ -765,10 +789,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--voxels', type=int, default=1_000_000, help='voxels per GPU')
     ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-other-configs', action='store_true', help='headline only: skip configs 3 / 4 (FreeWater 2 M, SANDI 1 M), CylinderZeppelinBall and the host-buffer legs of the default run')
+    ap.add_argument('--no-other-configs', action='store_true', help='headline only: skip configs 3 / 4 (FreeWater 2 M, SANDI 1 M), CylinderZeppelinBall and the host-buffer legs of the --full run')
     ap.add_argument('--model', default='noddi', choices=['noddi', 'freewater', 'sandi', 'czb', 'dti', 'prep', 'lut', 'pipeline'],
                     help='noddi = the BASELINE.json headline; the others are extra measurements (configs 3, 4)')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline figure: stage-group event probes, roofline and counter figures, solver statistics, '
+                         'oracle parity, size scan, host-buffer legs, other protocols and models, CPU baselines')
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write the maps of the last step as DIR/<name>.npy (float64, at most 64 MB)')
     args = ap.parse_args()
+    if args.dump_outputs and args.model != 'noddi':
+        raise SystemExit('bench.py: --dump-outputs is implemented for the NODDI headline (--model noddi) only')
     if args.model == 'dti':
         return dti_directions(args)
     if args.model == 'prep':
@@ -818,7 +849,6 @@ def main():
     gathered = torch.zeros((world * n, 3), dtype=torch.float64, device=dev) if world > 1 else None
     stream = torch.cuda.current_stream().cuda_stream
     L = _capi.lib()
-    ctx.set_profiling(True)
 
     def fit():
         ctx.check(L.amx_noddi_fit_device(ctx._h, lut._h, y.data_ptr(), d.data_ptr(), n, 0.5, 1e-3, 0,
@@ -834,38 +864,62 @@ def main():
             except Exception:                                   # seed kernels absent (AMX_NO_SEED=1)
                 pass
 
-    # Untimed probe steps with EVERY event pair recorded: the stage groups' times and which single kernel dominates.  An event is a
-    # packet of the stream (~5 us of the fit each, ~70 us for the full set: tools/r06/a27.sh), so the timed steps record only the
-    # dominant kernel's pair -- the duration the roofline object is computed from is still measured inside the timed region.
-    PROBE = 3
-    for k in range(max(1, args.warmup) + PROBE):
-        step(); ctx.sync(stream)
-        if k >= max(1, args.warmup):
-            read_pairs((0, 1, 2, 3, 5, 6, 7, 8, 9))
-    kms /= PROBE
-    # the dominant SINGLE kernel: the stage-1 seed solver (its own event pair), else the slowest of the other launches
-    stage = max((8, 9, 1, 2, 3), key=lambda w: kms[w])
-    if kms[8] == 0.0 and kms[9] == 0.0:                        # seeds off: the three stage kernels are the whole fit
-        stage = max((1, 2, 3), key=lambda w: kms[w])
-    probe_all_ms = float(kms[0])
-    ctx.set_profiling(True, only=stage)
-    kms[stage] = 0.0
+    if args.full:
+        # Untimed probe steps with EVERY event pair recorded: the stage groups' times and which single kernel dominates.  An event is a
+        # packet of the stream (~5 us of the fit each, ~70 us for the full set: tools/r06/a27.sh), so the timed steps record only the
+        # dominant kernel's pair -- the duration the roofline object is computed from is still measured inside the timed region.
+        ctx.set_profiling(True)
+        PROBE = 3
+        for k in range(max(1, args.warmup) + PROBE):
+            step(); ctx.sync(stream)
+            if k >= max(1, args.warmup):
+                read_pairs((0, 1, 2, 3, 5, 6, 7, 8, 9))
+        kms /= PROBE
+        # the dominant SINGLE kernel: the stage-1 seed solver (its own event pair), else the slowest of the other launches
+        stage = max((8, 9, 1, 2, 3), key=lambda w: kms[w])
+        if kms[8] == 0.0 and kms[9] == 0.0:                        # seeds off: the three stage kernels are the whole fit
+            stage = max((1, 2, 3), key=lambda w: kms[w])
+        probe_all_ms = float(kms[0])
+        ctx.set_profiling(True, only=stage)
+        kms[stage] = 0.0
 
-    def per_step():
-        read_pairs((stage,))
+        def per_step():
+            read_pairs((stage,))
+        warmup = args.warmup
+    else:
+        # a plain run records no events: W warm-up steps, at least one (the first fit of a context sizes its buffers), then the K
+        # timed steps
+        per_step = None
+        warmup = max(1, args.warmup)
 
     # ctx.sync: status of the step (raises on error)
-    elapsed = timed_steps(step, lambda: ctx.sync(stream), args.steps, args.warmup, world, dev, per_step)
-    kms[stage] /= max(1, args.steps)
-    ctx.set_profiling(False)                                   # (everything below is timed as a user would run it)
-    stats = ctx.last_stats()
-    seed_chain = ctx.last_seed_stats()
-    if seed_chain.get('seeded_voxels'):            # (the counters accumulate between two syncs: one step's worth here)
-        seed_chain['certified_by_gram_certificates'] = seed_chain.pop('certified')
+    elapsed = timed_steps(step, lambda: ctx.sync(stream), args.steps, warmup, world, dev, per_step)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {'estimates': est if gathered is None else gathered})
+    if args.full:
+        kms[stage] /= max(1, args.steps)
+        ctx.set_profiling(False)                                   # (everything below is timed as a user would run it)
+        stats = ctx.last_stats()
+        seed_chain = ctx.last_seed_stats()
+        if seed_chain.get('seeded_voxels'):            # (the counters accumulate between two syncs: one step's worth here)
+            seed_chain['certified_by_gram_certificates'] = seed_chain.pop('certified')
+        who = rank_records(world, rank, dev)
 
-    who = rank_records(world, rank, dev)
     if rank == 0:
         value = world * n * args.steps / elapsed
+        out = {
+            'metric': 'voxels/sec (whole node), NODDI fit',
+            'value': value, 'unit': 'voxels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
+            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak',
+            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
+            'config': {'workload': 'NODDI fit, %d masked voxels per GPU, 99-volume 2-shell scheme '
+                                   '(9 b0 + 30@b700 + 60@b2000), 145 atoms, ndirs=500, inputs resident in HBM' % n,
+                       'voxels_per_gpu': n, 'global_voxels': world * n,
+                       'parallelism': 'voxel shards x%d, one RCCL all_gather of the maps per step' % world},
+        }
+        if not args.full:
+            print(json.dumps(out))
+    if rank == 0 and args.full:
         groups = {1: 'k_noddi<1> (stage 1: voxels the Gram certificate left over) + re-run kernel', 2: 'k_noddi<4> (LASSO: left-over voxels) + re-run kernel',
                   3: 'k_noddi<3> (stage 3: left-over voxels) + re-run kernel',
                   5: "k_noddi_gemm + k_nnls_seed<1> + k_nnls_gcert<1> (A'y on the matrix cores, seed solver, Gram certificate of stage 1)",
@@ -877,15 +931,7 @@ def main():
         achieved = BYTES_PER_VOXEL * n / (dom_ms * 1e-3) / 1e9
         traffic = pmc_traffic(stage, n)
         whole = pmc_whole_fit(n)
-        out = {
-            'metric': 'voxels/sec (whole node), NODDI fit',
-            'value': value, 'unit': 'voxels/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
-            'ms_per_step': 1e3 * elapsed / args.steps, 'higher_is_better': True, 'scaling': 'weak',
-            'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
-            'config': {'workload': 'NODDI fit, %d masked voxels per GPU, 99-volume 2-shell scheme '
-                                   '(9 b0 + 30@b700 + 60@b2000), 145 atoms, ndirs=500, inputs resident in HBM' % n,
-                       'voxels_per_gpu': n, 'global_voxels': world * n,
-                       'parallelism': 'voxel shards x%d, one RCCL all_gather of the maps per step' % world},
+        out.update({
             'roofline': {'bound': 'hbm', 'achieved': achieved, 'peak': HBM_PEAK_GBS, 'unit': 'GB/s',
                          'frac': achieved / HBM_PEAK_GBS, 'traffic': traffic,
                          # the same two figures for the WHOLE fit: algorithmic bytes of the step over its wall time, and the counter
@@ -906,7 +952,7 @@ def main():
             'solver_stats': stats, 'seed_chain': seed_chain,
             'multi_gpu': dict(who, elapsed_s_per_rank=getattr(timed_steps, 'per_rank', None), elapsed_s_max=elapsed),
             'build': build_record(),
-        }
+        })
         if world == 1:
             from oracle import oracle
             # parity on a sample of the benchmarked voxels (max |dmap| of BASELINE.json's metric)

@@ -112,6 +112,31 @@ def test_bench_gpus2_starts_its_own_ranks():
     assert '2 GPUs requested, 1 visible' in (p.stdout + p.stderr)
 
 
+def test_bench_plain_line_and_dumped_maps(tmp_path):
+    """a plain `bench.py --steps K --warmup W`: the headline line alone (K timed steps, ms_per_step), and --dump-outputs writes the
+    maps of the last step -- the seeded workload's own maps, as the oracle computes them"""
+    import json
+    from amico_amd import synthetic as S
+    from oracle import oracle
+    n = 4096
+    p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--voxels', str(n),
+                        '--dump-outputs', str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads(p.stdout.strip().splitlines()[-1])
+    assert line['steps'] == 3 and line['warmup'] == 1 and line['n_gpus'] == 1
+    assert line['unit'] == 'voxels/s' and line['higher_is_better'] is True and line['dtype'] == 'f64'
+    assert line['ms_per_step'] > 0 and abs(line['value'] - n / (line['ms_per_step'] * 1e-3)) < 1e-6 * line['value']
+    assert 'roofline' not in line and 'parity' not in line and 'other_configs' not in line      # (those are --full)
+    est = np.load(tmp_path / 'estimates.npy')
+    assert est.dtype == np.float64 and est.shape == (n, 3)
+    dirs = S.fibonacci_hemisphere(500); ht = S.build_htable(dirs)
+    sch = S.make_scheme(seed=0); K = S.noddi_kernels(sch, dirs)
+    y_h, d_h = S.noddi_signals(n, K, ht, sch, seed=1)                  # bench.py's workload, rank 0
+    ref = oracle.noddi_fit(y_h, d_h, K, ht, sch.dwi_idx, nthreads=os.cpu_count() or 1)['estimates']
+    diff = np.abs(est - ref).max(axis=1)
+    assert diff.max() < 1e-4 and (diff < 1e-6).mean() >= 0.995
+
+
 def test_noddi_fit_is_bitwise_repeatable():
     """The seed solvers run one voxel per lane next to 63 others drawn from a ticket: which voxels share a wavefront changes
     from call to call, the result of a voxel must not (a neighbour-dependent branch once made ~20 of 900 000 seeds differ

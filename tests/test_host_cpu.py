@@ -318,3 +318,24 @@ def test_fit_on_devices_shards_like_the_reference_chunks(monkeypatch):
     with pytest.raises(RuntimeError, match=r'\[voxel 673\]'):          # 668 + 5
         m._fit_on_devices(Ev(), n, lambda c: 'x', bad, (np.zeros((n, 2)), None, np.zeros(n)))
     assert all(c.sizes[-1] == 0 for c in ctxs)
+
+
+def test_bench_dump_outputs_writes_float64_and_samples_fixed_rows(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array written as float64; above the size limit the same seeded rows of every array, in
+    order, so that two builds can be compared output for output"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.arange(3000, dtype=np.float64).reshape(1000, 3)
+    b = torch.arange(1000, dtype=torch.float32)
+    bench.dump_outputs(str(tmp_path / 'all'), {'estimates': a, 'rmse': b})
+    got_a, got_b = np.load(tmp_path / 'all' / 'estimates.npy'), np.load(tmp_path / 'all' / 'rmse.npy')
+    assert got_a.dtype == got_b.dtype == np.float64
+    assert np.array_equal(got_a, a) and np.array_equal(got_b, b.numpy())
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', (a.nbytes + b.numel() * 8) // 4)
+    for run in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / run), {'estimates': a, 'rmse': b})
+    s_a, s_b = np.load(tmp_path / 's1' / 'estimates.npy'), np.load(tmp_path / 's1' / 'rmse.npy')
+    assert s_a.nbytes + s_b.nbytes <= bench.DUMP_LIMIT_BYTES and len(s_a) == len(s_b) == 250
+    assert np.all(np.diff(s_a[:, 0]) > 0) and np.array_equal(s_a[:, 0] / 3, s_b)         # the same rows of both, row order kept
+    assert np.array_equal(s_a, np.load(tmp_path / 's2' / 'estimates.npy'))
