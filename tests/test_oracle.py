@@ -211,3 +211,109 @@ def test_czb_oracle_matches_fixture(czb_fix, htable500):
         x = o['x'][v]
         g = A.T @ (f['y'][v] - A @ x) - float(f['lambda2']) * x
         assert np.abs(g[x > 0]).max(initial=0.0) < 1e-10 and g[x == 0].max(initial=0.0) < 1e-10
+
+
+# ------------------------------------------------------------------ scale equivariance (the exact reference at amplitudes far from 1)
+SCALES = (2.0 ** -10, 2.0 ** -4, 2.0 ** 4, 2.0 ** 10, 2.0 ** 14)      # powers of two: c * y is exact in float32 and float64
+MAP_EQ = 1e-12
+
+
+def _map_tol(x1, c):
+    """per-voxel bound on the change of a map: MAP_EQ plus the reference's `+ 1e-16` terms in the ratios' denominators, which do
+    not scale -- they show on voxels whose coefficients are small (the hard mix's background, or any voxel at c = 2^-10)"""
+    return MAP_EQ + 1e-15 / np.maximum(c * np.abs(x1).sum(axis=1), 1e-300)
+
+
+def _rel_scaled(a_c, a_1, c):
+    """max |a(c y) - c a(y)| / c: the departure from equivariance of a quantity that scales with the signal, in unit-scale terms"""
+    return float(np.abs(np.asarray(a_c) / c - np.asarray(a_1)).max(initial=0.0))
+
+
+def test_nnls_and_lasso_are_scale_equivariant():
+    """x(c y) = c x(y) for NNLS, and for the non-negative elastic net with (c lambda1, lambda2)"""
+    rng = np.random.default_rng(11)
+    for (m, n) in [(20, 5), (6, 15), (99, 30), (50, 50)]:
+        for _ in range(4):
+            A = np.abs(rng.standard_normal((m, n))); y = np.abs(rng.standard_normal(m))
+            x1, rn1, _ = oracle.nnls(A, y)
+            xl1, _ = oracle.lasso(A, y, 0.3, 0.05)
+            for c in SCALES:
+                xc, rnc, mode = oracle.nnls(A, c * y)
+                assert mode == 1 and np.array_equal(xc > 0, x1 > 0)
+                assert _rel_scaled(xc, x1, c) <= 1e-12 * max(1.0, np.abs(x1).max()), (m, n, c)
+                assert abs(rnc / c - rn1) <= 1e-12 * max(1.0, rn1), (m, n, c)
+                xlc, st = oracle.lasso(A, c * y, 0.3 * c, 0.05)
+                assert st == 0 and np.array_equal(xlc > 0, xl1 > 0)
+                assert _rel_scaled(xlc, xl1, c) <= 1e-12 * max(1.0, np.abs(xl1).max()), (m, n, c)
+
+
+@pytest.mark.parametrize('exvivo', [False, True])
+def test_noddi_oracle_is_scale_equivariant(htable500, exvivo):
+    """maps (NDI / ODI / FWF, the ex vivo fraction, modulated maps) and NRMSE invariant, RMSE and x scaling with c, on clean and
+    hard-mix signals -- which makes the unit-scale device fit a reference at every amplitude"""
+    ht = htable500['htable']
+    sch = S.make_scheme(seed=0)
+    K = S.noddi_kernels(sch, htable500['dirs'])
+    y0, d0 = S.noddi_signals(600, K, ht, sch, seed=5)
+    y1, d1, _ = S.noddi_hard_signals(600, K, ht, sch, seed=6)
+    y, d = np.concatenate([y0, y1]), np.concatenate([d0, d1])
+    kw = dict(is_exvivo=exvivo, rmse=True, nrmse=True, mod=True, return_x=True, nthreads=8)
+    ref = oracle.noddi_fit(y, d, K, ht, sch.dwi_idx, 0.5, 1e-3, **kw)
+    for c in SCALES:
+        out = oracle.noddi_fit(c * y, d, K, ht, sch.dwi_idx, 0.5 * c, 1e-3, **kw)
+        assert out['err'] == 0
+        tol = _map_tol(ref['x'][:, 2], c)
+        for k in ('estimates', 'estimates_mod'):
+            assert (np.abs(out[k] - ref[k]).max(axis=1) <= tol).all(), (c, k)
+        assert np.abs(out['nrmse'] - ref['nrmse']).max() <= MAP_EQ, c
+        assert _rel_scaled(out['rmse'], ref['rmse'], c) <= 1e-12, c
+        assert _rel_scaled(out['x'], ref['x'], c) <= 1e-12, c
+
+
+def test_freewater_oracle_is_scale_equivariant(htable500):
+    ht = htable500['htable']
+    sch = S.make_scheme(1, ((1000.0, 64),), seed=3)
+    K = S.freewater_kernels(sch, htable500['dirs'])
+    y, d = S.freewater_signals(1500, K, ht, sch, seed=4, snr=10.0)
+    for mouse in (False, True):
+        kw = dict(is_mouse=mouse, rmse=True, nrmse=True, corrected=True, return_x=True, nthreads=8)
+        ref = oracle.freewater_fit(y, d, K, ht, 0.0, 1e-3, **kw)
+        for c in SCALES:
+            out = oracle.freewater_fit(c * y, d, K, ht, 0.0, 1e-3, **kw)
+            assert out['err'] == 0
+            assert (np.abs(out['estimates'] - ref['estimates']).max(axis=1) <= _map_tol(ref['x'], c)).all(), (mouse, c)
+            assert np.abs(out['nrmse'] - ref['nrmse']).max() <= MAP_EQ, (mouse, c)
+            for k in ('rmse', 'y_corrected', 'x'):
+                assert _rel_scaled(out[k], ref[k], c) <= 1e-12, (mouse, c, k)
+
+
+def test_sandi_oracle_is_scale_equivariant():
+    avg = S.directional_average_scheme(S.make_sandi_scheme())
+    K, Rs, d_in, d_isos = S.sandi_kernels(avg)
+    y = S.sandi_signals(1500, K, avg, seed=4, snr=10.0)
+    kw = dict(rmse=True, nrmse=True, return_x=True, nthreads=8)
+    ref = oracle.sandi_fit(y, K, Rs, d_in, d_isos, 0.0, 5e-3, **kw)
+    for c in SCALES:
+        out = oracle.sandi_fit(c * y, K, Rs, d_in, d_isos, 0.0, 5e-3, **kw)
+        e, r, tol = out['estimates'], ref['estimates'], _map_tol(ref['x'], c)
+        assert (np.abs(e[:, :3] - r[:, :3]).max(axis=1) <= tol).all(), c                                  # volume fractions
+        parts = np.split(ref['x'], np.cumsum([len(Rs), len(d_in)]), axis=1)                                # Rsoma / Din / De: per compartment
+        tol = np.stack([_map_tol(p, c) for p in parts], axis=1)
+        assert (np.abs(e[:, 3:] - r[:, 3:]) / (np.abs(r[:, 3:]) + 1e-3) <= tol).all(), c
+        assert np.abs(out['nrmse'] - ref['nrmse']).max() <= MAP_EQ, c
+        assert _rel_scaled(out['rmse'], ref['rmse'], c) <= 1e-12, c
+        assert _rel_scaled(out['x'], ref['x'], c) <= 1e-12, c
+
+
+def test_czb_oracle_is_scale_equivariant(czb_fix, htable500):
+    f = czb_fix
+    kw = dict(rmse=True, nrmse=True, return_x=True, nthreads=8)
+    ref = oracle.czb_fit(f['y'], f['dirs'], f['kernels'], f['Rs'], htable500['htable'], 0.0, 4.0, **kw)
+    for c in SCALES:
+        out = oracle.czb_fit(c * f['y'], f['dirs'], f['kernels'], f['Rs'], htable500['htable'], 0.0, 4.0, **kw)
+        assert out['err'] == 0
+        rel = np.abs(out['estimates'] - ref['estimates']) / (np.abs(ref['estimates']) + 1e-3)                 # v / a / d
+        assert (rel.max(axis=1) <= _map_tol(ref['x'], c)).all(), c
+        assert np.abs(out['nrmse'] - ref['nrmse']).max() <= MAP_EQ, c
+        assert _rel_scaled(out['rmse'], ref['rmse'], c) <= 1e-12, c
+        assert _rel_scaled(out['x'], ref['x'], c) <= 1e-12, c
