@@ -22,7 +22,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_noddi_fit_device_f32', 'amx_freewater_fit_device_f32', 'amx_sandi_fit_device_f32', 'amx_czb_fit_device_f32',
            'amx_set_debug_x', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
            'amx_set_profiling', 'amx_last_kernel_ms', 'amx_last_stats', 'amx_last_seed_stats', 'amx_last_host_narrowed', 'amx_last_path', 'amx_host_pool_info', 'amx_selftest',
-           'amx_dti_create', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32', 'amx_prep_gather_device_f32',
+           'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
            'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
@@ -141,6 +141,9 @@ def lib():
     L.amx_lasso_batched_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_double, C.c_double, c_vp, c_vp]
     L.amx_selftest.argtypes = [c_vp, c_dp]
     L.amx_dti_create.argtypes = [c_vp, c_dp, C.c_int, C.c_double, C.POINTER(c_vp)]
+    L.amx_dti_create_method.argtypes = [c_vp, c_dp, c_dp, C.c_int, C.c_double, C.c_int, C.POINTER(c_vp)]
+    L.amx_dti_last_unconverged.argtypes = [c_vp, c_vp, C.POINTER(C.c_int64)]
+    L.amx_dti_last_trips.argtypes = [c_vp, c_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.amx_dti_destroy.argtypes = [c_vp]
     L.amx_dti_destroy.restype = None
     L.amx_dti_directions.argtypes = [c_vp, c_vp, c_dp, C.c_int64, c_dp]
@@ -617,13 +620,38 @@ def dir_to_lut_idx(ctx, lut, dirs):
 class Dti:
     """amx_dti: principal-direction estimator of one acquisition scheme (include/amico_amd.h, row f1)."""
 
-    def __init__(self, ctx, inv_design, min_signal=1e-4):
+    METHODS = {'OLS': 0, 'WLS': 1, 'NLLS': 2}        # AMX_DTI_* (include/amico_amd.h)
+
+    def __init__(self, ctx, inv_design, min_signal=1e-4, design=None, method='OLS'):
         w = np.ascontiguousarray(inv_design, dtype=np.float64)
         if w.ndim != 2 or w.shape[0] != 7:
             raise ValueError('inv_design must be pinv(design matrix), shape [7, nS]')
-        self.ctx, self.nS = ctx, w.shape[1]
+        if method not in self.METHODS:
+            raise ValueError("method must be one of 'OLS', 'WLS', 'NLLS'")
+        if design is None:
+            if method != 'OLS':
+                raise ValueError('%s needs the design matrix, shape [nS, 7]' % method)
+            x = None
+        else:
+            x = np.ascontiguousarray(design, dtype=np.float64)
+            if x.shape != (w.shape[1], 7):
+                raise ValueError('design must be the design matrix, shape [nS, 7] = [%d, 7]' % w.shape[1])
+        self.ctx, self.nS, self.method = ctx, w.shape[1], method
         self._h = c_vp()
-        ctx.check(lib().amx_dti_create(ctx._h, _p(w, c_dp), self.nS, float(min_signal), C.byref(self._h)))
+        ctx.check(lib().amx_dti_create_method(ctx._h, None if x is None else _p(x, c_dp), _p(w, c_dp), self.nS, float(min_signal),
+                                              self.METHODS[method], C.byref(self._h)))
+
+    def last_unconverged(self):
+        """voxels of the last NLLS call that kept their starting parameters (waits for the call)"""
+        out = C.c_int64(0)
+        self.ctx.check(lib().amx_dti_last_unconverged(self.ctx._h, self._h, C.byref(out)))
+        return out.value
+
+    def last_trips(self):
+        """(Levenberg-Marquardt trips summed over the voxels, trips their wavefronts ran for them) of the last NLLS call"""
+        a, b = C.c_int64(0), C.c_int64(0)
+        self.ctx.check(lib().amx_dti_last_trips(self.ctx._h, self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
 
     def close(self):
         if getattr(self, '_h', None) and getattr(self.ctx, '_h', None):

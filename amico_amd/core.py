@@ -4,7 +4,7 @@ in-memory volumes, every per-voxel step on the GPU:
 
   set_data   ~ load_data's preprocessing inputs (core.py:209-268): raw float32 image, scheme, mask
   fit        b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
-             principal directions from the log-linear tensor fit                -> ``DIRs``   (amx_dti_directions)
+             principal directions from the tensor fit (DTI_fit_method)          -> ``DIRs``   (amx_dti_directions)
              model.fit(self)                                                    -> maps       (amx_*_fit)
              scatter into float32 volumes (core.py:472-498)                     -> ``RESULTS`` (amx_prep_scatter)
 
@@ -190,6 +190,7 @@ class Evaluation:
             raise RuntimeError('Response functions not set; call "set_kernels()" first')
         if self.KERNELS['model'] != self.model.id:
             raise RuntimeError('Response functions were not created with the same model')
+        _dti.check_fit_method(self.get_config('DTI_fit_method'))     # core.py:419-420: before anything is uploaded
         nt = self.get_config('nthreads')
         self.nthreads = nt if nt > 0 else cpu_count()
         self.model.scheme = self.scheme
@@ -221,9 +222,9 @@ class Evaluation:
         elif self._dirs_img is not None:
             d_dirs = torch.from_numpy(np.ascontiguousarray(self._dirs_img[sel, :], dtype=np.float64)).to(dev)
         else:
-            if self.get_config('DTI_fit_method') not in ('OLS', 'LS'):
-                raise NotImplementedError('only the default DTI_fit_method (OLS) runs on the GPU')
-            est = _dti.TensorDirections.from_scheme(self._raw_scheme, do_merge_b0=self.get_config('doMergeB0'), ctx=ctx)
+            # (raises NotImplementedError for 'RT' / 'RESTORE': only here, where a tensor fit would actually run)
+            est = _dti.TensorDirections.from_scheme(self._raw_scheme, do_merge_b0=self.get_config('doMergeB0'), ctx=ctx,
+                                                    fit_method=self.get_config('DTI_fit_method'))
             d_dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
             est.fit_device(d_y.data_ptr(), n, d_dirs.data_ptr(), f32=True)
         ctx.sync()

@@ -1,5 +1,6 @@
 // amx_signal.hip -- the steps either side of model.fit (SURVEY section 8 f): principal directions from the
-// log-linear tensor fit (core.py:431-436, 456-458) -- streaming, HBM-bound kernels.
+// log-linear tensor fit (core.py:431-436, 456-458) -- streaming, HBM-bound kernels -- and from the weighted / non-linear
+// fits of DTI_fit_method 'WLS' / 'NLLS' (core.py:419-420, 436), k_dti_dirs_w.
 #include "amx_host.hpp"
 #include "amx_tensor.hpp"
 
@@ -139,25 +140,381 @@ __global__ __launch_bounds__(kDtiThreads, 4) void k_dti_dirs(const YT *__restric
     }
 }
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// WLS and NLLS tensor fits (dipy/reconst/dti.py: wls_fit_tensor, nlls_fit_tensor with weighting=None).  X = design matrix
+// [nS][7], s = max(y, min_signal):
+//   WLS   p_ols = pinv(X) log s;  w = exp(X p_ols) (the signal OLS predicts);  p = argmin sum w_i^2 (log s_i - X_i p)^2
+//         (dipy: pinv(X * w[:, None]) @ (w * log s))
+//   NLLS  p = argmin sum (s_i - exp(X_i p))^2: the local minimum next to the linear fit.  dipy runs MINPACK's
+//         Levenberg-Marquardt from a linear fit (which one has changed between dipy releases; the minimum does not depend on it
+//         except in pathological voxels) and keeps the starting parameters when the solve fails.  Here: Levenberg-Marquardt
+//         from the WLS solution, stopped when the cost no longer moves in fp64.
+// Both run on the design matrix with its columns scaled to unit max-abs (host side; the scale is undone on the six tensor
+// entries before the eigen-solve): the 7 x 7 normal matrix of the scaled system is conditioned well enough for a register
+// Cholesky to reproduce the SVD route (cond(X) = 2.1e3 on the 99-volume scheme, cond of the scaled normal matrix <= 2.5e2).
+//
+// Tile staging, logarithms and the batched eigen-solves are k_dti_dirs'.  In between, the eight lanes of a voxel each
+// accumulate their share of the 28 + 7 normal-equation sums over the voxel's LDS row; an xor-butterfly leaves all eight with
+// the same bits, and all eight run the 7 x 7 Cholesky solve redundantly -- no LDS round trip or barrier inside the
+// Levenberg-Marquardt loop, and a wavefront waits for the slowest of its 8 voxels, not of 64.
+struct DtiScale { double ics[7]; };            // 1 / column scale of the design matrix
+constexpr int kDtiNormLd = 37;                 // 28 + 7 sums per voxel, odd row stride
+constexpr int kLmTrips = 64;                    // trip cap of the NLLS loop (10 on average, 32 at most in a numpy emulation)
+
+__device__ __forceinline__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
+
+__device__ __forceinline__ double lanes_sum(double x)
+{
+#pragma unroll
+    for (int m = 1; m < kDtiLanes; m <<= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+// (A + lam diag A) x = b for the symmetric positive definite A (lower triangle, packed by rows), in place: A becomes its
+// Cholesky factor (1 / pivot on the diagonal), b becomes x.  false when a pivot is not positive.
+__device__ __forceinline__ bool chol_solve7(double (&A)[28], double (&b)[7], double lam)
+{
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 7; j++) {
+        double d = fma(A[tri(j, j)], lam, A[tri(j, j)]);
+#pragma unroll
+        for (int k = 0; k < j; k++) d = fma(-A[tri(j, k)], A[tri(j, k)], d);
+        const bool pos = d > 1e-280 && d < 1e280;
+        ok = ok && pos;
+        const double inv = fast_rsqrt(pos ? d : 1.0);
+        A[tri(j, j)] = inv;
+#pragma unroll
+        for (int i = j + 1; i < 7; i++) {
+            double t = A[tri(i, j)];
+#pragma unroll
+            for (int k = 0; k < j; k++) t = fma(-A[tri(i, k)], A[tri(j, k)], t);
+            A[tri(i, j)] = t * inv;
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 7; i++) {
+        double t = b[i];
+#pragma unroll
+        for (int k = 0; k < i; k++) t = fma(-A[tri(i, k)], b[k], t);
+        b[i] = t * A[tri(i, i)];
+    }
+#pragma unroll
+    for (int i = 6; i >= 0; i--) {
+        double t = b[i];
+#pragma unroll
+        for (int k = i + 1; k < 7; k++) t = fma(-A[tri(k, i)], b[k], t);
+        b[i] = t * A[tri(i, i)];
+    }
+    return ok;
+}
+
+// one lane's share (volumes q, q + 8, ..) of the weighted normal equations, summed over the voxel's lanes:
+// G = X^T W^2 X, g = X^T W^2 log s with W = exp(X p)
+__device__ __forceinline__ void wls_pass(const double *__restrict__ xl, const double *__restrict__ yr, int nS, int q,
+                                         const double (&p)[7], double (&G)[28], double (&g)[7])
+{
+#pragma unroll
+    for (int k = 0; k < 28; k++) G[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = 0.0;
+#pragma unroll 1
+    for (int v = q; v < nS; v += kDtiLanes) {
+        double x[7], t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) { x[k] = xl[v * 7 + k]; t = fma(x[k], p[k], t); }
+        const double w2 = exp(2.0 * t), ly = yr[v];
+#pragma unroll
+        for (int j = 0; j < 7; j++) {
+            const double wx = w2 * x[j];
+            g[j] = fma(wx, ly, g[j]);
+#pragma unroll
+            for (int k = 0; k <= j; k++) G[tri(j, k)] = fma(wx, x[k], G[tri(j, k)]);
+        }
+    }
+    // (in chunks: left to itself the scheduler keeps the sources and results of all 35 butterflies live at once)
+#pragma unroll
+    for (int k0 = 0; k0 < 28; k0 += 7) {
+#pragma unroll
+        for (int k = k0; k < k0 + 7; k++) G[k] = lanes_sum(G[k]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = lanes_sum(g[k]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// the same for the non-linear cost at p: e = exp(X p), r = s - e, c = sum r^2, G = J^T J, g = J^T r with J = e (.) X
+__device__ __forceinline__ void nlls_pass(const double *__restrict__ xl, const double *__restrict__ sr, int nS, int q,
+                                          const double (&p)[7], double &c, double (&G)[28], double (&g)[7])
+{
+    c = 0.0;
+#pragma unroll
+    for (int k = 0; k < 28; k++) G[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = 0.0;
+#pragma unroll 1
+    for (int v = q; v < nS; v += kDtiLanes) {
+        double x[7], t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) { x[k] = xl[v * 7 + k]; t = fma(x[k], p[k], t); }
+        const double e = exp(t), r = sr[v] - e;
+        c = fma(r, r, c);
+#pragma unroll
+        for (int j = 0; j < 7; j++) {
+            const double ex = e * x[j];
+            g[j] = fma(ex, r, g[j]);
+#pragma unroll
+            for (int k = 0; k <= j; k++) G[tri(j, k)] = fma(ex, e * x[k], G[tri(j, k)]);
+        }
+    }
+    c = lanes_sum(c);
+    // (in chunks: left to itself the scheduler keeps the sources and results of all 35 butterflies live at once)
+#pragma unroll
+    for (int k0 = 0; k0 < 28; k0 += 7) {
+#pragma unroll
+        for (int k = k0; k < k0 + 7; k++) G[k] = lanes_sum(G[k]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = lanes_sum(g[k]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+__device__ __forceinline__ int wave_sum(int x)
+{
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+// y f64|f32[n][nS] -> dirs f64[n][3].  wt7 f64[nS][7]: pinv(X)^T with row k scaled by the column scale of X; xs f64[nS][7]: X
+// with its columns scaled to unit max-abs.  stats (NLLS): [0] voxels that kept their starting parameters, [1] trips of the
+// voxels, [2] trips their wavefronts made for them (a voxel waits for the slowest of the 8 in its wavefront).
+template <typename YT, bool NLLS>
+__global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const YT *__restrict__ y, const double *__restrict__ wt7,
+                                                                        const double *__restrict__ xs, DtiScale sc,
+                                                                        int nS, int ldl, int tv, long long n, double min_signal,
+                                                                        double *__restrict__ dirs, unsigned long long *__restrict__ stats)
+{
+    extern __shared__ double sm[];
+    double *wl = sm;                                   // nS * 7
+    double *xl = sm + nS * 7;                          // nS * 7 (odd row stride)
+    double *yl = sm + ((nS * 14 + 1) & ~1);            // tv * ldl
+    double *dl = yl + tv * ldl;                        // kDtiBatch * tv * 7 (6 tensor entries, odd stride)
+    double *gl = dl + kDtiBatch * tv * 7;              // NLLS: tv * kDtiNormLd (normal equations of each voxel's accepted point)
+    const int tid = threadIdx.x;
+    for (int i = tid; i < nS * 7; i += kDtiThreads) { wl[i] = wt7[i]; xl[i] = xs[i]; }
+    const long long n_tiles = (n + tv - 1) / tv;
+    const int step = 2 * kDtiThreads;
+    const int step_vol = step % nS, step_adr = (step / nS) * ldl + step_vol;
+    const int vox0 = (2 * tid) / nS, vol0 = 2 * tid - vox0 * nS, adr0 = vox0 * ldl + vol0;
+    const int eslot = tid / tv, evox = tid - eslot * tv;      // tensor this thread diagonalises in a batch
+    double2 pre[kDtiPre];
+#pragma unroll
+    for (int i = 0; i < kDtiPre; i++) pre[i] = make_double2(1.0, 1.0);
+    long long tile = blockIdx.x;
+    if (tile < n_tiles) {
+        const long long v0 = tile * tv;
+        dti_prefetch(pre, y + v0 * nS, (int)((n - v0) < tv ? (n - v0) : tv) * nS, tid);
+    }
+    long long batch_tile = tile;
+    int slot = 0;
+    for (; tile < n_tiles; tile += gridDim.x) {
+        const long long v0 = tile * tv;
+        const int nv = (int)((n - v0) < tv ? (n - v0) : tv);
+        const int cnt = nv * nS;
+#pragma unroll
+        for (int i = 0; i < kDtiPre; i++) {            // (four chains at a time: the registers belong to the normal equations here)
+            pre[i].x = fast_log(fmax(pre[i].x, min_signal));
+            pre[i].y = fast_log(fmax(pre[i].y, min_signal));
+            if (i & 1) __builtin_amdgcn_sched_barrier(0);
+        }
+        int vol = vol0, adr = adr0;
+#pragma unroll
+        for (int i = 0; i < kDtiPre; i++) {
+            const int e = 2 * (tid + i * kDtiThreads);
+            if (e < cnt) yl[adr] = pre[i].x;
+            if (e + 1 < cnt) yl[vol + 1 == nS ? adr + 1 + ldl - nS : adr + 1] = pre[i].y;
+            vol += step_vol; adr += step_adr;
+            if (vol >= nS) { vol -= nS; adr += ldl - nS; }
+        }
+        __syncthreads();                               // log-signals of this tile are in LDS
+        const long long nt = tile + gridDim.x;
+        if (nt < n_tiles) {
+            const long long w0 = nt * tv;
+            dti_prefetch(pre, y + w0 * nS, (int)((n - w0) < tv ? (n - w0) : tv) * nS, tid);
+        }
+        const int vox = tid / kDtiLanes, q = tid % kDtiLanes;
+        const bool live = vox < nv;
+        double *yr = yl + (live ? vox : 0) * ldl;      // (lanes without a voxel go through the motions on row 0 and store nothing)
+        // pass 1: all seven OLS parameters (ln S0 is needed for the weights), in the scaled parametrisation
+        double p[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        for (int v = q; v < nS; v += kDtiLanes) {
+            const double ly = yr[v];
+            const double *w = wl + v * 7;
+#pragma unroll
+            for (int k = 0; k < 7; k++) p[k] = fma(w[k], ly, p[k]);
+        }
+#pragma unroll
+        for (int k = 0; k < 7; k++) p[k] = lanes_sum(p[k]);
+        // pass 2: weighted normal equations; a voxel whose system is not positive definite keeps the OLS parameters
+        {
+            double G[28], g[7];
+            wls_pass(xl, yr, nS, q, p, G, g);
+            bool ok = chol_solve7(G, g, 0.0);
+#pragma unroll
+            for (int k = 0; k < 7; k++) ok = ok && fabs(g[k]) < 1e300;
+#pragma unroll
+            for (int k = 0; k < 7; k++) p[k] = ok ? g[k] : p[k];
+        }
+        if constexpr (NLLS) {
+            // the row becomes the signal itself (each lane its own entries; nobody else reads them before the next barrier)
+            double ss = 0.0;
+            for (int v = q; v < nS; v += kDtiLanes) {
+                const double sv = exp(yr[v]);
+                if (live) yr[v] = sv;
+                ss = fma(sv, sv, ss);
+            }
+            ss = lanes_sum(ss);
+            // normal equations of the accepted point: parked in LDS between trips (every lane of the voxel writes the same bits
+            // and reads its own back, so no ordering between lanes is needed); registers hold one set of 35 sums at a time
+            double *gv = gl + (live ? vox : 0) * kDtiNormLd;
+            double c, p0[7];
+#pragma unroll
+            for (int k = 0; k < 7; k++) p0[k] = p[k];
+            {
+                double G[28], g[7];
+                nlls_pass(xl, yr, nS, q, p, c, G, g);
+                if (live) {
+#pragma unroll
+                    for (int k = 0; k < 28; k++) gv[k] = G[k];
+#pragma unroll
+                    for (int k = 0; k < 7; k++) gv[28 + k] = g[k];
+                }
+            }
+            bool failed = live && !(c < 1e300);
+            bool active = live && !failed;
+            double lam = 1e-3;
+            const double floor_c = 1e-30 * ss;         // an exact fit (7 volumes) ends at rounding noise of the signal, not at zero
+            int trips = 0, wtrips = 0;
+#pragma unroll 1
+            for (int trip = 0; trip < kLmTrips; trip++) {
+                if (!__any(active)) break;             // the loop is uniform over the wavefront: the shuffles see every lane
+                wtrips++;
+                double pt[7];
+                bool ok;
+                {
+                    double G[28], g[7];
+#pragma unroll
+                    for (int k = 0; k < 28; k++) G[k] = gv[k];
+#pragma unroll
+                    for (int k = 0; k < 7; k++) g[k] = gv[28 + k];
+                    ok = chol_solve7(G, g, lam);
+#pragma unroll
+                    for (int k = 0; k < 7; k++) pt[k] = ok ? p[k] + g[k] : p[k];
+                }
+                double ct, Gt[28], gt[7];
+                nlls_pass(xl, yr, nS, q, pt, ct, Gt, gt);
+                if (active) {
+                    trips++;
+                    const bool acc = ok && ct <= c;    // (false for a non-finite trial cost)
+                    const bool flat = ok && fabs(c - ct) <= fma(1e-15, c, floor_c);
+                    if (acc) {
+#pragma unroll
+                        for (int k = 0; k < 7; k++) { p[k] = pt[k]; gv[28 + k] = gt[k]; }
+#pragma unroll
+                        for (int k = 0; k < 28; k++) gv[k] = Gt[k];
+                        c = ct;
+                        lam = fmax(lam * 0.1, 1e-12);
+                    } else {
+                        lam *= 10.0;
+                    }
+                    if (flat && trip >= 2) active = false;                  // converged: the cost has stopped moving in fp64
+                    else if (lam > 1e12) { active = false; failed = true; }
+                }
+            }
+            failed = failed || active;                 // trip cap
+#pragma unroll
+            for (int k = 0; k < 7; k++) p[k] = failed ? p0[k] : p[k];
+            const bool head = live && q == 0;
+            const int nf = wave_sum(head && failed ? 1 : 0), vt = wave_sum(head ? trips : 0), wt = wave_sum(head ? wtrips : 0);
+            if ((tid & 63) == 0) {
+                if (nf) atomicAdd(stats, (unsigned long long)nf);
+                atomicAdd(stats + 1, (unsigned long long)vt);
+                atomicAdd(stats + 2, (unsigned long long)wt);
+            }
+        }
+        if (q == 0 && live) {
+#pragma unroll
+            for (int k = 0; k < 6; k++) dl[(slot * tv + vox) * 7 + k] = p[k] * sc.ics[k];
+        }
+        slot++;
+        __syncthreads();                               // tensors in LDS; the signal rows may be overwritten
+        if (slot == kDtiBatch || nt >= n_tiles) {
+            if (eslot < slot) {
+                const long long e0 = (batch_tile + (long long)eslot * gridDim.x) * tv;
+                if (e0 + evox < n) {
+                    double d[6], o[3];
+#pragma unroll
+                    for (int k = 0; k < 6; k++) d[k] = dl[(eslot * tv + evox) * 7 + k];
+                    principal_direction(d, o);
+                    double *dst = dirs + (e0 + evox) * 3;
+                    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+                }
+            }
+            slot = 0;
+            batch_tile = nt;
+        }
+    }
+}
+
 }  // namespace amx
 
 extern "C" {
 
-int amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_signal, amx_dti **out)
+int amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method,
+                          amx_dti **out)
 {
     if (!ctx) return AMX_E_BADARG;
     if (!inv_design || !out || nS < 7 || nS > 2048) return amx_bad(ctx, "amx_dti_create: need inv_design f64[7][nS], 7 <= nS <= 2048");
     if (!(min_signal > 0.0)) return amx_bad(ctx, "amx_dti_create: min_signal must be positive");
+    if (method != AMX_DTI_OLS && method != AMX_DTI_WLS && method != AMX_DTI_NLLS)
+        return amx_bad(ctx, "amx_dti_create_method: method must be AMX_DTI_OLS, AMX_DTI_WLS or AMX_DTI_NLLS");
+    if (method != AMX_DTI_OLS && !design) return amx_bad(ctx, "amx_dti_create_method: WLS and NLLS need the design matrix f64[nS][7]");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<double> wt((size_t)nS * 6);
     for (int v = 0; v < nS; v++)
         for (int k = 0; k < 6; k++) wt[(size_t)v * 6 + k] = inv_design[(size_t)k * nS + v];
     amx_dti *h = new amx_dti;
-    h->ctx = ctx; h->nS = nS; h->min_signal = min_signal;
+    h->ctx = ctx; h->nS = nS; h->min_signal = min_signal; h->method = method;
     hipError_t e = hipMalloc((void **)&h->wt, wt.size() * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(h->wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice);
+    if (e == hipSuccess && method != AMX_DTI_OLS) {
+        // columns of the design matrix scaled to unit max-abs: the fit runs in p * scale, the kernel undoes it on the tensor
+        std::vector<double> tab((size_t)nS * 14);                   // [nS][7] scaled pinv^T, then [nS][7] scaled design
+        for (int k = 0; k < 7; k++) {
+            double cs = 0.0;
+            for (int v = 0; v < nS; v++) cs = std::fmax(cs, std::fabs(design[(size_t)v * 7 + k]));
+            if (!(cs > 0.0) || !std::isfinite(cs)) cs = 1.0;
+            h->ics[k] = 1.0 / cs;
+            for (int v = 0; v < nS; v++) {
+                tab[(size_t)v * 7 + k] = inv_design[(size_t)k * nS + v] * cs;
+                tab[(size_t)(nS + v) * 7 + k] = design[(size_t)v * 7 + k] / cs;
+            }
+        }
+        e = hipMalloc((void **)&h->wt7, tab.size() * sizeof(double) + 4 * sizeof(unsigned long long));
+        if (e == hipSuccess) e = hipMemcpy(h->wt7, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
+        if (e == hipSuccess) {
+            h->xs = h->wt7 + (size_t)nS * 7;
+            h->stats = reinterpret_cast<unsigned long long *>(h->wt7 + (size_t)nS * 14);
+            e = hipMemset(h->stats, 0, 4 * sizeof(unsigned long long));
+        }
+    }
     if (e != hipSuccess) {
         if (h->wt) (void)hipFree(h->wt);
+        if (h->wt7) (void)hipFree(h->wt7);
         delete h;
         ctx->err = std::string("amx_dti_create: ") + hipGetErrorString(e);
         return AMX_E_HIP;
@@ -166,15 +523,84 @@ int amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_si
     return AMX_OK;
 }
 
+int amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_signal, amx_dti **out)
+{
+    return amx_dti_create_method(ctx, nullptr, inv_design, nS, min_signal, AMX_DTI_OLS, out);
+}
+
 void amx_dti_destroy(amx_dti *h)
 {
     if (!h) return;
     if (h->ctx) (void)hipSetDevice(h->ctx->device);
     if (h->wt) (void)hipFree(h->wt);
+    if (h->wt7) (void)hipFree(h->wt7);
     delete h;
 }
 
+static int dti_read_stats(amx_ctx *ctx, const amx_dti *h, unsigned long long (&st)[3])
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_last_stats: not an estimator of this ctx");
+    st[0] = st[1] = st[2] = 0;
+    if (h->method != AMX_DTI_NLLS) return AMX_OK;
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    HIPCHK(ctx, hipStreamSynchronize(h->last_stream));
+    HIPCHK(ctx, hipMemcpy(st, h->stats, sizeof st, hipMemcpyDeviceToHost));
+    return AMX_OK;
+}
+
+int amx_dti_last_unconverged(amx_ctx *ctx, const amx_dti *h, int64_t *out)
+{
+    if (ctx && !out) return amx_bad(ctx, "amx_dti_last_unconverged: null output");
+    unsigned long long st[3];
+    const int rc = dti_read_stats(ctx, h, st);
+    if (rc == AMX_OK) *out = (int64_t)st[0];
+    return rc;
+}
+
+int amx_dti_last_trips(amx_ctx *ctx, const amx_dti *h, int64_t *out_voxel_trips, int64_t *out_wavefront_trips)
+{
+    if (ctx && (!out_voxel_trips || !out_wavefront_trips)) return amx_bad(ctx, "amx_dti_last_trips: null output");
+    unsigned long long st[3];
+    const int rc = dti_read_stats(ctx, h, st);
+    if (rc == AMX_OK) { *out_voxel_trips = (int64_t)st[1]; *out_wavefront_trips = (int64_t)st[2]; }
+    return rc;
+}
+
 }  // extern "C"
+
+template <typename YT, bool NLLS>
+static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, hipStream_t s)
+{
+    const int nS = h->nS;
+    int ldl = (nS + 3) & ~3;
+    if (((ldl >> 2) & 1) == 0) ldl += 4;
+    int tv = (kDtiPre * 2 * kDtiThreads) / nS;
+    tv = tv > kDtiVox ? kDtiVox : (tv & ~1);
+    // the two [nS][7] tables (scaled pinv, scaled design matrix), the signal rows, the tensors of a batch, NLLS' normal equations
+    const size_t lds = ((size_t)((nS * 14 + 1) & ~1) + (size_t)tv * ldl + (size_t)kDtiBatch * tv * 7 +
+                        (NLLS ? (size_t)tv * kDtiNormLd : 0)) * sizeof(double);
+    if (tv < 2 || lds > 160 * 1024) return amx_bad(ctx, "amx_dti_directions: scheme too long for the LDS tile");
+    static bool attr_set[64];
+    if (!attr_set[ctx->device & 63]) {
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs_w<YT, NLLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        attr_set[ctx->device & 63] = true;
+    }
+    const long long n_tiles = (n_vox + tv - 1) / tv;
+    const int per_cu = (int)((160 * 1024) / lds) < 1 ? 1 : (int)((160 * 1024) / lds);
+    long long grid = 256LL * (per_cu > 8 ? 8 : per_cu);
+    if (grid > n_tiles) grid = n_tiles;
+    DtiScale sc;
+    for (int k = 0; k < 7; k++) sc.ics[k] = h->ics[k];
+    if (NLLS) HIPCHK(ctx, hipMemsetAsync(h->stats, 0, 4 * sizeof(unsigned long long), s));
+    h->last_stream = s;
+    rec(ctx, 8, s);
+    hipLaunchKernelGGL((k_dti_dirs_w<YT, NLLS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt7, h->xs, sc, nS, ldl, tv,
+                       (long long)n_vox, h->min_signal, d_dirs, h->stats);
+    HIPCHK(ctx, hipGetLastError());
+    rec(ctx, 9, s);
+    return AMX_OK;
+}
 
 template <typename YT>
 static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, void *hip_stream)
@@ -187,6 +613,8 @@ static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int
     if (sizeof(YT) == 8 && ((uintptr_t)d_y & 15) != 0) return amx_bad(ctx, "amx_dti_directions: y must be 16-byte aligned");
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (h->method == AMX_DTI_WLS) return dti_directions_w_dev<YT, false>(ctx, h, d_y, n_vox, d_dirs, s);
+    if (h->method == AMX_DTI_NLLS) return dti_directions_w_dev<YT, true>(ctx, h, d_y, n_vox, d_dirs, s);
     const int nS = h->nS;
     int ldl = (nS + 3) & ~3;                  // row stride = 4 * odd doubles: the 16 quads of a wavefront read
     if (((ldl >> 2) & 1) == 0) ldl += 4;      // conflict-free LDS rows

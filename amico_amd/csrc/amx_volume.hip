@@ -553,6 +553,13 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
         if (dti->ctx != ctx || !d_dirs) return amx_bad(ctx, "amx_prep_gather_directions: not a tensor helper of this ctx / null buffer");
         if (dti->nS != p->n_out) return amx_bad(ctx, "amx_prep_gather_directions: the tensor helper's scheme does not match the plan's output volumes");
     }
+    if (dti != nullptr && dti->method != AMX_DTI_OLS) {
+        // the fused kernel carries the OLS arithmetic only: the other methods fit the rows the gather wrote
+        const int rc = prep_gather_dev(ctx, p, d_img, normalize, b0_threshold, d_y, d_y32, d_mean_b0, hip_stream, nullptr, nullptr);
+        if (rc != AMX_OK) return rc;
+        return d_y32 ? amx_dti_directions_device_f32(ctx, dti, d_y32, p->n_vox, d_dirs, hip_stream)
+                     : amx_dti_directions_device(ctx, dti, d_y, p->n_vox, d_dirs, hip_stream);
+    }
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     PrepArgs a;

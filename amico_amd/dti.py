@@ -6,6 +6,8 @@ Mirrors what `Evaluation.fit` does before `model.fit` (core.py:431-436, 456-458)
     DTI  = dti.TensorModel(gtab, fit_method='OLS')
     DIRs = np.squeeze(DTI.fit(y).directions)
 
+and the same with `fit_method` 'WLS' or 'NLLS' (the configuration's DTI_fit_method, core.py:419-420, 436).
+
 The one-off part (gradient table, design matrix, pseudo-inverse: a 7 x nS matrix per scheme) is host numpy,
 like the reference; the per-voxel part (log, contraction, 3x3 eigen-decomposition) runs on the GPU through
 `amx_dti_directions*` (include/amico_amd.h).  There is no CPU fallback.
@@ -51,19 +53,49 @@ def design_matrix(bvals, bvecs):
     return -B
 
 
-class TensorDirections:
-    """`TensorModel(gtab, fit_method='OLS').fit(y).directions` of the reference's call site, on the GPU."""
+FIT_METHODS = {'OLS': 'OLS', 'LS': 'OLS', 'WLS': 'WLS', 'NLLS': 'NLLS'}
+ROBUST_METHODS = ('RT', 'RESTORE', 'restore')
+# core.py:419-420 of the reference
+FIT_METHOD_ERROR = ("DTI fit method must be one of the following:\n'OLS'(default) or 'LS': ordinary least squares\n"
+                    "'WLS': weighted least squares\n'NLLS': non-linear least squares\n"
+                    "'RT' or 'RESTORE' or 'restore': robust tensor\n"
+                    "NOTE: more info at https://dipy.org/documentation/1.6.0./reference/dipy.reconst/#dipy.reconst.dti.TensorModel")
 
-    def __init__(self, bvals, bvecs, min_signal=None, ctx=None):
+
+def check_fit_method(name):
+    """the reference's check of `DTI_fit_method` (core.py:419-420): ValueError for a name it does not know"""
+    if name not in FIT_METHODS and name not in ROBUST_METHODS:
+        raise ValueError(FIT_METHOD_ERROR)
+
+
+class TensorDirections:
+    """`TensorModel(gtab, fit_method=...).fit(y).directions` of the reference's call site, on the GPU.
+
+    fit_method as the reference spells it: 'OLS' | 'LS' (log-linear least squares), 'WLS' (dipy's wls_fit_tensor: the
+    log-linear fit weighted by the signal the OLS fit predicts), 'NLLS' (nlls_fit_tensor: the minimum of
+    sum (s - exp(X p))^2 next to the linear fit).  The robust fits need a noise estimate that the reference's call
+    never passes, so dipy raises for them there; here they are a NotImplementedError."""
+
+    def __init__(self, bvals, bvecs, min_signal=None, ctx=None, fit_method='OLS'):
         from .models import get_context
+        check_fit_method(fit_method)
+        if fit_method in ROBUST_METHODS:
+            raise NotImplementedError("DTI_fit_method %r: the robust tensor fit needs a noise estimate (sigma), which the "
+                                      "reference's own call (TensorModel(gtab, fit_method=...)) does not pass either: "
+                                      "it fails inside dipy" % (fit_method,))
         if min_signal is not None and min_signal <= 0:
             raise ValueError('The `min_signal` key-word argument needs to be strictly positive.')   # dipy's check
+        self.fit_method = FIT_METHODS[fit_method]
         self.bvals, self.bvecs = gradient_table(bvals, bvecs)
         self.design = design_matrix(self.bvals, self.bvecs)
         self.inv_design = np.linalg.pinv(self.design)
         self.min_signal = MIN_POSITIVE_SIGNAL if min_signal is None else float(min_signal)
         self.ctx = ctx if ctx is not None else get_context()
-        self._dti = _capi.Dti(self.ctx, self.inv_design, self.min_signal)
+        self._dti = _capi.Dti(self.ctx, self.inv_design, self.min_signal, design=self.design, method=self.fit_method)
+
+    def last_unconverged(self):
+        """NLLS: voxels of the last call that kept their starting (WLS) parameters, dipy's fallback; 0 otherwise"""
+        return self._dti.last_unconverged()
 
     @classmethod
     def from_scheme(cls, scheme, do_merge_b0=False, **kw):

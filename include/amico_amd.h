@@ -250,7 +250,30 @@ int amx_lasso_batched_device(amx_ctx *ctx, const amx_dict *dict, const int32_t *
  * min_signal = dipy's MIN_POSITIVE_SIGNAL (1e-4) unless the caller configured another.                        */
 typedef struct amx_dti amx_dti;
 int  amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_signal, amx_dti **out);
+/* The reference hands the configuration's DTI_fit_method to TensorModel (core.py:419-420, 436).  Besides 'OLS' | 'LS' above:
+ *   WLS  (dipy/reconst/dti.py: wls_fit_tensor)  X = design matrix, s = max(y, min_signal):  p_ols = pinv(X) log s;
+ *        w = exp(X p_ols), the signal the OLS fit predicts;  p = argmin sum_i w_i^2 (log s_i - X_i p)^2
+ *        (dipy: pinv(X * w[:, None]) @ (w * log s)); direction from p[0:6] as above.
+ *   NLLS (dipy/reconst/dti.py: nlls_fit_tensor, weighting=None)  p = argmin sum_i (s_i - exp(X_i p))^2, the local minimum
+ *        next to the linear fit.  dipy runs MINPACK's Levenberg-Marquardt from a linear fit with an analytic Jacobian (which
+ *        linear fit has changed between dipy releases; the minimum does not depend on it except in pathological voxels) and
+ *        keeps the starting parameters when the solve fails.  Here: Levenberg-Marquardt from the WLS solution, run until the
+ *        cost stops moving in fp64 -- MINPACK at dipy's default tolerances stops earlier, so the two agree to MINPACK's
+ *        stopping rule, not to rounding.  A voxel that reaches the trip cap or a non-finite value keeps the WLS parameters
+ *        and is counted (amx_dti_last_unconverged); no error is raised, as in the reference.
+ * 'RT' / 'RESTORE' are not built: the reference's call passes no sigma and raises inside dipy for them.
+ * design f64[nS][7] (host, C-order) = dipy.reconst.dti.design_matrix(gtab), needed for WLS / NLLS (may be NULL for OLS);
+ * both fits run in fp64 on the design matrix with its columns scaled to unit max-abs.  Schemes whose two [nS][7] tables and
+ * signal tile exceed the 160 KB of LDS are refused by amx_dti_directions* ("scheme too long").                              */
+enum { AMX_DTI_OLS = 0, AMX_DTI_WLS = 1, AMX_DTI_NLLS = 2 };
+int  amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method,
+                           amx_dti **out);
 void amx_dti_destroy(amx_dti *h);
+/* voxels of the last NLLS call on this handle that kept their starting parameters (0 for the other methods); waits for that call */
+int amx_dti_last_unconverged(amx_ctx *ctx, const amx_dti *h, int64_t *out);
+/* Levenberg-Marquardt trips of the last NLLS call: summed over its voxels, and summed over the trips their wavefronts ran for
+ * them (a voxel that has converged idles until the last of the 8 voxels of its wavefront has)                                */
+int amx_dti_last_trips(amx_ctx *ctx, const amx_dti *h, int64_t *out_voxel_trips, int64_t *out_wavefront_trips);
 /* y f64[n_vox][nS] -> dirs f64[n_vox][3]; host buffers (blocking) / device buffers (enqueued on hip_stream) */
 int amx_dti_directions(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double *out_dirs);
 /* (_f32: float32 signals, the dtype amx_prep_gather_device_f32 leaves them in -- same arithmetic, half the bytes)                */
@@ -298,7 +321,8 @@ int amx_prep_gather_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
 /* The gather with the tensor fit taken along (round 5): y AND the principal directions of core.py:431-436, 456-458 in ONE pass over
  * the image -- lane = voxel contracts log(max(y, min_signal)) with the helper's pseudo-inverse while the voxel's values are in the
  * gather's LDS tile; what amx_prep_gather_device[_f32] followed by amx_dti_directions_device[_f32] computes (y bit-identical, the
- * directions to rounding: the sum over the volumes runs in index order here).  h: amx_dti_create for the plan's n_out volumes.     */
+ * directions to rounding: the sum over the volumes runs in index order here).  h: amx_dti_create for the plan's n_out volumes.
+ * With a WLS / NLLS handle the call is exactly those two kernels, one after the other.                                             */
 int amx_prep_gather_directions_device(amx_ctx *ctx, const amx_prep *p, const amx_dti *h, const float *d_img, int normalize,
                                       float b0_threshold, double *d_y, float *d_mean_b0, double *d_dirs, void *hip_stream);
 int amx_prep_gather_directions_device_f32(amx_ctx *ctx, const amx_prep *p, const amx_dti *h, const float *d_img, int normalize,
