@@ -26,6 +26,8 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
            'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
+           'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
+           'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
            'amx_lut_resample', 'amx_lut_rotate_resample',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device']
 
@@ -165,6 +167,14 @@ def lib():
     L.amx_prep_mean_b0_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp]
     L.amx_prep_scatter.argtypes = [c_vp, c_vp, c_dp, C.c_int, c_fp]
     L.amx_prep_scatter_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp]
+    L.amx_debias_rows.argtypes = [c_vp, c_dp, C.c_int64, C.c_int, c_i32p, C.c_int, C.c_double, c_dp]
+    L.amx_debias_rows_f32.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_i32p, C.c_int, C.c_double, c_dp]
+    for f_ in (L.amx_debias_rows_device, L.amx_debias_rows_device_f32):
+        f_.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, c_i32p, C.c_int, C.c_double, c_vp, c_vp]      # ctx, S, n, nS, b0_idx (host), n_b0, snr, E, stream
+    L.amx_prep_set_debias_mask.argtypes = [c_vp, c_vp, C.POINTER(C.c_uint8)]
+    L.amx_prep_debias.argtypes = [c_vp, c_vp, c_fp, C.c_double]
+    L.amx_prep_debias_device.argtypes = [c_vp, c_vp, c_vp, C.c_double, c_vp]
+    L.amx_debias_last_unconverged.argtypes = [c_vp, C.POINTER(C.c_int64)]
     L.amx_lut_resample.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     L.amx_lut_rotate_resample.argtypes = [c_vp, c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     for name in SYMBOLS:
@@ -241,6 +251,12 @@ class Context:
         self.check(lib().amx_last_stats(self._h, out))
         return {'rerun_voxels': out[0], 'itercap_voxels': out[1], 'overflow_voxels': out[2],
                 'guard_trips': out[3] >> 32, 'guard_last': out[3] & 0xffffffff}
+
+    def debias_last_unconverged(self):
+        """samples of the last debias call that reached the trip cap (amx_debias_last_unconverged; waits for that call)"""
+        out = C.c_int64()
+        self.check(lib().amx_debias_last_unconverged(self._h, C.byref(out)))
+        return int(out.value)
 
     def last_host_narrowed(self):
         """batches of the last host-buffer call whose float64 signals crossed PCIe as float32, losslessly (amx_last_host_narrowed)"""
@@ -739,6 +755,25 @@ class Prep:
         self.ctx.check(lib().amx_prep_mean_b0(self.ctx._h, self._h, _p(buf, c_fp), _p(out, c_fp)))
         return out
 
+    def set_debias_mask(self, mask):
+        """mask [X, Y, Z] as given to load_data: the voxels debiasRician works on are those != 0 (preproc.py:29)"""
+        m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if m.shape != self.shape[:3]:
+            raise ValueError('mask must have the spatial shape of the image')
+        self.ctx.check(lib().amx_prep_set_debias_mask(self.ctx._h, self._h, _p(m, C.POINTER(C.c_uint8))))
+
+    def debias(self, img, snr):
+        """host image, IN PLACE: float32(E) where the mask is nonzero, 0 elsewhere (amx_prep_debias)"""
+        buf = self._img_buffer(img)
+        if not img.flags.writeable:
+            raise ValueError('the image is debiased in place and must be writeable')
+        self.ctx.check(lib().amx_prep_debias(self.ctx._h, self._h, _p(buf, c_fp), float(snr)))
+        return img
+
+    def debias_device(self, d_img, snr, stream=None):
+        """device pointer (int) of the image's element buffer, in place, enqueued on `stream`"""
+        self.ctx.check(lib().amx_prep_debias_device(self.ctx._h, self._h, c_vp(d_img), float(snr), c_vp(stream or 0)))
+
     def scatter(self, values):
         v = np.ascontiguousarray(values, dtype=np.float64)
         if v.ndim == 1:
@@ -748,6 +783,20 @@ class Prep:
         out = np.zeros(self.shape[:3] + (v.shape[1],), dtype=np.float32)
         self.ctx.check(lib().amx_prep_scatter(self.ctx._h, self._h, _p(v, c_dp), v.shape[1], _p(out, c_fp)))
         return out
+
+
+def debias_rows(ctx, S, b0_idx, snr):
+    """S f32 | f64 [n, nS] -> E f64 [n, nS]: the exact minimiser of preproc.py's functional, row by row (amx_debias_rows[_f32])"""
+    S = np.asarray(S)
+    if S.ndim != 2:
+        raise ValueError('S must be [n, nS]')
+    f32 = S.dtype == np.float32
+    S = np.ascontiguousarray(S, dtype=np.float32 if f32 else np.float64)
+    b0 = np.ascontiguousarray(b0_idx, dtype=np.int32)
+    E = np.empty(S.shape, dtype=np.float64)
+    fn = lib().amx_debias_rows_f32 if f32 else lib().amx_debias_rows
+    ctx.check(fn(ctx._h, _p(S, c_fp if f32 else c_dp), S.shape[0], S.shape[1], _p(b0, c_i32p), len(b0), float(snr), _p(E, c_dp)))
+    return E
 
 
 def lut_resample(ctx, lm, ylm_out, idx_out, nS):

@@ -2,16 +2,19 @@
 ``DIRs``, ``htable``, ``KERNELS``, ``nthreads``, ``get_config`` -- and the caller contract around the hot path for
 in-memory volumes, every per-voxel step on the GPU:
 
-  set_data   ~ load_data's preprocessing inputs (core.py:209-268): raw float32 image, scheme, mask
-  fit        b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
+  set_data   ~ load_data's preprocessing inputs (core.py:201-268): raw float32 image, scheme, mask
+  fit        Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
+             CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
+             b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
              principal directions from the tensor fit (DTI_fit_method)          -> ``DIRs``   (amx_dti_directions)
              model.fit(self)                                                    -> maps       (amx_*_fit)
              scatter into float32 volumes (core.py:472-498)                     -> ``RESULTS`` (amx_prep_scatter)
 
-NIfTI / scheme-file I/O, Rician debiasing and LUT generation stay out of scope.
+NIfTI / scheme-file I/O stays out of scope.
 """
 import inspect
 import time
+import warnings
 from os import cpu_count
 import numpy as np
 from . import models as _models
@@ -90,8 +93,20 @@ class Evaluation:
     # ---- in-memory replacement of load_data (core.py:107-278): volumes are given directly
     def set_data(self, dwi, scheme, mask=None, directions=None, b0_min_signal=0):
         """dwi [X,Y,Z,nS] raw signal (C or Fortran order), mask [X,Y,Z], directions [X,Y,Z,3] (optional peaks,
-        core.py:438-447: when absent they come from the tensor fit).  The options doNormalizeSignal / doMergeB0 /
-        doDirectionalAverage are read here, like load_data reads them."""
+        core.py:438-447: when absent they come from the tensor fit).  The options doDebiasSignal / DWI-SNR /
+        doNormalizeSignal / doMergeB0 / doDirectionalAverage are read here, like load_data reads them.
+        With doDebiasSignal the image is debiased in HBM inside fit(): `niiDWI_img` keeps the RAW image (the reference's load_data
+        replaces it with the debiased one); fit() leaves CONFIG['debias_unconverged'], the number of samples whose root search
+        reached its trip cap (0 on every signal tried; a warning is raised otherwise)."""
+        debias_snr = None
+        if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
+            debias_snr = self.get_config('DWI-SNR')
+            if debias_snr is None:
+                raise RuntimeError('Set noise variance for debiasing (eg. ae.set_config(\'RicianNoiseSigma\', sigma))')   # core.py:205
+            if scheme.b0_count == 0:
+                raise RuntimeError('No b0 volume to estimate the noise level from (doDebiasSignal)')   # preproc.py:30-31
+            if scheme.b0_count > _prep.MAX_DEBIAS_B0:
+                raise RuntimeError(f'doDebiasSignal: more than {_prep.MAX_DEBIAS_B0} b0 volumes are not supported')
         img = np.asarray(dwi)
         if img.ndim != 4:
             raise ValueError('DWI file is not a 4D image')                       # core.py:138-139
@@ -115,7 +130,7 @@ class Evaluation:
         self._prep = _prep.SignalPreparation(
             scheme, self.niiDWI_img, self.niiMASK_img, do_normalize=self.get_config('doNormalizeSignal'),
             do_merge_b0=self.get_config('doMergeB0'), do_directional_average=self.get_config('doDirectionalAverage'),
-            b0_min_signal=b0_min_signal)
+            b0_min_signal=b0_min_signal, debias_snr=debias_snr)
         # the scheme the model sees: one row per shell after the directional average (core.py:254-255)
         self.scheme = SimpleScheme(_prep.directional_average_table(scheme), scheme.b0_thr) \
             if self.get_config('doDirectionalAverage') else scheme
@@ -203,6 +218,9 @@ class Evaluation:
         img = self.niiDWI_img
         d_img = torch.from_numpy(np.lib.stride_tricks.as_strided(img, shape=(plan.extent,), strides=(4,))).to(dev)
         n = self._prep.n_vox
+        if self._prep.debias_snr is not None:
+            # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
+            self._prep._plan.debias_device(d_img.data_ptr(), self._prep.debias_snr)
         # the prepared signals stay float32 in HBM (every value of core.py:209-268 is a float32; core.py:451-452 only widen them):
         # the tensor fit and the model fit read them in place, half the bytes of the float64 rows
         d_y = torch.empty((n, self._prep.n_out), dtype=torch.float32, device=dev)
@@ -229,6 +247,11 @@ class Evaluation:
             est.fit_device(d_y.data_ptr(), n, d_dirs.data_ptr(), f32=True)
         ctx.sync()
         del d_img
+        if self._prep.debias_snr is not None:
+            # samples whose root search reached its trip cap (none on any signal tried: include/amico_amd.h); reported, not hidden
+            self.set_config('debias_unconverged', ctx.debias_last_unconverged())
+            if self.get_config('debias_unconverged'):
+                warnings.warn(f"Rician debias: {self.get_config('debias_unconverged')} samples did not converge")
         self._y, self._DIRs = None, None
         self._dev = {'y': d_y, 'dirs': d_dirs}
         self.mean_b0s = d_mb0.cpu().numpy() if self._prep.do_normalize else None

@@ -137,6 +137,11 @@ struct amx_ctx {
     bool opt_no_big_all = false;    // AMX_BIG_ALL=0: lambda1 = 0 fits take the fast kernels first and reach k_noddi_lasso_big through the overflow lists
     bool side_launch = false;       // transient: the launch being enqueued goes to the side stream (launch_pair picks its own overflow lists)
     std::string path;               // kernels of the last fit enqueued on this ctx, in launch order (amx_last_path)
+    // Rician debias (amx_debias.hip): sigma of every voxel / row of the call in flight, its b0 list, and the counter of samples that
+    // reached the trip cap in the last call (amx_debias_last_unconverged), read behind the event recorded after that call's kernels
+    DevBuf debias_sigma, debias_b0;
+    unsigned long long *debias_stats = nullptr;
+    hipEvent_t debias_ev = nullptr;
     int opt_seed_chunk = 0;        // AMX_SEED_CHUNK (0 = by the call's size, make_plan): voxels of one orientation per workgroup of the seed solvers (lanes refill from the chunk: the more voxels per lane, the smaller the share of the tail; 1 M voxels: 1024 -> 7.2 ms, 2048 -> 7.3, 4096 -> 5.5 for stage 1)
 };
 
@@ -221,6 +226,7 @@ struct amx_prep {
     // image is half background, and a strided walk over ALL tiles left some wavefronts with seven full tiles and others with none
     static constexpr int kCounterRing = 16;
     int *live64 = nullptr, *tile_counter = nullptr;
+    unsigned char *dmask = nullptr; // device u8[d2][d1][d0]: mask != 0 (amx_prep_set_debias_mask; null until then)
     mutable unsigned launch_seq = 0;
     long long n_live64 = 0;
 };

@@ -419,7 +419,7 @@ void amx_prep_destroy(amx_prep *p)
 {
     if (!p) return;
     if (p->ctx) (void)hipSetDevice(p->ctx->device);
-    void *ps[] = {p->rank, p->cidx, p->gptr, p->gidx, p->b0idx, p->live64, p->tile_counter};
+    void *ps[] = {p->rank, p->cidx, p->gptr, p->gidx, p->b0idx, p->live64, p->tile_counter, p->dmask};
     for (void *q : ps) if (q) (void)hipFree(q);
     delete p;
 }

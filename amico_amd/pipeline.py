@@ -1,5 +1,6 @@
 """Device-resident chain of the per-voxel steps: raw float32 image (in HBM) -> float32 map volumes (in HBM).
 
+    amx_prep_debias_device              Rician debias in place (optional: debias_snr)                     core.py:201-206, preproc.py:23-36
     amx_prep_gather_directions_device   b0 normalisation (+ merge / shell average), mask gather, clip     core.py:209-268, 451-452
                                         AND the principal directions (log-linear tensor fit)            core.py:428-436, 456-458
     amx_noddi_fit_device        NNLS -> LASSO -> NNLS, maps                                        models.pyx:816-991
@@ -17,7 +18,7 @@ from .models import get_context
 
 class NoddiVolumePipeline:
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
-                 b0_min_signal=0.0, device=None, fused=True):
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None):
         import torch
         self.fused = bool(fused)           # False: gather, then the tensor fit as its own pass over y (the round-4 chain; A/B)
         self.torch = torch
@@ -25,7 +26,7 @@ class NoddiVolumePipeline:
         self.dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
         self.scheme = scheme
         self.prep = _prep.SignalPreparation(scheme, img_like, mask, do_normalize=do_normalize,
-                                            b0_min_signal=b0_min_signal, ctx=self.ctx)
+                                            b0_min_signal=b0_min_signal, ctx=self.ctx, debias_snr=debias_snr)
         if b0_min_signal != 0.0:
             raise NotImplementedError('b0_min_signal needs the whole-volume b0 mean on the host: use Evaluation')
         self.tensor = _dti.TensorDirections.from_scheme(scheme, ctx=self.ctx)
@@ -42,9 +43,12 @@ class NoddiVolumePipeline:
         self.dirs_vol = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
 
     def enqueue(self, d_img, stream=None):
-        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`)"""
+        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`); with debias_snr
+        set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere"""
         L, c, p = _capi.lib(), self.ctx, self.prep._plan
         s = _capi.c_vp(stream or 0)
+        if self.prep.debias_snr is not None:
+            p.debias_device(d_img.data_ptr(), self.prep.debias_snr, stream)
         if self.fused:
             # one pass over the image: the tensor fit rides on the gather's LDS tile (amx_prep_gather_directions_device_f32)
             c.check(L.amx_prep_gather_directions_device_f32(c._h, p._h, self.tensor._dti._h, d_img.data_ptr(), int(self.prep.do_normalize), 0.0,

@@ -1,12 +1,15 @@
 """Signal preparation around the fit (SURVEY section 8 f, rows 2-3), host side.
 
 What `Evaluation.load_data` does to the 4-D image after reading it (core.py:209-268) and what `Evaluation.fit`
-does to get `y` (core.py:451-452) and to store the results (core.py:472-498), planned once per (image geometry,
+does to get `y` (core.py:451-452) and to store the results (core.py:472-498), with the optional Rician debias in front
+(core.py:201-206 -> preproc.py:23-36), planned once per (image geometry,
 mask, scheme, options) and executed on the GPU through `amx_prep_*` (include/amico_amd.h).  No CPU fallback.
 """
 import numpy as np
 
 from . import _capi
+
+MAX_DEBIAS_B0 = 128      # b0 volumes the debias kernel sums in numpy's order (include/amico_amd.h)
 
 
 def volume_groups(scheme, do_merge_b0=False, do_directional_average=False):
@@ -38,7 +41,9 @@ class SignalPreparation:
     """image [X, Y, Z, nS] float32 (any strides) + mask -> y f64[n_vox, n_out]; per-voxel results -> volumes."""
 
     def __init__(self, scheme, img_like, mask, do_normalize=True, do_merge_b0=False, do_directional_average=False,
-                 b0_min_signal=0.0, ctx=None):
+                 b0_min_signal=0.0, ctx=None, debias_snr=None):
+        """debias_snr (DWI-SNR, or None = doDebiasSignal off): the image is debiased first, on the voxels with mask != 0
+        (preproc.py:29), and is zero elsewhere (preproc.py:24)"""
         from .models import get_context
         if img_like.ndim != 4 or img_like.dtype != np.float32:
             raise ValueError('DWI image must be a 4D float32 array')
@@ -50,6 +55,11 @@ class SignalPreparation:
             raise ValueError('image strides must be positive multiples of the element size')
         if do_normalize and scheme.b0_count == 0:
             raise RuntimeError('No b0 volume to normalize signal with')                 # core.py:214-215
+        if debias_snr is not None and scheme.b0_count == 0:
+            raise RuntimeError('No b0 volume to estimate the noise level from (doDebiasSignal)')   # preproc.py:30-31: sigma = mean(b0) / SNR
+        if debias_snr is not None and scheme.b0_count > MAX_DEBIAS_B0:
+            raise RuntimeError(f'doDebiasSignal: more than {MAX_DEBIAS_B0} b0 volumes are not supported')
+        self.debias_snr = None if debias_snr is None else float(debias_snr)
         self.scheme = scheme
         self.do_normalize = bool(do_normalize)
         self.b0_min_signal = float(b0_min_signal)
@@ -62,16 +72,26 @@ class SignalPreparation:
                                 scheme.b0_idx, overwrite_in_order=bool(do_directional_average))
         self.n_vox, self.n_out = self._plan.n_vox, self._plan.n_out
         self.mean_b0s = None
+        if self.debias_snr is not None:
+            self._plan.set_debias_mask(mask)
+
+    def debias(self, img):
+        """-> the debiased float32 image (a copy in the same layout; `img` itself when debias_snr is None)"""
+        if self.debias_snr is None:
+            return img
+        out = np.lib.stride_tricks.as_strided(np.array(self._plan._img_buffer(img)), shape=img.shape, strides=img.strides)
+        return self._plan.debias(out, self.debias_snr)
 
     def b0_threshold(self, img):
         """right-hand side of core.py:217; needs the b0 mean of every voxel only when b0_min_signal != 0"""
         if not self.do_normalize or self.b0_min_signal == 0.0:
             return np.float32(0.0)
-        mean_b0s = self._plan.mean_b0(img)
+        mean_b0s = self._plan.mean_b0(img)                                               # (of the debiased image: zero outside its mask)
         return self.b0_min_signal * mean_b0s[mean_b0s > 0].mean()
 
     def gather(self, img):
         """-> (y f64[n_vox, n_out], mean_b0 f32[n_vox] of the masked voxels or None)"""
+        img = self.debias(img)
         y, mb0 = self._plan.gather(img, self.do_normalize, float(self.b0_threshold(img)))
         self.mean_b0s = mb0
         return y, mb0

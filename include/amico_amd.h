@@ -336,6 +336,40 @@ int amx_prep_scatter(amx_ctx *ctx, const amx_prep *p, const double *values, int 
 int amx_prep_scatter_device(amx_ctx *ctx, const amx_prep *p, const double *d_values, int n_cols,
                             float *d_volume, void *hip_stream);
 
+/* (f0) Rician debias of the raw signal, core.py:201-206 (doDebiasSignal, DWI-SNR) -> preproc.py:23-36 `debiasRician`:
+ *     per voxel with mask != 0:  sigma = DWI[ix,iy,iz,b0_idx].mean() / SNR;  E = argmin_E sum_i (S_i - mu(E_i))^2  from E = S,
+ *     mu(e) = sigma sqrt(pi/2) L_{1/2}(-e^2 / (2 sigma^2))  (preproc.py:8-12), the mean of a Rician variable of amplitude e;
+ *     voxels outside the mask become 0; the result replaces the image before normalisation, b0 merge and shell average.
+ * The functional is separable and mu is increasing and convex on e >= 0, mu(0) = |sigma| sqrt(pi/2) (the noise floor): its minimiser
+ * is E_i = mu^-1(S_i) for a sample above the floor and E_i = 0 for one at or below it (zero and negative samples included).  These
+ * entry points compute THAT minimiser, sample by sample in fp64 (Newton's method, residual |mu(E) - S| of a few ulp of S); the
+ * reference's L-BFGS-B run stops on its relative-reduction test 1e-5 .. 1e-3 b0 away from it ("Rician debias").
+ * The b0 mean is taken in the samples' own precision and in numpy's summation order (so `S[b0_idx].mean()` on the host gives the same
+ * bits; at most 128 b0 volumes), sigma = that mean / snr and everything after it in fp64.  Only sigma^2 enters: a negative b0 mean
+ * acts like its absolute value.  A voxel whose b0 mean is exactly 0 (or not finite) has no sigma -- the reference's objective is NaN
+ * for every E there -- and keeps its samples as they are; a NaN sample stays NaN.  A sample whose iteration reaches its trip cap (32;
+ * a CPU trial of the same arithmetic needed at most 5 evaluations for S up to 1e7 sigma) is written as it stands and counted:
+ * amx_debias_last_unconverged.
+ * One debias call per ctx in flight at a time (the per-voxel sigma lives in the ctx).
+ *
+ * rows form:   S f64 | f32 [n][nS] (C order), b0_idx int32[n_b0] (HOST memory in both forms) -> E f64[n][nS]                      */
+int amx_debias_rows(amx_ctx *ctx, const double *S, int64_t n, int nS, const int32_t *b0_idx, int n_b0, double snr, double *out_E);
+int amx_debias_rows_f32(amx_ctx *ctx, const float *S, int64_t n, int nS, const int32_t *b0_idx, int n_b0, double snr, double *out_E);
+int amx_debias_rows_device(amx_ctx *ctx, const double *d_S, int64_t n, int nS, const int32_t *b0_idx, int n_b0, double snr,
+                           double *d_E, void *hip_stream);
+int amx_debias_rows_device_f32(amx_ctx *ctx, const float *d_S, int64_t n, int nS, const int32_t *b0_idx, int n_b0, double snr,
+                               double *d_E, void *hip_stream);
+/* image form, in place: the float32 image of a plan in its own layout; voxels with mask != 0 (preproc.py:29 -- where the fit gathers
+ * mask == 1, core.py:451) get float32(E), all others 0.  The reference carries float64 from here on; one rounding to float32 costs
+ * 6e-8 relative and lets amx_prep_mean_b0* / amx_prep_gather* read the result unchanged.  mask u8[X][Y][Z] (host, C order) is
+ * uploaded into the plan once.  Scheme and b0 list are the plan's; a plan without b0 volumes is refused.                          */
+int amx_prep_set_debias_mask(amx_ctx *ctx, amx_prep *p, const uint8_t *mask);
+int amx_prep_debias(amx_ctx *ctx, const amx_prep *p, float *img, double snr);
+int amx_prep_debias_device(amx_ctx *ctx, const amx_prep *p, float *d_img, double snr, void *hip_stream);
+/* samples of the last debias call on this ctx that reached the trip cap; waits for that call (an event recorded behind its kernels: the
+ * stream it was enqueued on may be gone by then) */
+int amx_debias_last_unconverged(amx_ctx *ctx, int64_t *out);
+
 /* (f4) LUT resampling to the subject's scheme, lut.pyx:274-311 `resample_kernel` (called per atom by
  * NODDI.resample models.pyx:754-792, FreeWater.resample :1113-1144, ...):
  *     KR = np.ones((ndirs, nS), float32);  KR[i, idx_out] = np.dot(Ylm_out, KRlm[i, :])   for i in range(ndirs)
