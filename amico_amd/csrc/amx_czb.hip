@@ -9,7 +9,7 @@ static int go(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)
     constexpr int NW = 8;
     return launch_pair<NW>(ctx, a, pl, s, k_czb<NR, NQ, MP, NW, false>, k_czb<NR, NQ, MB, 1, true>,
                            [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MP, true) + ((size_t)a.c.n_atoms * a.ldG + (size_t)(MP + 1) * (MP + 2) + MP + 1) * sizeof(double) + 16; },
-                           fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, true), 0, 2);
+                           fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, true), 0, 2, NR == 2 ? "k_czb<2>" : (NR == 4 ? "k_czb<4>" : "k_czb<8>"));
 }
 
 // lambda2 below what the Gram form can take: thin QR in A-space (the other models route small ridges there too)
@@ -19,7 +19,8 @@ static int go_qr(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)
     constexpr int NQ = 1, MP = 32, MB = 64;
     constexpr int NW = 4;
     return launch_pair<NW>(ctx, a, pl, s, k_czb_qr<NR, NQ, MP, NW, false>, k_czb_qr<NR, NQ, MB, 1, true>,
-                           [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MP); }, fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB), 0, 2);
+                           [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MP); }, fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB), 0, 2,
+                           NR == 2 ? "k_czb_qr<2>" : (NR == 4 ? "k_czb_qr<4>" : "k_czb_qr<8>"));
 }
 
 int amx_launch_czb(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)

@@ -1,0 +1,229 @@
+"""CylinderZeppelinBall in plain numpy, for the tests of the GPU routes (test_gpu_czb_paths.py, test_czb_np.py): dictionaries of any
+shape from this repository's physics, signals, the Kuhn-Tucker certificate with a long-double residual, a high-precision re-solve,
+and the map formulas of models.pyx:616-633.  CPU only; nothing here touches the library under test."""
+import numpy as np
+
+LD = np.longdouble
+
+
+# ------------------------------------------------------------------------------------------------ schemes, dictionaries
+def make_scheme(nS, b0_at='start', n_b0=None, bvals=(1000.0, 2000.0, 3000.0), seed=0):
+    """STEJSKALTANNER scheme of exactly nS volumes, three shells; b0_at = 'start' / 'middle' (n_b0 volumes, default ~6 %) or
+    'single' (one b0, first volume)"""
+    from amico_amd import synthetic as S
+    if b0_at == 'single':
+        n_b0 = 1
+    elif n_b0 is None:
+        n_b0 = max(2, nS // 16)
+    n_dwi = nS - n_b0
+    per = [n_dwi // len(bvals) + (1 if k < n_dwi % len(bvals) else 0) for k in range(len(bvals))]
+    rng = np.random.default_rng(seed)
+    Delta, delta, TE = 0.040, 0.020, 0.080
+    rows = []
+    for bv, m in zip(bvals, per):
+        G = np.sqrt(bv * 1e6 / ((S.GAMMA * delta) ** 2 * (Delta - delta / 3.0)))
+        rows.append(np.hstack([S.random_unit_vectors(m, rng), np.full((m, 1), G)]))
+    dwi = np.vstack(rows)
+    b0 = np.zeros((n_b0, 4))
+    if b0_at == 'middle':
+        h = n_dwi // 2
+        tab = np.vstack([dwi[:h], b0, dwi[h:]])
+    else:
+        tab = np.vstack([b0, dwi])
+    tab = np.hstack([tab, np.full((nS, 1), Delta), np.full((nS, 1), delta), np.full((nS, 1), TE)])
+    sch = S.SimpleScheme(tab)
+    assert sch.nS == nS and sch.b0_count == n_b0
+    return sch
+
+
+def rotation_to_z(d):
+    """the rotation that carries the unit vector d to z (Rodrigues)"""
+    d = np.asarray(d, dtype=np.float64)
+    d = d / np.linalg.norm(d)
+    z = np.array([0.0, 0.0, 1.0])
+    v, c = np.cross(d, z), float(d @ z)
+    s = np.linalg.norm(v)
+    if s < 1e-12:
+        return np.eye(3) if c > 0 else np.diag([1.0, -1.0, -1.0])
+    vx = np.array([[0.0, -v[2], v[1]], [v[2], 0.0, -v[0]], [-v[1], v[0], 0.0]])
+    return np.eye(3) + vx + vx @ vx * ((1.0 - c) / (s * s))
+
+
+def czb_kernels(scheme, lut_ids, Rs, d_perps, d_isos, d_par, lut_dirs=None, ndirs=500):
+    """KERNELS of CylinderZeppelinBall for the orientations lut_ids of lut_dirs [ndirs, 3]: wmr [n_rs, ndirs, nS], wmh
+    [n_perp, ndirs, nS], iso [n_iso, nS], float32, b0 entries exactly 1, zeros at every other orientation.  The response functions
+    are amico_amd.synthesis's for a fibre along z, evaluated on the scheme rotated so that the LUT direction maps to z."""
+    from amico_amd import synthesis as syn
+    from amico_amd import synthetic as S
+    if lut_dirs is None:
+        raise ValueError('czb_kernels needs the LUT orientations (lut_dirs)')
+    table = np.asarray(scheme.raw, dtype=np.float64)
+    b0 = np.asarray(scheme.b0_idx)
+    nS = table.shape[0]
+    K = {'model': 'CylinderZeppelinBall',
+         'wmr': np.zeros((len(Rs), ndirs, nS), dtype=np.float32), 'wmh': np.zeros((len(d_perps), ndirs, nS), dtype=np.float32),
+         'iso': np.zeros((len(d_isos), nS), dtype=np.float32)}
+
+    def put(dst, s):
+        s = np.asarray(s, dtype=np.float64).copy()
+        s[b0] = 1.0
+        dst[:] = s.astype(np.float32)
+    for lid in lut_ids:
+        t = table.copy()
+        t[:, :3] = t[:, :3] @ rotation_to_z(lut_dirs[lid]).T
+        rs = S.SimpleScheme(t)
+        cyl, zep = syn.CylinderGPD(rs), syn.Zeppelin(rs)
+        for k, R in enumerate(Rs):
+            put(K['wmr'][k, lid], cyl.get_signal(d_par, R))
+        for k, dp in enumerate(d_perps):
+            put(K['wmh'][k, lid], zep.get_signal(d_par, dp))
+    ball = syn.Ball(S.SimpleScheme(table.copy()))
+    for k, di in enumerate(d_isos):
+        put(K['iso'][k], ball.get_signal(di))
+    assert all(np.isfinite(K[k]).all() for k in ('wmr', 'wmh', 'iso'))
+    return K
+
+
+def atom_sets(n_atoms):
+    """(Rs, d_perps, d_isos) of a dictionary with n_atoms columns: the model's defaults at 26, otherwise the same ranges resampled"""
+    d_isos = np.array([2.0e-3])
+    if n_atoms == 26:
+        return np.concatenate(([0.01], np.linspace(0.5, 8.0, 20))) * 1e-6, np.array([1.19e-3, 0.85e-3, 0.51e-3, 0.17e-3]), d_isos
+    n_perp = 2 if n_atoms < 16 else 4
+    n_rs = n_atoms - n_perp - 1
+    return (np.concatenate(([0.01], np.linspace(0.5, 8.0, n_rs - 1))) * 1e-6,
+            np.linspace(1.19e-3, 0.17e-3, n_perp), d_isos)
+
+
+def dictionary(K, lid):
+    """A [nS, n_atoms] float64 of orientation lid: cylinders | zeppelins | balls (models.pyx:608-610)"""
+    return np.concatenate([K['wmr'][:, lid], K['wmh'][:, lid], K['iso']], axis=0).astype(np.float64).T
+
+
+def by_direction(lut):
+    order = np.argsort(lut, kind='stable')
+    return np.split(order, np.flatnonzero(np.diff(lut[order])) + 1)
+
+
+# ------------------------------------------------------------------------------------------------ directions, signals
+def dirs_in_cells(ori, lut_dirs, htable, rng, jitter=0.01):
+    """one direction per entry of ori [n], inside the LUT cell of that orientation (jittered about the LUT direction; redrawn until
+    the reference's rounding to whole degrees lands in the cell)"""
+    from amico_amd import synthetic as S
+    ori = np.asarray(ori, dtype=np.int64)
+    d = np.array(lut_dirs[ori], dtype=np.float64)
+    todo = np.arange(len(ori))
+    for trip in range(200):
+        v = lut_dirs[ori[todo]] + jitter * rng.standard_normal((len(todo), 3))
+        v /= np.linalg.norm(v, axis=1, keepdims=True)
+        d[todo] = v
+        todo = todo[S.lut_indices(v, htable) != ori[todo]]
+        if len(todo) == 0:
+            return np.ascontiguousarray(d)
+        if trip % 20 == 19:
+            jitter *= 0.5
+    raise RuntimeError('no direction found inside LUT cells %s' % np.unique(ori[todo]))
+
+
+def czb_signals(K, lut, rng, snr=20.0, hard=False):
+    """one cylinder + one zeppelin + the ball with Dirichlet(2, 2, 1) weights and Rician noise (float64).  hard: SNR 5, and from
+    the front of the array, cyclically over the first tenth: a pure-noise voxel, an all-zero voxel, a voxel that is exactly one
+    atom, a voxel that is only ball."""
+    n = len(lut)
+    n_rs, n_p = K['wmr'].shape[0], K['wmh'].shape[0]
+    w = rng.dirichlet([2.0, 2.0, 1.0], n)
+    k1, k2 = rng.integers(n_rs, size=n), rng.integers(n_p, size=n)
+    iso = K['iso'][0].astype(np.float64)
+    y0 = w[:, :1] * K['wmr'][k1, lut].astype(np.float64) + w[:, 1:2] * K['wmh'][k2, lut].astype(np.float64) + w[:, 2:] * iso
+    s = 1.0 / (5.0 if hard else snr)
+    y = np.abs(y0 + rng.normal(scale=s, size=y0.shape) + 1j * rng.normal(scale=s, size=y0.shape))
+    if hard:
+        m = max(4, n // 10) if n >= 4 else 0
+        idx = np.arange(m)
+        noise = idx[idx % 4 == 0]
+        y[noise] = np.abs(rng.normal(size=(len(noise), y.shape[1])))
+        y[idx[idx % 4 == 1]] = 0.0
+        ex = idx[idx % 4 == 2]
+        y[ex] = K['wmr'][k1[ex], lut[ex]].astype(np.float64)
+        y[idx[idx % 4 == 3]] = iso
+    return np.ascontiguousarray(y)
+
+
+# ------------------------------------------------------------------------------------------------ certificate
+def czb_gradient(K, lut, y, x, lam1, lam2, rows=None):
+    """g = A'(y - A x) - lambda2 x - lambda1 for every voxel of rows (default: all), float64 from a long-double residual"""
+    g = np.zeros_like(x)
+    sel = np.arange(len(lut)) if rows is None else np.asarray(rows)
+    for grp in by_direction(lut[sel]):
+        r = sel[grp]
+        A = dictionary(K, lut[r[0]]).astype(LD)
+        X = x[r].astype(LD)
+        res = y[r].astype(LD) - X @ A.T
+        g[r] = (res @ A - LD(lam2) * X - LD(lam1)).astype(np.float64)
+    return g
+
+
+def czb_certificate(K, lut, y, x, lam1, lam2, rows=None):
+    """(max |g_P|, max g_Z, min x) over the voxels of rows: the Kuhn-Tucker conditions of
+    min 1/2 |y - A x|^2 + lambda1 sum x + lambda2 / 2 |x|^2, x >= 0 -- zero on the passive atoms, <= 0 on the clamped ones"""
+    sel = np.arange(len(lut)) if rows is None else np.asarray(rows)
+    if len(sel) == 0:
+        return 0.0, 0.0, 0.0
+    g = czb_gradient(K, lut, y, x, lam1, lam2, sel)[sel]
+    P = x[sel] > 0
+    return float(np.abs(g[P]).max(initial=0.0)), float(g[~P].max(initial=0.0)), float(x[sel].min())
+
+
+def czb_resolve(A, y, lam1, lam2, refine=3):
+    """the optimum of one voxel by block principal pivoting on H = A'A + lambda2 I, every solve refined against long-double
+    residuals: (x, g) float64 -- the support of x is that of the exact optimum unless an atom is degenerate to ~1e-18"""
+    A = np.asarray(A, dtype=np.float64).astype(LD)
+    n = A.shape[1]
+    H = A.T @ A + LD(lam2) * np.eye(n, dtype=LD)
+    c = A.T @ np.asarray(y, dtype=np.float64).astype(LD) - LD(lam1)
+    H64 = H.astype(np.float64)
+    P = np.asarray(c > 0)
+    ninf, backup = n + 1, 3
+    for trip in range(20 * n + 50):
+        x = np.zeros(n, dtype=LD)
+        p = np.flatnonzero(P)
+        if len(p):
+            Hp = H64[np.ix_(p, p)]
+            xp = np.linalg.solve(Hp, c[p].astype(np.float64)).astype(LD)
+            for _ in range(refine):
+                xp = xp + np.linalg.solve(Hp, (c[p] - H[np.ix_(p, p)] @ xp).astype(np.float64)).astype(LD)
+            x[p] = xp
+        g = c - H @ x
+        bad = np.flatnonzero((P & (x <= 0)) | (~P & (g > 0)))
+        if len(bad) == 0:
+            g[P] = 0
+            return x.astype(np.float64), g.astype(np.float64)
+        if len(bad) < ninf:
+            ninf, backup = len(bad), 3
+        elif backup > 0:
+            backup -= 1
+        else:
+            bad = bad[-1:]
+        P[bad] = ~P[bad]
+    raise RuntimeError('czb_resolve: no optimum')
+
+
+# ------------------------------------------------------------------------------------------------ maps
+def czb_maps(x, Rs, n_perp):
+    """v, a, d of models.pyx:616-633 from the coefficients x [n, n_atoms], with the reference's 1e-16 guards in its order"""
+    x = np.asarray(x, dtype=np.float64)
+    Rs = np.asarray(Rs, dtype=np.float64)
+    n_rs = len(Rs)
+    f1 = x[:, :n_rs].sum(axis=1)
+    f2 = x[:, n_rs:n_rs + n_perp].sum(axis=1) + 1e-16
+    v = f1 / (f1 + f2 + 1e-16)
+    f1 = f1 + 1e-16
+    a = 1e6 * 2.0 * (x[:, :n_rs] @ Rs) / f1
+    d = (4.0 * v) / (np.pi * a ** 2.0 + 1e-16)
+    return np.stack([v, a, d], axis=1)
+
+
+def x_bound(n_atoms, lam2, s=1.0, eps=1e-9):
+    """two feasible points whose Kuhn-Tucker residuals are at most eps s lie within 2 sqrt(n_atoms) eps s / lambda2 of each other
+    (the objective is lambda2-strongly convex)"""
+    return 2.0 * np.sqrt(n_atoms) * eps * s / lam2 if lam2 > 0 else np.inf

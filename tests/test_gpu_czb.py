@@ -27,6 +27,13 @@ def test_czb_golden_fixture_and_model_surface(czb_fix, htable500):
     assert rel.max() < 1e-6, rel.max()
     assert np.abs(out['rmse'] - f['rmse']).max() < 1e-9
     assert np.allclose(out['estimates'][0], 0.0)
+    # the default configuration (no error maps) takes the other device route (k_czb_project + k_czb_lane): same fixture, same bound
+    plain = m.fit(Holder(f['y'], f['dirs'], htable500['htable'], f['kernels']))
+    from amico_amd import get_context
+    assert 'k_czb_lane' in get_context().last_path(), get_context().last_path()
+    assert set(plain) == {'estimates'} and plain['estimates'].shape == (len(f['y']), 3)
+    rel = np.abs(plain['estimates'] - f['estimates']) / (np.abs(f['estimates']) + 1e-3)
+    assert rel.max() < 1e-6, rel.max()
     # float32 signals through the host entry point: same maps
     out32 = m.fit(Holder(f['y'].astype(np.float32), f['dirs'], htable500['htable'], f['kernels']))
     ref32 = m.fit(Holder(f['y'].astype(np.float32).astype(np.float64), f['dirs'], htable500['htable'], f['kernels']))
