@@ -28,6 +28,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
+           'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_lut_resample', 'amx_lut_rotate_resample',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device']
 
@@ -175,6 +176,13 @@ def lib():
     L.amx_prep_debias.argtypes = [c_vp, c_vp, c_fp, C.c_double]
     L.amx_prep_debias_device.argtypes = [c_vp, c_vp, c_vp, C.c_double, c_vp]
     L.amx_debias_last_unconverged.argtypes = [c_vp, C.POINTER(C.c_int64)]
+    L.amx_prep_sanitize.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
+    L.amx_prep_sanitize_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp]
+    L.amx_sanitize_device_f32.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_float, c_vp]
+    L.amx_sanitize_device.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_double, c_vp]
+    L.amx_sanitize.argtypes = [c_vp, c_dp, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_int64)]
+    L.amx_sanitize_last.argtypes = [c_vp, C.POINTER(C.c_int64)]
+    L.amx_sanitize_previous.argtypes = [c_vp, C.POINTER(C.c_int64)]
     L.amx_lut_resample.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     L.amx_lut_rotate_resample.argtypes = [c_vp, c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     for name in SYMBOLS:
@@ -256,6 +264,18 @@ class Context:
         """samples of the last debias call that reached the trip cap (amx_debias_last_unconverged; waits for that call)"""
         out = C.c_int64()
         self.check(lib().amx_debias_last_unconverged(self._h, C.byref(out)))
+        return int(out.value)
+
+    def sanitize_last(self):
+        """NaN / Inf elements the last sanitize call on this context found (amx_sanitize_last; waits for that call)"""
+        out = C.c_int64()
+        self.check(lib().amx_sanitize_last(self._h, C.byref(out)))
+        return int(out.value)
+
+    def sanitize_previous(self):
+        """... and the call before the last one (amx_sanitize_previous): a chain scans the image, then y, and reads both at its end"""
+        out = C.c_int64()
+        self.check(lib().amx_sanitize_previous(self._h, C.byref(out)))
         return int(out.value)
 
     def last_host_narrowed(self):
@@ -774,6 +794,22 @@ class Prep:
         """device pointer (int) of the image's element buffer, in place, enqueued on `stream`"""
         self.ctx.check(lib().amx_prep_debias_device(self.ctx._h, self._h, c_vp(d_img), float(snr), c_vp(stream or 0)))
 
+    def sanitize(self, img, replace=None):
+        """host image: -> number of NaN / Inf samples; with `replace` (a finite number) they are overwritten IN PLACE with float32(replace),
+        np.nan_to_num(img, copy=False, nan=r, posinf=r, neginf=r) of core.py:156 (amx_prep_sanitize)"""
+        buf = self._img_buffer(img)
+        if replace is not None and not img.flags.writeable:
+            raise ValueError('the image is sanitized in place and must be writeable')
+        out = C.c_int64()
+        self.ctx.check(lib().amx_prep_sanitize(self.ctx._h, self._h, _p(buf, c_fp), int(replace is not None), _replacement(replace, np.float32),
+                                               C.byref(out)))
+        return int(out.value)
+
+    def sanitize_device(self, d_img, replace=None, stream=None):
+        """device pointer (int) of the image's element buffer, enqueued on `stream`; the count: Context.sanitize_last()"""
+        self.ctx.check(lib().amx_prep_sanitize_device(self.ctx._h, self._h, c_vp(d_img), int(replace is not None), _replacement(replace, np.float32),
+                                                      c_vp(stream or 0)))
+
     def scatter(self, values):
         v = np.ascontiguousarray(values, dtype=np.float64)
         if v.ndim == 1:
@@ -783,6 +819,32 @@ class Prep:
         out = np.zeros(self.shape[:3] + (v.shape[1],), dtype=np.float32)
         self.ctx.check(lib().amx_prep_scatter(self.ctx._h, self._h, _p(v, c_dp), v.shape[1], _p(out, c_fp)))
         return out
+
+
+def _replacement(replace, dtype):
+    """the value handed to the library: `replace` rounded ONCE to the buffer's type (what numpy's assignment into the image does); 0 when
+    nothing is to be replaced.  A value that is finite but overflows the type becomes Inf here and the library refuses it."""
+    if replace is None:
+        return 0.0
+    with np.errstate(over='ignore'):
+        return float(dtype(replace))
+
+
+def sanitize_device(ctx, d_buf, count, replace=None, stream=None, f32=True):
+    """`count` contiguous float32 (f32=True) | float64 elements at device pointer `d_buf` (int): count the NaN / Inf elements and, with
+    `replace`, overwrite them (amx_sanitize_device[_f32]); enqueued on `stream`; the count: Context.sanitize_last()"""
+    fn = lib().amx_sanitize_device_f32 if f32 else lib().amx_sanitize_device
+    ctx.check(fn(ctx._h, c_vp(d_buf), int(count), int(replace is not None), _replacement(replace, np.float32 if f32 else np.float64),
+                 c_vp(stream or 0)))
+
+
+def sanitize(ctx, y, replace=None):
+    """host float64 array (C-contiguous), IN PLACE when `replace` is given: -> number of NaN / Inf elements (amx_sanitize)"""
+    if y.dtype != np.float64 or not y.flags.c_contiguous or (replace is not None and not y.flags.writeable):
+        raise ValueError('y must be a C-contiguous (writeable) float64 array')
+    out = C.c_int64()
+    ctx.check(lib().amx_sanitize(ctx._h, _p(y, c_dp), y.size, int(replace is not None), _replacement(replace, np.float64), C.byref(out)))
+    return int(out.value)
 
 
 def debias_rows(ctx, S, b0_idx, snr):

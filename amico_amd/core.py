@@ -3,7 +3,10 @@
 in-memory volumes, every per-voxel step on the GPU:
 
   set_data   ~ load_data's preprocessing inputs (core.py:201-268): raw float32 image, scheme, mask
-  fit        Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
+  fit        NaN / Inf scan of the raw image, replacement with replace_bad_voxels (core.py:152-158)    (amx_prep_sanitize);
+             CONFIG['bad_samples_raw'] = samples found; the same for ``y`` after the gather (core.py:270-276) (amx_sanitize),
+             CONFIG['bad_samples_preprocessed']
+             Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
              principal directions from the tensor fit (DTI_fit_method)          -> ``DIRs``   (amx_dti_directions)
@@ -91,13 +94,24 @@ class Evaluation:
         return self.CONFIG.get(key)
 
     # ---- in-memory replacement of load_data (core.py:107-278): volumes are given directly
-    def set_data(self, dwi, scheme, mask=None, directions=None, b0_min_signal=0):
+    def set_data(self, dwi, scheme, mask=None, directions=None, b0_min_signal=0, replace_bad_voxels=None):
         """dwi [X,Y,Z,nS] raw signal (C or Fortran order), mask [X,Y,Z], directions [X,Y,Z,3] (optional peaks,
         core.py:438-447: when absent they come from the tensor fit).  The options doDebiasSignal / DWI-SNR /
         doNormalizeSignal / doMergeB0 / doDirectionalAverage are read here, like load_data reads them.
         With doDebiasSignal the image is debiased in HBM inside fit(): `niiDWI_img` keeps the RAW image (the reference's load_data
         replaces it with the debiased one); fit() leaves CONFIG['debias_unconverged'], the number of samples whose root search
-        reached its trip cap (0 on every signal tried; a warning is raised otherwise)."""
+        reached its trip cap (0 on every signal tried; a warning is raised otherwise).
+        replace_bad_voxels (core.py:122-123): value that takes the place of NaN and Inf samples; None (the default) = refuse them.
+        fit() scans the image in HBM before any other kernel reads it (core.py:152-158) and the prepared signals `y` after the
+        gather (core.py:270-276); it leaves the counts in CONFIG['bad_samples_raw'] / ['bad_samples_preprocessed'], and a count
+        that is not 0 raises the reference's RuntimeError (no value given) or its warning (the samples are replaced, the fit goes
+        on).  Replacement happens in HBM only: `niiDWI_img` keeps the RAW image with its NaNs, as it does with the debias.
+        Two deliberate differences from load_data: (1) the second check covers the rows of the masked voxels, not the whole
+        pre-processed image -- nothing outside the mask reaches a result; (2) it runs after the gather's clip (core.py:452), so a
+        -Inf has already become 0 like every negative sample where the reference would flag it first (-Inf can only come from
+        float32 overflow in the normalisation of a negative sample)."""
+        _prep.check_replace_bad_voxels(replace_bad_voxels)                       # before any context is made or anything uploaded
+        self.set_config('replace_bad_voxels', replace_bad_voxels)               # core.py:134
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
             debias_snr = self.get_config('DWI-SNR')
@@ -130,7 +144,7 @@ class Evaluation:
         self._prep = _prep.SignalPreparation(
             scheme, self.niiDWI_img, self.niiMASK_img, do_normalize=self.get_config('doNormalizeSignal'),
             do_merge_b0=self.get_config('doMergeB0'), do_directional_average=self.get_config('doDirectionalAverage'),
-            b0_min_signal=b0_min_signal, debias_snr=debias_snr)
+            b0_min_signal=b0_min_signal, debias_snr=debias_snr, replace_bad_voxels=replace_bad_voxels)
         # the scheme the model sees: one row per shell after the directional average (core.py:254-255)
         self.scheme = SimpleScheme(_prep.directional_average_table(scheme), scheme.b0_thr) \
             if self.get_config('doDirectionalAverage') else scheme
@@ -218,6 +232,12 @@ class Evaluation:
         img = self.niiDWI_img
         d_img = torch.from_numpy(np.lib.stride_tricks.as_strided(img, shape=(plan.extent,), strides=(4,))).to(dev)
         n = self._prep.n_vox
+        # core.py:152-158: the first kernel of the chain; its count comes home before anything else is enqueued (one small wait), so
+        # that nothing downstream ever reads a NaN / Inf image.  A refusal leaves RESULTS and the device state as they were.
+        bad_value = self.get_config('replace_bad_voxels')
+        plan.sanitize_device(d_img.data_ptr(), bad_value)
+        self.set_config('bad_samples_raw', ctx.sanitize_last())
+        _prep.refuse_or_warn(self.get_config('bad_samples_raw'), bad_value, _prep.BAD_RAW)
         if self._prep.debias_snr is not None:
             # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
             self._prep._plan.debias_device(d_img.data_ptr(), self._prep.debias_snr)
@@ -233,6 +253,10 @@ class Evaluation:
             thr = float(self._prep.b0_min_signal * mean_b0s[mean_b0s > 0].mean())
         ctx.check(L.amx_prep_gather_device_f32(ctx._h, plan._h, d_img.data_ptr(), int(self._prep.do_normalize), thr,
                                            d_y.data_ptr(), d_mb0.data_ptr(), None))  # core.py:209-268 + 451-452
+        # core.py:270-276 on the rows the fit reads (float32 overflow in the normalisation is what can make one), before the tensor fit
+        _capi.sanitize_device(ctx, d_y.data_ptr(), n * self._prep.n_out, bad_value)
+        self.set_config('bad_samples_preprocessed', ctx.sanitize_last())
+        _prep.refuse_or_warn(self.get_config('bad_samples_preprocessed'), bad_value, _prep.BAD_PREPROCESSED)
         # precompute directions (core.py:428-458)
         d_dirs = None
         if self.get_config('doDirectionalAverage'):

@@ -366,6 +366,9 @@ void amx_ctx_destroy(amx_ctx *ctx)
     for (DevBuf *b : bufs) if (b->p) hipFree(b->p);
     if (ctx->debias_stats) hipFree(ctx->debias_stats);
     if (ctx->debias_ev) (void)hipEventDestroy(ctx->debias_ev);
+    if (ctx->san_count) hipFree(ctx->san_count);
+    if (ctx->san_host) hipHostFree(ctx->san_host);
+    for (hipEvent_t e : ctx->san_ev) if (e) (void)hipEventDestroy(e);
     for (DevBuf &b : ctx->alt) if (b.p) hipFree(b.p);
     if (ctx->status_d) hipFree(ctx->status_d);
     if (ctx->status_h) hipHostFree(ctx->status_h);

@@ -142,6 +142,11 @@ struct amx_ctx {
     DevBuf debias_sigma, debias_b0;
     unsigned long long *debias_stats = nullptr;
     hipEvent_t debias_ev = nullptr;
+    // NaN / Inf scan (amx_sanitize.hip): counters of the last two calls, alternating, each read behind the event recorded after its kernel
+    unsigned long long *san_count = nullptr;
+    unsigned long long *san_host = nullptr;    // pinned mirror of the two counters, written by a copy enqueued behind each scan
+    hipEvent_t san_ev[2] = {nullptr, nullptr};
+    unsigned san_seq = 0;          // sanitize calls enqueued on this ctx so far; call k counts into san_count[k & 1]
     int opt_seed_chunk = 0;        // AMX_SEED_CHUNK (0 = by the call's size, make_plan): voxels of one orientation per workgroup of the seed solvers (lanes refill from the chunk: the more voxels per lane, the smaller the share of the tail; 1 M voxels: 1024 -> 7.2 ms, 2048 -> 7.3, 4096 -> 5.5 for stage 1)
 };
 

@@ -1,8 +1,10 @@
 """Device-resident chain of the per-voxel steps: raw float32 image (in HBM) -> float32 map volumes (in HBM).
 
+    amx_prep_sanitize_device            NaN / Inf samples of the image replaced (optional: replace_bad_voxels) core.py:152-156
     amx_prep_debias_device              Rician debias in place (optional: debias_snr)                     core.py:201-206, preproc.py:23-36
     amx_prep_gather_directions_device   b0 normalisation (+ merge / shell average), mask gather, clip     core.py:209-268, 451-452
                                         AND the principal directions (log-linear tensor fit)            core.py:428-436, 456-458
+    amx_sanitize_device_f32             NaN / Inf values of y replaced (optional: replace_bad_voxels)     core.py:270-274
     amx_noddi_fit_device        NNLS -> LASSO -> NNLS, maps                                        models.pyx:816-991
     amx_prep_scatter_device     maps / directions into float32 volumes                             core.py:472-498
 
@@ -18,7 +20,12 @@ from .models import get_context
 
 class NoddiVolumePipeline:
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
-                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None):
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None):
+        """replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
+        the scan of the image ahead of everything else and the scan of y behind the gather, both replacing what they find, on
+        the same stream and without a host wait; run() then leaves the two counts in `bad_samples` (image) and
+        `bad_samples_preprocessed` (y).  With fused=True the gather computes the directions in the same kernel as y, so the
+        directions of a voxel whose y is replaced afterwards come from the unreplaced values (fused=False fits them from the replaced y)."""
         import torch
         self.fused = bool(fused)           # False: gather, then the tensor fit as its own pass over y (the round-4 chain; A/B)
         self.torch = torch
@@ -26,7 +33,10 @@ class NoddiVolumePipeline:
         self.dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
         self.scheme = scheme
         self.prep = _prep.SignalPreparation(scheme, img_like, mask, do_normalize=do_normalize,
-                                            b0_min_signal=b0_min_signal, ctx=self.ctx, debias_snr=debias_snr)
+                                            b0_min_signal=b0_min_signal, ctx=self.ctx, debias_snr=debias_snr,
+                                            replace_bad_voxels=replace_bad_voxels)
+        self.replace_bad_voxels = self.prep.replace_bad_voxels
+        self.bad_samples = self.bad_samples_preprocessed = None
         if b0_min_signal != 0.0:
             raise NotImplementedError('b0_min_signal needs the whole-volume b0 mean on the host: use Evaluation')
         self.tensor = _dti.TensorDirections.from_scheme(scheme, ctx=self.ctx)
@@ -44,9 +54,13 @@ class NoddiVolumePipeline:
 
     def enqueue(self, d_img, stream=None):
         """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`); with debias_snr
-        set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere"""
+        set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere; with replace_bad_voxels set its
+        NaN / Inf samples are overwritten before that"""
         L, c, p = _capi.lib(), self.ctx, self.prep._plan
         s = _capi.c_vp(stream or 0)
+        r = self.replace_bad_voxels
+        if r is not None:
+            p.sanitize_device(d_img.data_ptr(), r, stream)
         if self.prep.debias_snr is not None:
             p.debias_device(d_img.data_ptr(), self.prep.debias_snr, stream)
         if self.fused:
@@ -56,7 +70,11 @@ class NoddiVolumePipeline:
         else:
             c.check(L.amx_prep_gather_device_f32(c._h, p._h, d_img.data_ptr(), int(self.prep.do_normalize), 0.0,
                                                  self.y.data_ptr(), self.mean_b0.data_ptr(), s))
+            if r is not None:
+                _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
             self.tensor.fit_device(self.y.data_ptr(), self.n_vox, self.dirs.data_ptr(), stream, f32=True)
+        if r is not None and self.fused:
+            _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
         c.check(L.amx_noddi_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox,
                                        self.lambda1, self.lambda2, 0, self.est.data_ptr(), None, None, None, s))
         c.check(L.amx_prep_scatter_device(c._h, p._h, self.est.data_ptr(), 3, self.maps.data_ptr(), s))
@@ -65,4 +83,7 @@ class NoddiVolumePipeline:
     def run(self, d_img, stream=None):
         self.enqueue(d_img, stream)
         self.ctx.sync(stream)
+        if self.replace_bad_voxels is not None:
+            # the chain's two scans are the last two sanitize calls of the context: image first, y second
+            self.bad_samples, self.bad_samples_preprocessed = self.ctx.sanitize_previous(), self.ctx.sanitize_last()
         return self.maps, self.dirs_vol

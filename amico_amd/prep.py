@@ -5,11 +5,46 @@ does to get `y` (core.py:451-452) and to store the results (core.py:472-498), wi
 (core.py:201-206 -> preproc.py:23-36), planned once per (image geometry,
 mask, scheme, options) and executed on the GPU through `amx_prep_*` (include/amico_amd.h).  No CPU fallback.
 """
+import numbers
+import warnings
+
 import numpy as np
 
 from . import _capi
 
 MAX_DEBIAS_B0 = 128      # b0 volumes the debias kernel sums in numpy's order (include/amico_amd.h)
+
+# the reference's sentences (core.py:155, 158, 273, 276), with set_data() in place of load_data()
+BAD_RAW = 'Nan or Inf values in the raw signal.'
+BAD_PREPROCESSED = 'Nan or Inf values in the signal after the pre-processing.'
+_BAD_TRY = ' Try using the "replace_bad_voxels" or "b0_min_signal" parameters when calling "set_data()"'
+
+
+def check_replace_bad_voxels(value):
+    """load_data's `replace_bad_voxels` (core.py:122-123): None, or the number that takes the place of NaN / Inf samples.
+    -> the value as given.  The image is float32: a value that is not finite AS A FLOAT32 would plant the very thing it is meant
+    to remove, so it is refused here -- on the host, before any context exists -- like a value that is no number at all."""
+    if value is None:
+        return None
+    if not isinstance(value, (numbers.Real, np.integer, np.floating)):
+        raise ValueError(f'replace_bad_voxels must be None or a finite number, not {value!r}')
+    try:
+        with np.errstate(over='ignore'):
+            finite = bool(np.isfinite(np.float32(value)))
+    except OverflowError:
+        finite = False
+    if not finite:
+        raise ValueError(f'replace_bad_voxels must be finite as a float32, not {value!r}')
+    return value
+
+
+def refuse_or_warn(count, replace, sentence):
+    """core.py:153-158 / 271-276 once the scan has counted `count` bad samples: nothing to do, a warning, or the refusal"""
+    if count == 0:
+        return
+    if replace is None:
+        raise RuntimeError(sentence + _BAD_TRY)
+    warnings.warn(f'{sentence} They will be replaced with: {replace}')
 
 
 def volume_groups(scheme, do_merge_b0=False, do_directional_average=False):
@@ -41,10 +76,15 @@ class SignalPreparation:
     """image [X, Y, Z, nS] float32 (any strides) + mask -> y f64[n_vox, n_out]; per-voxel results -> volumes."""
 
     def __init__(self, scheme, img_like, mask, do_normalize=True, do_merge_b0=False, do_directional_average=False,
-                 b0_min_signal=0.0, ctx=None, debias_snr=None):
+                 b0_min_signal=0.0, ctx=None, debias_snr=None, replace_bad_voxels=None):
         """debias_snr (DWI-SNR, or None = doDebiasSignal off): the image is debiased first, on the voxels with mask != 0
-        (preproc.py:29), and is zero elsewhere (preproc.py:24)"""
+        (preproc.py:29), and is zero elsewhere (preproc.py:24).
+        replace_bad_voxels (core.py:122-123; None = no scan at all): gather() replaces the NaN / Inf samples of a private copy of
+        the image before anything else reads it (core.py:152-156) and those of y after the gather (core.py:270-274, on the masked
+        voxels' rows); the counts are left in bad_samples_raw / bad_samples_preprocessed and a warning is raised when one is not 0"""
         from .models import get_context
+        self.replace_bad_voxels = check_replace_bad_voxels(replace_bad_voxels)      # (before a context is made)
+        self.bad_samples_raw = self.bad_samples_preprocessed = None
         if img_like.ndim != 4 or img_like.dtype != np.float32:
             raise ValueError('DWI image must be a 4D float32 array')
         if img_like.shape[3] != scheme.nS:
@@ -91,8 +131,16 @@ class SignalPreparation:
 
     def gather(self, img):
         """-> (y f64[n_vox, n_out], mean_b0 f32[n_vox] of the masked voxels or None)"""
+        r = self.replace_bad_voxels
+        if r is not None:
+            img = np.lib.stride_tricks.as_strided(np.array(self._plan._img_buffer(img)), shape=img.shape, strides=img.strides)
+            self.bad_samples_raw = self._plan.sanitize(img, r)                          # core.py:152-156
+            refuse_or_warn(self.bad_samples_raw, r, BAD_RAW)
         img = self.debias(img)
         y, mb0 = self._plan.gather(img, self.do_normalize, float(self.b0_threshold(img)))
+        if r is not None:
+            self.bad_samples_preprocessed = _capi.sanitize(self.ctx, y, r)              # core.py:270-274
+            refuse_or_warn(self.bad_samples_preprocessed, r, BAD_PREPROCESSED)
         self.mean_b0s = mb0
         return y, mb0
 

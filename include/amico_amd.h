@@ -370,6 +370,30 @@ int amx_prep_debias_device(amx_ctx *ctx, const amx_prep *p, float *d_img, double
  * stream it was enqueued on may be gone by then) */
 int amx_debias_last_unconverged(amx_ctx *ctx, int64_t *out);
 
+/* (f0') NaN / Inf samples, load_data(..., replace_bad_voxels): core.py:152-158 on the raw image and core.py:270-276 on the
+ * pre-processed one --
+ *     if np.isnan(img).any() or np.isinf(img).any():
+ *         replace_bad_voxels is None -> ERROR(...);  else np.nan_to_num(img, copy=False, nan=r, posinf=r, neginf=r)
+ * These entry points COUNT the non-finite elements of a buffer (every exponent bit set, tested on the integer pattern) and, with
+ * replace != 0, overwrite exactly those with `value`: NaN, +Inf and -Inf all become value, every finite element -- -0.0 and denormals
+ * included -- keeps its bits, and on clean data the buffer is only read.  With replace == 0 the buffer is only read whatever it holds.
+ * replace != 0 with a non-finite value is AMX_E_BADARG.  Refusing or warning is the caller's part (amico_amd.core.Evaluation).
+ * flat form:   `count` contiguous float32 | float64 elements in device memory (the prepared signals y), aligned to 4 bytes.
+ * image form:  the float32 image of a plan in the plan's own layout, every voxel inside and outside the mask as in the reference.  A
+ *              layout that is a permutation of a contiguous block (C order, the Fortran order nibabel hands out) is scanned as that
+ *              block; any other view is visited element by element, and memory between its elements is neither counted nor written.
+ * The device forms are enqueued on `hip_stream` and wait for nothing.  amx_sanitize_last gives the count of the last sanitize call on
+ * this ctx, amx_sanitize_previous that of the call before it (a chain scans the image and then y on one stream and reads both at
+ * its end); each waits for its call through an event recorded behind the kernel and gives 0 when there was no such call.  The ctx
+ * keeps those two counters: a third call reuses the first one's, so calls on different streams must not leave more than two in flight. */
+int amx_prep_sanitize(amx_ctx *ctx, const amx_prep *p, float *img, int replace, float value, int64_t *out_count);   /* host image, in place */
+int amx_prep_sanitize_device(amx_ctx *ctx, const amx_prep *p, float *d_img, int replace, float value, void *hip_stream);
+int amx_sanitize_device_f32(amx_ctx *ctx, float *d_buf, int64_t count, int replace, float value, void *hip_stream);
+int amx_sanitize_device(amx_ctx *ctx, double *d_buf, int64_t count, int replace, double value, void *hip_stream);
+int amx_sanitize(amx_ctx *ctx, double *buf, int64_t count, int replace, double value, int64_t *out_count);          /* host buffer, in place */
+int amx_sanitize_last(amx_ctx *ctx, int64_t *out_count);
+int amx_sanitize_previous(amx_ctx *ctx, int64_t *out_count);
+
 /* (f4) LUT resampling to the subject's scheme, lut.pyx:274-311 `resample_kernel` (called per atom by
  * NODDI.resample models.pyx:754-792, FreeWater.resample :1113-1144, ...):
  *     KR = np.ones((ndirs, nS), float32);  KR[i, idx_out] = np.dot(Ylm_out, KRlm[i, :])   for i in range(ndirs)
