@@ -196,12 +196,12 @@ void progress_tick(amx_ctx *ctx, hipStream_t s, int64_t done, int64_t total)
 amx_stage::Pool *make_stage_pool(amx_ctx *ctx)
 {
     const unsigned hw = std::thread::hardware_concurrency();
-    int nt = ctx->opt_host_threads;
+    int nt = (int)ctx->opt_host_threads;
     if (hw >= 2 && nt > (int)(hw / 2)) nt = (int)(hw / 2);
     int node = -1;
-    const char *pe = getenv("AMX_HOST_PIN");
-    if (!pe || pe[0] == 'g') node = amx_stage::device_node(ctx->device);
-    if ((pe && pe[0] == 'c') || ((!pe || pe[0] == 'g') && node < 0)) {
+    const bool pin_gpu = ctx->opt_host_pin == 'g', pin_caller = ctx->opt_host_pin == 'c';
+    if (pin_gpu) node = amx_stage::device_node(ctx->device);
+    if (pin_caller || (pin_gpu && node < 0)) {
         const int cpu = sched_getcpu();
         cpu_set_t cs;
         for (int nd = 0; nd < 16 && cpu >= 0; nd++)
@@ -209,10 +209,9 @@ amx_stage::Pool *make_stage_pool(amx_ctx *ctx)
     }
     // the other devices of that node have pools of their own (this process's other contexts, or other ranks): disjoint shares
     int sib_i = 0, sib_n = 1;
-    const char *se = getenv("AMX_HOST_SIBLINGS");          // "i/n" forces (diagnosis, tests)
-    if (se && sscanf(se, "%d/%d", &sib_i, &sib_n) == 2 && sib_n >= 1 && sib_i >= 0) { }
-    else { sib_i = 0; sib_n = 1; if (!pe || pe[0] == 'g') amx_stage::device_siblings(ctx->device, node, &sib_i, &sib_n); }
-    return amx_stage::Pool::create(nt < 1 ? 1 : nt, node, sib_i, sib_n);
+    if (ctx->opt_host_siblings[1] >= 1 && ctx->opt_host_siblings[0] >= 0) { sib_i = (int)ctx->opt_host_siblings[0]; sib_n = (int)ctx->opt_host_siblings[1]; }   // AMX_HOST_SIBLINGS=i/n forces
+    else if (pin_gpu) amx_stage::device_siblings(ctx->device, node, (int)ctx->opt_local_rank, (int)ctx->opt_local_world, &sib_i, &sib_n);
+    return amx_stage::Pool::create(nt < 1 ? 1 : nt, node, sib_i, sib_n, (char)ctx->opt_host_pin_cores);
 }
 
 // Round 6: the pool is made WHILE the dictionary is uploaded.  Pinning its 64 MB ring and starting its threads takes ~15 ms, and it used to
@@ -222,8 +221,7 @@ amx_stage::Pool *make_stage_pool(amx_ctx *ctx)
 void prefetch_stage_pool(amx_ctx *ctx)
 {
     if (ctx->stage || ctx->stage_failed || ctx->stage_bg_started || ctx->opt_host_no_narrow) return;
-    const char *pe = getenv("AMX_HOST_PIN"), *pf = getenv("AMX_HOST_PREFETCH");
-    if ((pe && pe[0] == 'c') || (pf && pf[0] == '0')) return;          // (the caller's node is the CALLING thread's: made where it is needed)
+    if (ctx->opt_host_pin == 'c' || ctx->opt_host_no_prefetch) return;          // (the caller's node is the CALLING thread's: made where it is needed)
     ctx->stage_bg_started = true;
     try {
         ctx->stage_thread = std::thread([ctx] {
@@ -272,82 +270,21 @@ int amx_ctx_create(int device, amx_ctx **out)
         return AMX_E_HIP;
     }
     for (int k = 0; k < kEv; k++) { hipEventCreate(&ctx->ev[k]); ctx->ev_valid[k] = false; }
-    {
-        const char *e = getenv("AMX_NO_SEED");
-        ctx->opt_no_seed = e && *e && *e != '0';
-        e = getenv("AMX_NO_GCERT");
-        ctx->opt_no_gcert = e && *e && *e != '0';
-        e = getenv("AMX_S2_EXACT");
-        ctx->opt_s2_exact = e && *e && *e != '0';
-        auto on = [](const char *name) { const char *v = getenv(name); return v && *v && *v != '0'; };
-        ctx->opt_no_gram = on("AMX_NO_GRAM"); ctx->opt_lasso_qr = on("AMX_LASSO_QR"); ctx->opt_cold_start = on("AMX_COLD_START");
-        { const char *m2 = getenv("AMX_SEED2_MAXATOMS"); if (m2 && *m2) { const int v = atoi(m2); ctx->opt_seed2_maxatoms = v < 8 ? 8 : (v > 30 ? 30 : v); } }
-        { const char *rp = getenv("AMX_GCERT_REPAIR"); if (rp && *rp) ctx->opt_gcert_repair = atoi(rp) != 0 ? 1 : 0; }
-        { const char *t3 = getenv("AMX_GCERT2_THIRD"); if (t3 && *t3) ctx->opt_gcert2_third = atoi(t3) != 0 ? 1 : 0; }
-        ctx->opt_host_one_shot = on("AMX_HOST_ONE_SHOT"); ctx->opt_host_one_stream = on("AMX_HOST_ONE_STREAM"); ctx->opt_host_late_results = on("AMX_HOST_LATE_RESULTS");
-        e = getenv("AMX_HOST_PIPELINE_FROM");
-        if (e && atoll(e) >= 262144) ctx->opt_host_pipeline_from = atoll(e);       // (a pipelined call has a first batch of 131 072 voxels and a second one at least as long)
-        e = getenv("AMX_HOST_NATIVE32");
-        ctx->opt_host_no_native32 = e && *e == '0';
-        e = getenv("AMX_HOST_NARROW");
-        ctx->opt_host_no_narrow = e && *e == '0';
-        e = getenv("AMX_HOST_THREADS");
-        if (e && atoi(e) >= 1) ctx->opt_host_threads = atoi(e) > 64 ? 64 : atoi(e);
-        ctx->opt_tile_f32 = on("AMX_TILE_F32"); ctx->opt_fw_proj_valu = on("AMX_FW_PROJ_VALU"); ctx->opt_sandi_atom_space = on("AMX_SANDI_ATOM_SPACE");
-        ctx->opt_prep_tile = on("AMX_PREP_TILE"); ctx->opt_prep_scalar = on("AMX_PREP_SCALAR"); ctx->opt_lut_regs = on("AMX_LUT_REGS"); ctx->opt_no_refill = on("AMX_NO_REFILL");
-        ctx->opt_wave_per_voxel = on("AMX_WAVE_PER_VOXEL"); ctx->opt_fw_no_fuse = on("AMX_FW_NO_FUSE");
-        e = getenv("AMX_REFILL_CHUNK");
-        if (e) ctx->opt_refill_chunk = atoi(e);
-        e = getenv("AMX_HOST_RAMP");
-        if (e && *e) { const long long v = atoll(e); ctx->opt_host_ramp = v <= 0 ? 0 : (v > 131072 ? 131072 : ((v + 3) & ~3LL)); }
-        e = getenv("AMX_HOST_BATCH");
-        // (a multiple of 4: k_widen reads float4; at least the largest ramp batch, 131072: the ramp batches are written into slots of this size)
-        if (e && atol(e) >= 131072) ctx->opt_host_batch = ((long long)atol(e) + 3) & ~3LL;
-        e = getenv("AMX_SEED_WAVES");
-        if (e && *e) { const int v = atoi(e); ctx->opt_seed_waves = (v == 1 || v == 2 || v == 4) ? v : 0; }
-        e = getenv("AMX_SEED_MIN_VOXELS");
-        if (e && *e) ctx->opt_seed_min_voxels = atoll(e);
-        e = getenv("AMX_SEED_OCC2_FROM");
-        if (e && *e) ctx->opt_seed_occ2_from = atoll(e);
-        e = getenv("AMX_SEED2_OCC2_FROM");
-        if (e && *e) ctx->opt_seed2_occ2_from = atoll(e);
-        ctx->opt_no_chunk_order = on("AMX_NO_CHUNK_ORDER");
-        ctx->opt_no_hard_first = on("AMX_NO_HARD_FIRST");
-        ctx->opt_prep_no_direct = on("AMX_PREP_NO_DIRECT");
-        e = getenv("AMX_NO_GCERT_WIDE");
-        ctx->opt_no_gcert_wide = e && *e && *e != '0';
-        e = getenv("AMX_RESCUE_FROM");
-        if (e && *e) { ctx->opt_rescue_from = atoll(e); ctx->opt_rescue_from_set = true; }
-        e = getenv("AMX_GCERT2_THIRD_MIN");
-        if (e && *e) ctx->opt_gcert2_third_min = atoi(e) < 0 ? 0 : atoi(e);
-        e = getenv("AMX_NO_SCREEN");
-        ctx->opt_no_screen = e && *e && *e != '0';
-        e = getenv("AMX_SEED_STAGES");
-        if (e && *e) ctx->opt_seed_stages = atoi(e) & 7;
-        e = getenv("AMX_SEED_TRIPCAP");
-        if (e && *e) {
-            int c[3] = {ctx->opt_seed_tripcap[0], ctx->opt_seed_tripcap[1], ctx->opt_seed_tripcap[2]};
-            sscanf(e, "%d,%d,%d", &c[0], &c[1], &c[2]);
-            for (int k = 0; k < 3; k++) ctx->opt_seed_tripcap[k] = c[k] < 4 ? 4 : c[k];
+    for (const amx_switch &w : kSwitches) {                  // the ONE place that reads the environment (amx_host.hpp)
+        const char *v = getenv(w.name);
+        const bool given = v && *v;
+        long long c[3] = {w.dflt[0], w.dflt[1], w.dflt[2]};
+        switch (w.kind) {
+        case SW_FLAG: ctx->*w.flag = given && *v != '0'; break;
+        case SW_OFF: ctx->*w.flag = v && *v == '0'; break;
+        case SW_GIVEN: ctx->*w.flag = v != nullptr; break;
+        case SW_CHAR: ctx->*w.num = v ? (unsigned char)*v : w.dflt[0]; break;
+        case SW_INT: ctx->*w.num = given ? w.fix(atoll(v), w.dflt[0]) : w.dflt[0]; break;
+        case SW_LIST:
+            if (given) sscanf(v, w.fmt, &c[0], &c[1], &c[2]);
+            for (int k = 0; k < 3; k++) (ctx->*w.list)[k] = given ? w.fix(c[k], w.dflt[k]) : c[k];
+            break;
         }
-        e = getenv("AMX_LEFT_SMALL");
-        if (e && *e) {
-            long long c[3] = {ctx->opt_left_small[0], ctx->opt_left_small[1], ctx->opt_left_small[2]};
-            sscanf(e, "%lld,%lld,%lld", &c[0], &c[1], &c[2]);
-            for (int k = 0; k < 3; k++) ctx->opt_left_small[k] = c[k] < 0 ? 0 : c[k];
-        }
-        e = getenv("AMX_LEFT_NR4_NW8");
-        ctx->opt_no_nr4_nw8 = e && *e == '0';
-        e = getenv("AMX_BIG_ALL");
-        ctx->opt_no_big_all = e && *e == '0';
-        e = getenv("AMX_FORK");
-        if (e && *e) ctx->opt_fork = atoi(e) & 3;
-        e = getenv("AMX_FORK_CUS");
-        if (e && *e) ctx->opt_fork_cus = atoi(e) < 0 ? 0 : atoi(e);
-        ctx->opt_fork_prio = on("AMX_FORK_PRIO") ? 1 : 0;
-        e = getenv("AMX_SEED_CHUNK");
-        // (never below kChunk: the left-over passes size their grid by the FIRST plan's chunk count, n / kChunk + ndirs + 1)
-        if (e && atoi(e) >= kChunk) ctx->opt_seed_chunk = (atoi(e) + 63) & ~63;
     }
     reset_status(ctx, nullptr);
     hipStreamSynchronize(nullptr);
@@ -469,7 +406,7 @@ int amx_lut_upload_noddi(amx_ctx *ctx, const float *wm, const float *iso, const 
     // Gram matrices of every orientation (all rows for the NNLS stages, stage-2 rows for the LASSO):
     // they let the solver update the dual vector without sweeping the tile (amx_solver.hpp)
     {
-        if (!ctx->opt_no_gram) {
+        {
             lut->ldG = n_atoms <= 192 ? 192 : 256;            // (>= 64 atoms per lane-row of the solvers' column reads)
             const size_t gbytes = (size_t)ndirs * n_atoms * lut->ldG * sizeof(double);
             const size_t lds_tile = (size_t)nS * lut->ldA * sizeof(float);
@@ -632,23 +569,23 @@ int amx_sync_status(amx_ctx *ctx, void *hip_stream)
     ctx->seed_stats[0] = ctx->seeded_vox; ctx->seeded_vox = 0;
     for (int k = 0; k < 3; k++) { ctx->seed_stats[1 + k] = st[ST_LEFT + k] + ctx->uncert_vox[k]; ctx->uncert_vox[k] = 0; }
     ctx->seed_stats[4] = st[ST_CLIP];
-    if (amx_debug()) fprintf(stderr, "[amx] dual-vector evaluations per stage: exact %d %d %d  gram %d %d %d  inner iterations %d %d %d\n", st[ST_EXACT], st[ST_EXACT + 1], st[ST_EXACT + 2], st[ST_GRAM], st[ST_GRAM + 1], st[ST_GRAM + 2], st[ST_ITERS], st[ST_ITERS + 1], st[ST_ITERS + 2]);
-    if (amx_debug()) fprintf(stderr, "[amx] seeds: stage 1 tried %d certified %d, stage 3 tried %d certified %d; seed solver trips %d lane-trips used %d; stage-1 refusals: malformed %d pivot %d refinement %d x<=0 %d dual %d\n", st[ST_SEED], st[ST_SEED + 1], st[ST_SEED + 2], st[ST_SEED + 3], st[ST_SEED + 4], st[ST_SEED + 5], st[ST_SEED + 7], st[ST_SEED + 8], st[ST_SEED + 9], st[ST_SEED + 10], st[ST_SEED + 11]);
-    if (amx_debug()) fprintf(stderr, "[amx] screened certificates: %d exact dot products (NNLS stages), %d (LASSO stage)\n", st[ST_SEED + 22], st[ST_SEED + 23]);
-    if (amx_debug()) fprintf(stderr, "[amx] Gram certificates stage 1: %d voxels, %d certified (pivot ratio %d, x <= 0 %d, dual %d), %d dual values; stage 3: %d voxels, %d certified (pivot %d, x <= 0 %d, dual %d), %d dual values\n",
+    if (ctx->opt_debug) fprintf(stderr, "[amx] dual-vector evaluations per stage: exact %d %d %d  gram %d %d %d  inner iterations %d %d %d\n", st[ST_EXACT], st[ST_EXACT + 1], st[ST_EXACT + 2], st[ST_GRAM], st[ST_GRAM + 1], st[ST_GRAM + 2], st[ST_ITERS], st[ST_ITERS + 1], st[ST_ITERS + 2]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] seeds: stage 1 tried %d certified %d, stage 3 tried %d certified %d; seed solver trips %d lane-trips used %d; stage-1 refusals: malformed %d pivot %d refinement %d x<=0 %d dual %d\n", st[ST_SEED], st[ST_SEED + 1], st[ST_SEED + 2], st[ST_SEED + 3], st[ST_SEED + 4], st[ST_SEED + 5], st[ST_SEED + 7], st[ST_SEED + 8], st[ST_SEED + 9], st[ST_SEED + 10], st[ST_SEED + 11]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] screened certificates: %d exact dot products (NNLS stages), %d (LASSO stage)\n", st[ST_SEED + 22], st[ST_SEED + 23]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificates stage 1: %d voxels, %d certified (pivot ratio %d, x <= 0 %d, dual %d), %d dual values; stage 3: %d voxels, %d certified (pivot %d, x <= 0 %d, dual %d), %d dual values\n",
                              st[ST_SEED + 24], st[ST_SEED + 25], st[ST_SEED + 26], st[ST_SEED + 27], st[ST_SEED + 28], st[ST_SEED + 29], st[ST_SEED + 30], st[ST_SEED + 31], st[ST_SEED + 32], st[ST_SEED + 33], st[ST_SEED + 34], st[ST_SEED + 35]);
-    if (amx_debug()) fprintf(stderr, "[amx] Gram certificates LASSO: %d voxels, %d certified (more than 12 atoms %d, x <= 0 %d, dual %d), %d dual values\n",
+    if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificates LASSO: %d voxels, %d certified (more than 12 atoms %d, x <= 0 %d, dual %d), %d dual values\n",
                              st[ST_SEED + 36], st[ST_SEED + 37], st[ST_SEED + 38], st[ST_SEED + 39], st[ST_SEED + 40], st[ST_SEED + 41]);
-    if (amx_debug()) fprintf(stderr, "[amx] Gram certificates LASSO, second pass: %d voxels, %d certified (more than 18 atoms %d, x <= 0 %d, dual %d), %d dual values\n",
+    if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificates LASSO, second pass: %d voxels, %d certified (more than 18 atoms %d, x <= 0 %d, dual %d), %d dual values\n",
                              st[ST_SEED + 48], st[ST_SEED + 49], st[ST_SEED + 50], st[ST_SEED + 51], st[ST_SEED + 52], st[ST_SEED + 53]);
-    if (amx_debug()) fprintf(stderr, "[amx] LASSO seeds: tried %d certified %d; seed solver trips %d lane-trips used %d\n", st[ST_SEED + 18], st[ST_SEED + 19], st[ST_SEED + 20], st[ST_SEED + 21]);
-    if (amx_debug()) fprintf(stderr, "[amx] seed solver kcycles (wave sums / 1024): take %d solve+drop %d residual %d scan %d append %d store %d\n", st[ST_SEED + 12], st[ST_SEED + 13], st[ST_SEED + 14], st[ST_SEED + 15], st[ST_SEED + 16], st[ST_SEED + 17]);
-    if (amx_debug()) fprintf(stderr, "[amx] Gram certificate kcycles (decode | gather+factor+solve | screening | exact duals | output): stage 1 %d %d %d %d %d, stage 3 %d %d %d %d %d\n",
+    if (ctx->opt_debug) fprintf(stderr, "[amx] LASSO seeds: tried %d certified %d; seed solver trips %d lane-trips used %d\n", st[ST_SEED + 18], st[ST_SEED + 19], st[ST_SEED + 20], st[ST_SEED + 21]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] seed solver kcycles (wave sums / 1024): take %d solve+drop %d residual %d scan %d append %d store %d\n", st[ST_SEED + 12], st[ST_SEED + 13], st[ST_SEED + 14], st[ST_SEED + 15], st[ST_SEED + 16], st[ST_SEED + 17]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificate kcycles (decode | gather+factor+solve | screening | exact duals | output): stage 1 %d %d %d %d %d, stage 3 %d %d %d %d %d\n",
                              st[ST_SEED + 60], st[ST_SEED + 61], st[ST_SEED + 62], st[ST_SEED + 63], st[ST_SEED + 64], st[ST_SEED + 65], st[ST_SEED + 66], st[ST_SEED + 67], st[ST_SEED + 68], st[ST_SEED + 69]);
-    if (amx_debug()) fprintf(stderr, "[amx] LASSO Gram certificate kcycles (decode | gather+factor+solve | screening | exact duals | output): %d %d %d %d %d\n",
+    if (ctx->opt_debug) fprintf(stderr, "[amx] LASSO Gram certificate kcycles (decode | gather+factor+solve | screening | exact duals | output): %d %d %d %d %d\n",
                              st[ST_SEED + 70], st[ST_SEED + 71], st[ST_SEED + 72], st[ST_SEED + 73], st[ST_SEED + 74]);
-    if (amx_debug()) fprintf(stderr, "[amx] stage-3 seed solver kcycles: take %d solve+drop %d residual %d scan %d append %d store %d\n", st[ST_SEED + 54], st[ST_SEED + 55], st[ST_SEED + 56], st[ST_SEED + 57], st[ST_SEED + 58], st[ST_SEED + 59]);
-    if (amx_debug() && st[ST_GRAM + 1] > 0) fprintf(stderr, "[amx] k_noddi_lasso_big: %d voxels, %.1f pivoting steps per voxel\n", st[ST_GRAM + 1], (double)st[ST_ITERS + 1] / st[ST_GRAM + 1]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] stage-3 seed solver kcycles: take %d solve+drop %d residual %d scan %d append %d store %d\n", st[ST_SEED + 54], st[ST_SEED + 55], st[ST_SEED + 56], st[ST_SEED + 57], st[ST_SEED + 58], st[ST_SEED + 59]);
+    if (ctx->opt_debug && st[ST_GRAM + 1] > 0) fprintf(stderr, "[amx] k_noddi_lasso_big: %d voxels, %.1f pivoting steps per voxel\n", st[ST_GRAM + 1], (double)st[ST_ITERS + 1] / st[ST_GRAM + 1]);
     {
         // first offending voxel and what it held, as the kernels' one 64-bit atomicMin left them
         int *sth = ctx->status_h;
@@ -793,17 +730,7 @@ static int fork_ready(amx_ctx *ctx)
 {
     const int w = ctx->work_idx;
     if (ctx->fork_s[w]) return AMX_OK;
-    int lo = 0, hi = 0;
-    if (ctx->opt_fork_prio) (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (ctx->opt_fork_cus > 0) {
-        // n compute units for the side stream, spread evenly over the mask's bits (one bit per CU)
-        uint32_t mask[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int total = ctx->n_cu > 256 ? 256 : ctx->n_cu, n = ctx->opt_fork_cus > total ? total : ctx->opt_fork_cus;
-        for (int k = 0; k < n; k++) { const int b = (int)((long long)k * total / n); mask[b >> 5] |= 1u << (b & 31); }
-        HIPCHK(ctx, hipExtStreamCreateWithCUMask(&ctx->fork_s[w], (uint32_t)((total + 31) / 32), mask));
-    } else {
-        HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->fork_s[w], hipStreamNonBlocking, ctx->opt_fork_prio ? hi : lo));
-    }
+    HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->fork_s[w], hipStreamNonBlocking, 0));
     for (int k = 0; k < 4; k++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->fork_ev[w][k], hipEventDisableTiming));
     return AMX_OK;
 }
@@ -895,7 +822,7 @@ static int noddi_fit_dev(amx_ctx *ctx, const amx_lut *lut, const double *d_y, co
     progress_tick(ctx, s, n_vox / 3, n_vox);                       // (three stages: a third of the work each, roughly)
     a.c.chunks = pl.chunks; a.c.n_chunks = pl.n_chunks; a.rlist = nullptr; a.rcount = nullptr; a.done = nullptr;
     // the LASSO seeds need x_iso: Gram-space solver only (lambda2 >= 1e-5), with the default dictionary shape
-    if (seeds && (ctx->opt_seed_stages & 4) && lut->basis2_S != nullptr && lambda2 >= 1e-5 && (gemm_ks > 0 || lut->nS <= 128) && !ctx->opt_lasso_qr &&
+    if (seeds && (ctx->opt_seed_stages & 4) && lut->basis2_S != nullptr && lambda2 >= 1e-5 && (gemm_ks > 0 || lut->nS <= 128) &&
         (lambda1 > 0.0 || ctx->opt_no_big_all || lut->n_wm <= 64)) {       // (lambda1 = 0: a dense optimum -- no seeds to propose, amx_launch_noddi_s2 goes to k_noddi_lasso_big)
         const bool gcert2 = !ctx->opt_no_gcert && gemm_ks > 0 && lut->screen2_kappa0 != nullptr && lut->u2iso != nullptr;
         rec(ctx, 12, s);
@@ -992,14 +919,13 @@ static int freewater_fit_dev(amx_ctx *ctx, const amx_lut *lut, const double *d_y
     rec(ctx, 0, s);
     const bool refill = amx_use_lane_solver(ctx, lut->n_atoms, lambda2) && amx_fw_use_refill(ctx, lut->n_atoms, lut->nS, flags, lambda2);
     // (no memset of the maps: skipped voxels are zeroed by k_dir_to_lut, every other voxel is written -- test_freewater_fit_writes_every_voxel)
-    if ((rc = enqueue_bucketing(ctx, lut, d_dirs, n_vox, pl, s, refill ? amx_refill_chunk(ctx, n_vox) : kChunk, d_estimates, is_mouse ? 4 : 2))) return rc;
+    if ((rc = enqueue_bucketing(ctx, lut, d_dirs, n_vox, pl, s, refill ? amx_refill_chunk(n_vox) : kChunk, d_estimates, is_mouse ? 4 : 2))) return rc;
     FwArgs a;
     memset(&a, 0, sizeof a);
     a.c.tiles = lut->tiles; a.c.y = d_y; a.c.y32 = d_y32; a.c.perm = pl.perm; a.c.chunks = pl.chunks; a.c.n_chunks = pl.n_chunks;
     a.c.lutidx = pl.lutidx; a.c.status = ctx->status_d; a.c.nS = lut->nS; a.c.ldA = lut->ldA;
     a.c.n_atoms = lut->n_atoms; a.c.tile_stride = lut->tile_stride; a.c.lam1 = lambda1; a.c.lam2 = lambda2; a.c.flags = flags;
     a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = is_mouse; a.n_maps = is_mouse ? 4 : 2;
-    if (ctx->opt_cold_start) a.c.flags |= 0x80000000u;
     if (flags & AMX_F_DEBUG_X) {
         if (!ctx->dbg_x) return bad(ctx, "amx_freewater_fit: AMX_F_DEBUG_X without a buffer (amx_set_debug_x)");
         a.c.xdbg = ctx->dbg_x + (size_t)ctx->vox_base * lut->n_atoms;
@@ -1041,7 +967,6 @@ static int sandi_fit_dev(amx_ctx *ctx, const amx_lut *lut, const double *d_y, co
     a.c.n_atoms = lut->n_atoms; a.c.tile_stride = lut->tile_stride; a.c.lam1 = lambda1; a.c.lam2 = lambda2; a.c.flags = flags;
     a.norms = lut->norms; a.Rs = lut->Rs; a.d_in = lut->d_in; a.d_isos = lut->d_isos;
     a.n_rs = lut->n_rs; a.n_in = lut->n_in; a.n_iso = lut->n_isos;
-    if (ctx->opt_cold_start) a.c.flags |= 0x80000000u;
     if (flags & AMX_F_DEBUG_X) {
         if (!ctx->dbg_x) return bad(ctx, "amx_sandi_fit: AMX_F_DEBUG_X without a buffer (amx_set_debug_x)");
         a.c.xdbg = ctx->dbg_x + (size_t)ctx->vox_base * lut->n_atoms;
@@ -1083,7 +1008,7 @@ static int czb_fit_dev(amx_ctx *ctx, const amx_lut *lut, const double *d_y, cons
     HIPCHK(ctx, hipSetDevice(ctx->device));
     Plan pl; int rc;
     // the default problem (strong ridge, <= 32 atoms, maps only): complementary form, one voxel per lane (amx_czb.hip)
-    const bool fast = lut->n_atoms <= 32 && lambda2 >= 1e-2 && !(flags & (AMX_F_RMSE | AMX_F_NRMSE)) && !ctx->opt_cold_start &&
+    const bool fast = lut->n_atoms <= 32 && lambda2 >= 1e-2 && !(flags & (AMX_F_RMSE | AMX_F_NRMSE)) &&
                       !ctx->opt_wave_per_voxel && lut->nS <= 160 && lut->gram != nullptr;
     if ((rc = make_plan(ctx, n_vox, lut->ndirs, pl, false, 64, fast ? 2048 : 0))) return rc;
     clear_events(ctx);
@@ -1095,7 +1020,6 @@ static int czb_fit_dev(amx_ctx *ctx, const amx_lut *lut, const double *d_y, cons
     a.c.lutidx = pl.lutidx; a.c.status = ctx->status_d; a.c.nS = lut->nS; a.c.ldA = lut->ldA;
     a.c.n_atoms = lut->n_atoms; a.c.tile_stride = lut->tile_stride; a.c.lam1 = lambda1; a.c.lam2 = lambda2; a.c.flags = flags;
     a.n_rs = lut->n_rs; a.n_perp = lut->n_perp; a.Rs = lut->Rs; a.gram = lut->gram; a.ldG = lut->ldG;
-    if (ctx->opt_cold_start) a.c.flags |= 0x80000000u;
     if (flags & AMX_F_DEBUG_X) {
         if (!ctx->dbg_x) return bad(ctx, "amx_czb_fit: AMX_F_DEBUG_X without a buffer (amx_set_debug_x)");
         a.c.xdbg = ctx->dbg_x + (size_t)ctx->vox_base * lut->n_atoms;
@@ -1301,7 +1225,7 @@ int amx_freewater_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *
                                  double *d_ycorr, void *hip_stream)
 {
     if (!ctx) return AMX_E_BADARG;
-    if (!lut || lut->model != 2 || !d_y || n_vox <= 0 || amx_fw_native_f32(ctx, lut->n_atoms, lut->nS, flags | (ctx->opt_cold_start ? 0x80000000u : 0u), lambda2))
+    if (!lut || lut->model != 2 || !d_y || n_vox <= 0 || amx_fw_native_f32(ctx, lut->n_atoms, lut->nS, flags, lambda2))
         return freewater_fit_dev(ctx, lut, nullptr, d_y, d_dirs, n_vox, lambda1, lambda2, is_mouse, flags, d_estimates, d_rmse, d_nrmse, d_ycorr, hip_stream);
     const double *wide; int rc;
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -1400,11 +1324,11 @@ static int fit_host(amx_ctx *ctx, const T *y, const double *dirs, int64_t n_vox,
     struct HostFitScope { amx_ctx *c; ~HostFitScope() { c->in_host_fit = false; } } host_scope{ctx};
     // Batch c runs on stream c & 1 with workspace set c & 1: the kernels of consecutive batches overlap, so the idle tail
     // of every launch (and the one-wavefront re-run kernels) is filled by the other batch instead of adding up six times.
-    const bool two_streams = pipelined && !ctx->opt_host_one_stream;
+    const bool two_streams = pipelined;
     hipStream_t s = pipelined ? ctx->hs : nullptr;
     int64_t off = 0, done_before[kBufs] = {0, 0, 0};         // voxels complete once the event of that buffer has fired
     // AMX_HOST_TRACE=1 (diagnosis): wall-clock timeline of the call on stderr -- per batch the wait for its buffer, its copy, its enqueue
-    static const bool trace = getenv("AMX_HOST_TRACE") != nullptr;
+    const bool trace = ctx->opt_host_trace;
     auto wall = [] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
     const double tr0 = trace ? wall() : 0.0;
     int64_t reported = 0;                                    // progress is reported once per batch, in order

@@ -252,7 +252,7 @@ struct GramSolver {
                 for (int u = 0; u < 4; u++) {
                     const int t = bcast_i(idx, (s0 + u < np) ? s0 + u : np - 1);
                     p[u] = 0.0;
-                    if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+                    if constexpr (is_global_tile<AT>::value || kTileColLds) {
                         double col[NR];
                         tile_column<NR, AT>(As, ldA, nS, t, lane, rowok, col);
 #pragma unroll
@@ -276,7 +276,7 @@ struct GramSolver {
             for (int s = 0; s < np; s++) {
                 const int t = bcast_i(idx, s);
                 const double cx = bcast(sc * x, s);
-                if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+                if constexpr (is_global_tile<AT>::value || kTileColLds) {
                     double col[NR];
                     tile_column<NR, AT>(As, ldA, nS, t, lane, rowok, col);
 #pragma unroll
@@ -341,7 +341,7 @@ struct GramSolver {
                     const int t = kWave * q + tl;
                     todo &= todo - 1ull;
                     double p = 0.0;
-                    if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+                    if constexpr (is_global_tile<AT>::value || kTileColLds) {
                         double col[NR];
                         tile_column<NR, AT>(As, ldA, nS, t, lane, rowok, col);
 #pragma unroll
@@ -399,7 +399,6 @@ struct GramSolver {
         double u[NQ], uy[NQ];                 // atom space: A'r and A'y (unscaled)
 #pragma unroll
         for (int q = 0; q < NQ; q++) { u[q] = 0.0; uy[q] = 0.0; }
-#ifndef AMX_NO_LASSO_WARM
         // WARM START from a refused seed (round 5).  The voxels that reach this solver with a seed that was not certified -- a support
         // wrong in an atom or two, or the passive set the seed solver held when it gave up at its trip cap (flag word set: then the
         // set is incomplete, not wrong) -- used to start from the EMPTY set: 20 - 30 additions, one factor row and one dual update
@@ -446,7 +445,6 @@ struct GramSolver {
                 force_exact = true;              // the dual vector of this state comes from the true residual
             }
         }
-#endif
 
         for (int outer = 0; status == kSolved; ++outer) {
             if (outer > 2 * itmax) { status = kGuardOuter; break; }
@@ -458,7 +456,7 @@ struct GramSolver {
                 for (int sl = 0; sl < np; sl++) {
                     const int a = bcast_i(idx, sl);
                     const double cx = bcast(sc * x, sl);
-                    if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+                    if constexpr (is_global_tile<AT>::value || kTileColLds) {
                         double col[NR];
                         tile_column<NR, AT>(As, ldA, nS, a, lane, rowok, col);
 #pragma unroll
@@ -523,9 +521,7 @@ struct GramSolver {
                 }
                 const double wmax = wave_max(best);
                 if (!exact) {
-#ifndef AMX_ALWAYS_CONFIRM
                     if (uni(wmax < -kExactBelow)) break;           // clearly a KKT point: no exact confirmation needed
-#endif
                     if (uni(!(wmax > kExactBelow))) { force_exact = true; redo = true; break; }
                 }
                 if (!uni(wmax > tol)) break;

@@ -10,10 +10,7 @@
 #include <string>
 #include <vector>
 
-#ifndef AMX_CHUNK
-#define AMX_CHUNK 256
-#endif
-constexpr int kChunk = AMX_CHUNK;        // voxels of one orientation per workgroup
+constexpr int kChunk = 256;        // voxels of one orientation per workgroup
 constexpr int kListGrid = 512;     // workgroups of the large-MAXP re-run pass
 constexpr int kEv = 20;           // event pairs: 0 whole call, 1-3 NODDI stage kernels, 4 small-model solver, 5-7 NODDI GEMM + seed + certificate kernels of stages 1 / 2 / 3, 8 k_nnls_seed<1> alone, 9 k_lasso_seed alone
 
@@ -54,7 +51,6 @@ struct amx_ctx {
     bool stage_bg_started = false;
     bool host_native32 = false;    // set by a model's host entry point whose kernels read float32 signals in place (fit_host then skips k_widen)
     const float *host_y32 = nullptr;   // the current batch's float32 signals in HBM (fit_host -> the model's enqueue), or null: float64 in the staging buffer
-    bool opt_host_no_native32 = false; // AMX_HOST_NATIVE32=0: float32 batches are widened on the device first (the round-5 behaviour)
     bool stage_failed = false;     // the pool could not be made: host signals are copied as they are
     int host_narrowed = 0;         // batches of the last host-buffer call that travelled as float32 (amx_last_host_narrowed)
     hipStream_t hs = nullptr;      // non-blocking compute streams of the chunked host entry points: batches alternate
@@ -69,72 +65,17 @@ struct amx_ctx {
         for (int i = 0; i < 22; i++) { DevBuf t = *named[i]; *named[i] = alt[i]; alt[i] = t; }
         work_idx ^= 1;
     }
-    // switches read ONCE, at amx_ctx_create (environment): diagnosis / A-B only
-    // switches below: environment variables read ONCE, at amx_ctx_create (diagnosis / A-B tools; the defaults are the product path)
-    bool opt_no_gram = false;          // AMX_NO_GRAM=1: no Gram matrices at upload (the solvers sweep the tile instead)
-    bool opt_lasso_qr = false;         // AMX_LASSO_QR=1: NODDI stage 2 by the A-space QR solver whatever lambda2
-    bool opt_cold_start = false;       // AMX_COLD_START=1: FreeWater / SANDI / CZB start from the empty passive set
-    bool opt_host_one_shot = false;    // AMX_HOST_ONE_SHOT=1: host-buffer entry points upload everything, then fit
-    bool opt_host_one_stream = false;  // AMX_HOST_ONE_STREAM=1: pipelined host path on one stream
-    bool opt_host_late_results = false; // AMX_HOST_LATE_RESULTS=1: the results of a host-buffer call go home in one copy after the last batch (diagnosis)
-    long long opt_host_pipeline_from = 393217;   // AMX_HOST_PIPELINE_FROM: host-buffer calls of fewer voxels upload everything, then fit (>= 262144).  From 3 x 131 072 voxels a call has two batches -- the first short -- and the second copy hides behind the first fit: 400 000 voxels 7.63 -> 6.85 ms (float32 signals 6.94 -> 6.08), 500 000 8.66 -> 7.92 (8.30 -> 7.51); was 524 288 while a float64 copy took twice as long (profiles/r05c_host_transport.txt, section 9)
-    bool opt_host_no_narrow = false;   // AMX_HOST_NARROW=0: float64 host signals are always copied as they are (amx_stage.hpp)
-    int opt_host_threads = 12;         // AMX_HOST_THREADS: host threads that narrow + send float64 host signals (1 .. 64; at most half the logical CPUs)
-    long long opt_host_ramp = 131072;  // AMX_HOST_RAMP: voxels of the first pipelined batch (its copy is the only one nothing hides; 0 = equal batches)
-    long long opt_host_batch = 393216; // AMX_HOST_BATCH: voxels per pipelined batch (>= 131072, multiple of 4)
-    bool opt_tile_f32 = false;         // AMX_TILE_F32=1: NNLS stages keep the float32 tile in LDS
-    bool opt_fw_proj_valu = false;     // AMX_FW_PROJ_VALU=1: FreeWater projection without the matrix cores
-    bool opt_fw_no_fuse = false;       // AMX_FW_NO_FUSE=1: FreeWater by the projection + solver kernel pair instead of k_freewater_fused
-    bool opt_sandi_atom_space = false; // AMX_SANDI_ATOM_SPACE=1: SANDI 6 x 15 by the atom-space lane kernel
-    bool opt_prep_scalar = false;      // AMX_PREP_SCALAR=1: the streaming preparation kernel with one voxel per lane (4-byte loads) instead of four
-    bool opt_prep_no_direct = false;   // AMX_PREP_NO_DIRECT=1: k_prep_gather stages the planes through registers (32 loads in flight) instead of global -> LDS loads
-    bool opt_prep_tile = false;        // AMX_PREP_TILE=1: signal preparation always through the transposition tile
-    bool opt_lut_regs = false;         // AMX_LUT_REGS=1: LUT resampling with register operands
-    bool opt_no_refill = false;        // AMX_NO_REFILL=1: FreeWater by k_freewater_lane (one solve per lane and pass)
-    bool opt_wave_per_voxel = false;   // AMX_WAVE_PER_VOXEL=1: small models by the wavefront-per-voxel kernels
-    int opt_refill_chunk = 0;          // AMX_REFILL_CHUNK: voxels per workgroup of k_freewater_refill (0 = by problem size)
-    bool opt_no_chunk_order = false; // AMX_NO_CHUNK_ORDER=1: the chunks of the second plan stay in orientation order (default: longest first)
-    int opt_seed2_maxatoms = 0;     // AMX_SEED2_MAXATOMS=n: atoms at which the LASSO seed solver gives a voxel up (default 20, 26 with a third certificate pass; <= 30)
-    int opt_gcert_repair = -1;      // AMX_GCERT_REPAIR=0 / 1: never / always the NNLS certificates' second look at a mendable seed (default: where the tile is read from L2)
-    int opt_gcert2_third_min = 16;  // AMX_GCERT2_THIRD_MIN: list entries a chunk must hold for the third LASSO certificate pass to work on it (tiles in LDS; 0 with global tiles)
-    bool opt_rescue_from_set = false;   // AMX_RESCUE_FROM given: the caller's threshold alone decides
-    int opt_gcert2_third = -1;      // AMX_GCERT2_THIRD=0 / 1: never / always a third LASSO certificate pass (default: where the tile is read from L2)
-    bool opt_no_gcert_wide = false; // AMX_NO_GCERT_WIDE=1: no second Gram-certificate pass for LASSO supports of 13 .. 16 atoms
-    int64_t opt_rescue_from = 2000000;   // AMX_RESCUE_FROM=n: calls of n voxels and more run the rescue pass of the NNLS certificates (k_nnls_gcert<., true>)
-    bool opt_no_gcert = false;     // AMX_NO_GCERT=1: every seed is certified by the wavefront-per-voxel kernels (true residual)
-    bool opt_no_screen = false;    // AMX_NO_SCREEN=1: certify seeds with the full exact sweep of the dual vector
-    bool opt_s2_exact = false;     // AMX_S2_EXACT=1: every voxel's stage-2 products by the exact pass (k_noddi_gemm<true>), none derived from the stage-1 table
-    bool opt_no_seed = false;      // AMX_NO_SEED=1: Lawson-Hanson from the empty set in the NNLS stages (the round-2 path)
-    long long opt_seed_min_voxels = 22528; // AMX_SEED_MIN_VOXELS: smaller calls run the wavefront-per-voxel kernels on all voxels (the seeded chain of ~16 kernels has a floor of ~1.5 ms; measured, tools/r04/round8.sh: 20 000 voxels 1.58 against 1.49 ms, 25 000 voxels 1.60 against 1.78, 40 000 1.70 against 2.34)
-    long long opt_seed_occ2_from = 65536; // AMX_SEED_OCC2_FROM: calls of at least this many voxels run k_nnls_seed<1> at two wavefronts per SIMD (a third more time per trip, twice the wavefronts: wins when the kernel is throughput bound -- 1 M voxels 2.80 -> 2.14 ms --, loses when the longest voxel's path bounds it: 50 000 voxels 0.54 -> 0.73 ms; with four wavefronts per workgroup the crossover sits between 200 000 and 300 000 voxels)
-    long long opt_seed2_occ2_from = 65536; // AMX_SEED2_OCC2_FROM: the same for k_lasso_seed (200 000 voxels: 0.50 -> 0.42 ms, 1 M: 1.67 -> 1.27 ms)
-    // AMX_SEED_TRIPCAP=a,b,c: trips after which k_nnls_seed<1> / k_lasso_seed / k_nnls_seed<3> give a voxel up (no seed: it goes
-    // to the left-over kernels).  A lane kernel lasts as long as its slowest voxel, and the slowest are a handful: of 1 M bench
-    // voxels 12 need more than 32 stage-1 trips (mean ~10), yet with the old cap of 64 they held the kernel 0.4 ms longer.
-    // Measured (tools/r04/tripcap2.sh; 50 000 / 200 000 / 1 M voxels, fit in ms): 64,64,64 2.09 / 3.31 / 8.17; 28,24,12 1.74 / 2.94 /
-    // 7.66; below 20 / 18 / 8 the left-over kernels get more voxels than the shorter tails are worth
-    int opt_seed_tripcap[3] = {20, 20, 10};     // (28, 24, 12 before the normalised entering rule shortened the paths, 24, 24, 10 until the stage-1 solver handed its support on and the LASSO left-over solver started from the seed: profiles/r05b_tripcaps.txt)
-    bool opt_no_hard_first = false; // AMX_NO_HARD_FIRST=1: the left-over kernels of the NNLS stages walk their lists in the order the certificates wrote them
-    int opt_seed_waves = 0;        // AMX_SEED_WAVES: wavefronts per workgroup of the lane kernels (0 = by the number of chunks, make_plan)
-    int opt_seed_stages = 7;       // AMX_SEED_STAGES: bit 0 = seed stage 1, bit 1 = seed stage 3, bit 2 = seed the LASSO stage
-    // AMX_FORK (round 6; bit 0 / bit 1): the left-over kernels of stage 1 / of the LASSO stage run on a SIDE stream beside the next stage's
-    // lane kernels (noddi_fit_dev).  Bit 1 is a correct fit (the forked voxels skip the stage-3 lane kernels and end in k_noddi<3> on the side
-    // stream); bit 0 is a TIMING PROBE only (the stage-2 lane kernels read the x_iso the previous call left for those voxels).
-    int opt_fork = 0;
-    int opt_fork_cus = 0;           // AMX_FORK_CUS=n: the side stream may use n compute units only (hipExtStreamCreateWithCUMask; 0 = no mask)
-    int opt_fork_prio = 0;          // AMX_FORK_PRIO=1: the side stream at the highest priority
+    // environment switches: read ONCE, by amx_ctx_create on the caller's thread, through kSwitches below -- the table is their documentation
+    bool opt_no_seed, opt_no_gcert, opt_no_gcert_wide, opt_no_screen, opt_s2_exact, opt_no_chunk_order, opt_no_hard_first, opt_no_big_all;
+    bool opt_wave_per_voxel, opt_no_refill, opt_sandi_atom_space, opt_fw_no_fuse, opt_prep_scalar, opt_debug;
+    bool opt_host_one_shot, opt_host_late_results, opt_host_no_native32, opt_host_no_narrow, opt_host_no_prefetch, opt_host_trace;
+    long long opt_seed_stages, opt_seed_chunk, opt_seed_waves, opt_seed_min_voxels, opt_seed_occ2_from, opt_seed2_occ2_from, opt_seed_tripcap[3];
+    long long opt_rescue_from, opt_gcert_repair, opt_gcert2_third, opt_fork;
+    long long opt_host_threads, opt_host_batch, opt_host_ramp, opt_host_pipeline_from, opt_host_pin, opt_host_pin_cores, opt_host_siblings[3];
+    long long opt_local_rank, opt_local_world;
     hipStream_t fork_s[2] = {nullptr, nullptr};          // (one per workspace set: work_idx)
     hipEvent_t fork_ev[2][4] = {{nullptr, nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr, nullptr}};
     int work_idx = 0;               // which of the two workspace sets the named buffers are (swap_work)
-    // AMX_LEFT_SMALL=a,b,c: calls of fewer voxels run the left-over kernels of stage 1 / LASSO / stage 3 in their small-call builds (float32 tile, 4
-    // wavefronts, two workgroups per CU: amx_noddi_s1.hip).  Measured (tools/r06/a05.sh; 50 000 / 100 000 / 200 000 / 300 000 / 500 000 / 1 M voxels, fit
-    // in ms, round-5 builds 1.441 / 1.817 / 2.386 / 2.885 / 4.000 / 6.421): stage 1 alone 1.421 / 1.793 / 2.394 / 2.921 / 4.072 / 6.591; stage 3 alone
-    // 1.415 / 1.797 / 2.371 / 2.849 / 3.989 / 6.506 (its 12-wavefront build spills 117 registers, this one none); the LASSO stage's (two wavefronts,
-    // no screening table) loses at every size (1.460 / 1.905 / 2.511 / ...): off.  The gain is ~20 us per kernel, not the ~100 the "one round of
-    // workgroups instead of two" arithmetic promised: a left-over kernel lasts as long as its longest voxel's Lawson-Hanson, whatever the rounds.
-    long long opt_left_small[3] = {150000, 0, 600000};
-    bool opt_no_nr4_nw8 = false;    // AMX_LEFT_NR4_NW8=0: protocols of 129 .. 256 volumes run their left-over lists on the round-5 builds (12 / 16 wavefronts, spilling)
-    bool opt_no_big_all = false;    // AMX_BIG_ALL=0: lambda1 = 0 fits take the fast kernels first and reach k_noddi_lasso_big through the overflow lists
     bool side_launch = false;       // transient: the launch being enqueued goes to the side stream (launch_pair picks its own overflow lists)
     std::string path;               // kernels of the last fit enqueued on this ctx, in launch order (amx_last_path)
     // Rician debias (amx_debias.hip): sigma of every voxel / row of the call in flight, its b0 list, and the counter of samples that
@@ -147,8 +88,117 @@ struct amx_ctx {
     unsigned long long *san_host = nullptr;    // pinned mirror of the two counters, written by a copy enqueued behind each scan
     hipEvent_t san_ev[2] = {nullptr, nullptr};
     unsigned san_seq = 0;          // sanitize calls enqueued on this ctx so far; call k counts into san_count[k & 1]
-    int opt_seed_chunk = 0;        // AMX_SEED_CHUNK (0 = by the call's size, make_plan): voxels of one orientation per workgroup of the seed solvers (lanes refill from the chunk: the more voxels per lane, the smaller the share of the tail; 1 M voxels: 1024 -> 7.2 ms, 2048 -> 7.3, 4096 -> 5.5 for stage 1)
 };
+
+// ------------------------------------------------------------------ environment switches
+// One row per switch: name, kind, the amx_ctx field it fills, default, the rule a given number goes through, and its description (the only
+// documentation of the field; DESIGN.md, "Switches", lists the same rows).  amx_ctx_create walks the table on the caller's thread; nothing else
+// in the library reads the environment.  All are diagnosis / A-B tools but the AMX_HOST_* placement and batch-plan set: the defaults are the product path.
+enum amx_sw_kind {
+    SW_FLAG,   // on when set to anything but "" and "0..."
+    SW_OFF,    // "=0 disables": the field (opt_no_* / opt_*_no_*) is true when the value starts with '0'
+    SW_GIVEN,  // on when the variable exists, whatever its value
+    SW_CHAR,   // the value's first character (the default when the variable does not exist)
+    SW_INT,    // an integer; `fix` clamps / rounds it, or returns the default to ignore it ("" is ignored)
+    SW_LIST    // up to three integers in `fmt`; the ones not given keep their defaults, every one goes through `fix`
+};
+struct amx_switch {
+    const char *name; amx_sw_kind kind;
+    bool amx_ctx::*flag; long long amx_ctx::*num; long long (amx_ctx::*list)[3];
+    long long dflt[3];
+    long long (*fix)(long long v, long long dflt);
+    const char *fmt, *doc;
+};
+constexpr long long sw_any(long long v, long long) { return v; }
+constexpr long long sw_not_negative(long long v, long long) { return v < 0 ? 0 : v; }
+constexpr long long sw_zero_one(long long v, long long) { return v != 0 ? 1 : 0; }
+constexpr amx_switch sw_flag(const char *n, bool amx_ctx::*f, const char *doc) { return {n, SW_FLAG, f, nullptr, nullptr, {0, 0, 0}, nullptr, nullptr, doc}; }
+constexpr amx_switch sw_off(const char *n, bool amx_ctx::*f, const char *doc) { return {n, SW_OFF, f, nullptr, nullptr, {0, 0, 0}, nullptr, nullptr, doc}; }
+constexpr amx_switch sw_given(const char *n, bool amx_ctx::*f, const char *doc) { return {n, SW_GIVEN, f, nullptr, nullptr, {0, 0, 0}, nullptr, nullptr, doc}; }
+constexpr amx_switch sw_char(const char *n, long long amx_ctx::*f, long long d, const char *doc) { return {n, SW_CHAR, nullptr, f, nullptr, {d, 0, 0}, nullptr, nullptr, doc}; }
+constexpr amx_switch sw_int(const char *n, long long amx_ctx::*f, long long d, long long (*fix)(long long, long long), const char *doc) { return {n, SW_INT, nullptr, f, nullptr, {d, 0, 0}, fix, nullptr, doc}; }
+constexpr amx_switch sw_list(const char *n, long long (amx_ctx::*f)[3], long long d0, long long d1, long long d2, long long (*fix)(long long, long long), const char *fmt, const char *doc) { return {n, SW_LIST, nullptr, nullptr, f, {d0, d1, d2}, fix, fmt, doc}; }
+
+inline constexpr amx_switch kSwitches[] = {
+    // ---- NODDI: which kernels a fit takes
+    sw_flag("AMX_NO_SEED", &amx_ctx::opt_no_seed, "Lawson-Hanson from the empty set in the NNLS stages (the round-2 path)"),
+    sw_flag("AMX_NO_GCERT", &amx_ctx::opt_no_gcert, "every seed is certified by the wavefront-per-voxel kernels (true residual)"),
+    sw_flag("AMX_NO_GCERT_WIDE", &amx_ctx::opt_no_gcert_wide, "no second Gram-certificate pass for LASSO supports of 12 .. 18 atoms"),
+    sw_flag("AMX_NO_SCREEN", &amx_ctx::opt_no_screen, "certify seeds with the full exact sweep of the dual vector"),
+    sw_flag("AMX_S2_EXACT", &amx_ctx::opt_s2_exact, "every voxel's stage-2 products by the exact pass (k_noddi_gemm<true>), none derived from the stage-1 table"),
+    sw_int("AMX_SEED_STAGES", &amx_ctx::opt_seed_stages, 7, [](long long v, long long) { return v & 7; }, "bit 0 = seed stage 1, bit 1 = seed stage 3, bit 2 = seed the LASSO stage"),
+    // (never below kChunk: the left-over passes size their grid by the FIRST plan's chunk count, n / kChunk + ndirs + 1.  Lanes refill from the
+    //  chunk: the more voxels per lane, the smaller the share of the tail; 1 M voxels: 1024 -> 7.2 ms, 2048 -> 7.3, 4096 -> 5.5 for stage 1)
+    sw_int("AMX_SEED_CHUNK", &amx_ctx::opt_seed_chunk, 0, [](long long v, long long d) { return v >= kChunk ? ((v + 63) & ~63LL) : d; },
+           "voxels of one orientation per workgroup of the seed solvers (at least 256, rounded up to a multiple of 64; 0 = by the call's size, make_plan)"),
+    sw_int("AMX_SEED_WAVES", &amx_ctx::opt_seed_waves, 0, [](long long v, long long) { return (v == 1 || v == 2 || v == 4) ? v : 0; },
+           "wavefronts per workgroup of the lane kernels: 1, 2 or 4 (0 = by the number of chunks, make_plan)"),
+    // (the seeded chain of ~16 kernels has a floor of ~1.5 ms; measured, tools/r04/round8.sh: 20 000 voxels 1.58 against 1.49 ms, 25 000 voxels 1.60 against 1.78, 40 000 1.70 against 2.34)
+    sw_int("AMX_SEED_MIN_VOXELS", &amx_ctx::opt_seed_min_voxels, 22528, sw_any, "smaller calls run the wavefront-per-voxel kernels on all voxels"),
+    // (a third more time per trip, twice the wavefronts: wins when the kernel is throughput bound -- 1 M voxels 2.80 -> 2.14 ms --, loses when the longest voxel's path bounds it:
+    //  50 000 voxels 0.54 -> 0.73 ms; with four wavefronts per workgroup the crossover sits between 200 000 and 300 000 voxels; k_lasso_seed: 200 000 voxels 0.50 -> 0.42 ms, 1 M: 1.67 -> 1.27 ms)
+    sw_int("AMX_SEED_OCC2_FROM", &amx_ctx::opt_seed_occ2_from, 65536, sw_any, "calls of at least this many voxels run k_nnls_seed<1> at two wavefronts per SIMD"),
+    sw_int("AMX_SEED2_OCC2_FROM", &amx_ctx::opt_seed2_occ2_from, 65536, sw_any, "the same for k_lasso_seed"),
+    // A lane kernel lasts as long as its slowest voxel, and the slowest are a handful: of 1 M bench voxels 12 need more than 32 stage-1 trips (mean ~10), yet
+    // with the old cap of 64 they held the kernel 0.4 ms longer.  Measured (tools/r04/tripcap2.sh; 50 000 / 200 000 / 1 M voxels, fit in ms): 64,64,64 2.09 /
+    // 3.31 / 8.17; 28,24,12 1.74 / 2.94 / 7.66; below 20 / 18 / 8 the left-over kernels get more voxels than the shorter tails are worth.  (28, 24, 12 before
+    // the normalised entering rule shortened the paths, 24, 24, 10 until the stage-1 solver handed its support on and the LASSO left-over solver started
+    // from the seed: profiles/r05b_tripcaps.txt)
+    sw_list("AMX_SEED_TRIPCAP", &amx_ctx::opt_seed_tripcap, 20, 20, 10, [](long long v, long long) { return v < 4 ? 4 : v; }, "%lld,%lld,%lld",
+            "a,b,c: trips after which k_nnls_seed<1> / k_lasso_seed / k_nnls_seed<3> give a voxel up (at least 4; no seed: it goes to the left-over kernels)"),
+    sw_flag("AMX_NO_CHUNK_ORDER", &amx_ctx::opt_no_chunk_order, "the chunks of the second plan stay in orientation order (default: longest first)"),
+    sw_flag("AMX_NO_HARD_FIRST", &amx_ctx::opt_no_hard_first, "the left-over kernels of the NNLS stages walk their lists in the order the certificates wrote them"),
+    sw_int("AMX_RESCUE_FROM", &amx_ctx::opt_rescue_from, -1, sw_not_negative,
+           "calls of n voxels and more run the rescue pass of the NNLS certificates (k_nnls_gcert<., true>), and the threshold alone decides (not given: kRescueFrom, and every call of a protocol of more than 128 volumes)"),
+    sw_int("AMX_GCERT_REPAIR", &amx_ctx::opt_gcert_repair, -1, sw_zero_one, "0 / 1: never / always the NNLS certificates' second look at a mendable seed (default: where the tile is read from L2)"),
+    sw_int("AMX_GCERT2_THIRD", &amx_ctx::opt_gcert2_third, -1, sw_zero_one, "0 / 1: never / always a third LASSO certificate pass (default: where the tile is read from L2, and large calls of 96 .. 128 volumes)"),
+    sw_off("AMX_BIG_ALL", &amx_ctx::opt_no_big_all, "=0: lambda1 = 0 fits take the fast kernels first and reach k_noddi_lasso_big through the overflow lists"),
+    // (round 6: a recorded negative result, profiles/r06_fork_negative.txt.  Bit 1 is a correct fit -- the forked voxels skip the stage-3 lane kernels and end in
+    //  k_noddi<3> on the side stream; bit 0 is a TIMING PROBE only: the stage-2 lane kernels read the x_iso the previous call left for those voxels)
+    sw_int("AMX_FORK", &amx_ctx::opt_fork, 0, [](long long v, long long) { return v & 3; },
+           "bit 0 / bit 1: the left-over kernels of stage 1 / of the LASSO stage run on a side stream beside the next stage's lane kernels (noddi_fit_dev)"),
+    // ---- the small models, signal preparation
+    sw_flag("AMX_WAVE_PER_VOXEL", &amx_ctx::opt_wave_per_voxel, "small models by the wavefront-per-voxel kernels"),
+    sw_flag("AMX_NO_REFILL", &amx_ctx::opt_no_refill, "FreeWater by k_freewater_lane (one solve per lane and pass)"),
+    sw_flag("AMX_FW_NO_FUSE", &amx_ctx::opt_fw_no_fuse, "FreeWater by the projection + solver kernel pair instead of k_freewater_fused"),
+    sw_flag("AMX_SANDI_ATOM_SPACE", &amx_ctx::opt_sandi_atom_space, "SANDI 6 x 15 by the atom-space lane kernel"),
+    sw_flag("AMX_PREP_SCALAR", &amx_ctx::opt_prep_scalar, "the streaming preparation kernel with one voxel per lane (4-byte loads) instead of four (tools/r04/prep.sh)"),
+    // ---- the host-buffer entry points (README.md, "Behaviour-changing defaults of the host-buffer calls")
+    sw_flag("AMX_HOST_ONE_SHOT", &amx_ctx::opt_host_one_shot, "host-buffer entry points upload everything, then fit"),
+    sw_flag("AMX_HOST_LATE_RESULTS", &amx_ctx::opt_host_late_results, "the results of a host-buffer call go home in one copy after the last batch"),
+    sw_off("AMX_HOST_NATIVE32", &amx_ctx::opt_host_no_native32, "=0: float32 batches are widened on the device first (the round-5 behaviour)"),
+    sw_off("AMX_HOST_NARROW", &amx_ctx::opt_host_no_narrow, "=0: float64 host signals are always copied as they are (amx_stage.hpp)"),
+    // (from 3 x 131 072 voxels a call has two batches -- the first short -- and the second copy hides behind the first fit: 400 000 voxels 7.63 -> 6.85 ms (float32 signals 6.94 -> 6.08),
+    //  500 000 8.66 -> 7.92 (8.30 -> 7.51); was 524 288 while a float64 copy took twice as long (profiles/r05c_host_transport.txt, section 9))
+    sw_int("AMX_HOST_PIPELINE_FROM", &amx_ctx::opt_host_pipeline_from, 393217, [](long long v, long long d) { return v >= 262144 ? v : d; },
+           "host-buffer calls of fewer voxels upload everything, then fit (at least 262144: a pipelined call has a first batch of 131 072 voxels and a second one at least as long)"),
+    sw_int("AMX_HOST_RAMP", &amx_ctx::opt_host_ramp, 131072, [](long long v, long long) { return v <= 0 ? 0 : (v > 131072 ? 131072 : ((v + 3) & ~3LL)); },
+           "voxels of the first pipelined batch (its copy is the only one nothing hides; at most 131072, a multiple of 4; 0 = equal batches)"),
+    sw_int("AMX_HOST_BATCH", &amx_ctx::opt_host_batch, 393216, [](long long v, long long d) { return v >= 131072 ? ((v + 3) & ~3LL) : d; },
+           "voxels per pipelined batch (a multiple of 4: k_widen reads float4; at least the largest ramp batch, 131072: the ramp batches are written into slots of this size)"),
+    sw_int("AMX_HOST_THREADS", &amx_ctx::opt_host_threads, 12, [](long long v, long long d) { return v >= 1 ? (v > 64 ? 64 : v) : d; },
+           "host threads that narrow + send float64 host signals (1 .. 64; at most half the logical CPUs)"),
+    sw_char("AMX_HOST_PIN", &amx_ctx::opt_host_pin, 'g', "gpu / caller / 0: those threads run on the device's NUMA node (their share of its cores), on the calling thread's node, anywhere"),
+    sw_char("AMX_HOST_PIN_CORES", &amx_ctx::opt_host_pin_cores, 0, "0: the threads share the node's CPUs as one set, 1: one core per thread (default: a stripe of the node's physical cores each)"),
+    sw_off("AMX_HOST_PREFETCH", &amx_ctx::opt_host_no_prefetch, "=0: the pool of those threads is made inside the first fit that needs it instead of beside the dictionary upload"),
+    sw_list("AMX_HOST_SIBLINGS", &amx_ctx::opt_host_siblings, -1, 0, 0, sw_any, "%lld/%lld", "i/n: the pool takes the i-th of n shares of its node's cores, whatever devices hang on the node (diagnosis, tests)"),
+    // (set by the launcher, one visible device per process: who else drives a device of this node -- amx_stage::device_siblings)
+    sw_int("LOCAL_RANK", &amx_ctx::opt_local_rank, -1, sw_any, "the launcher's (torchrun) local rank: with LOCAL_WORLD_SIZE, this process's share of the node's cores"),
+    sw_int("LOCAL_WORLD_SIZE", &amx_ctx::opt_local_world, -1, sw_any, "the launcher's number of processes on this host"),
+    // ---- tracing
+    sw_given("AMX_HOST_TRACE", &amx_ctx::opt_host_trace, "wall-clock timeline of every host-buffer call on stderr: per batch the wait for its buffer, its copy, its enqueue (tools/r05/host_trace.py)"),
+    sw_flag("AMX_DEBUG", &amx_ctx::opt_debug, "synchronise after every launch and trace progress and counters on stderr"),
+};
+
+// defaults of switches that were retired with nothing setting them (the measurements stay):
+// calls of fewer voxels run the left-over kernels of stage 1 / stage 3 in their small-call builds (float32 tile, 4 wavefronts, two workgroups per CU:
+// amx_noddi_s1.hip).  Measured (tools/r06/a05.sh; 50 000 / 100 000 / 200 000 / 300 000 / 500 000 / 1 M voxels, fit in ms, round-5 builds 1.441 / 1.817 /
+// 2.386 / 2.885 / 4.000 / 6.421): stage 1 alone 1.421 / 1.793 / 2.394 / 2.921 / 4.072 / 6.591; stage 3 alone 1.415 / 1.797 / 2.371 / 2.849 / 3.989 / 6.506
+// (its 12-wavefront build spills 117 registers, this one none); the LASSO stage's (two wavefronts, no screening table) lost at every size (1.460 / 1.905 /
+// 2.511 / ...) and is gone.  The gain is ~20 us per kernel, not the ~100 the "one round of workgroups instead of two" arithmetic promised: a left-over
+// kernel lasts as long as its longest voxel's Lawson-Hanson, whatever the rounds.
+constexpr long long kLeftSmall1 = 150000, kLeftSmall3 = 600000;
+constexpr long long kRescueFrom = 2000000;   // voxels from which the NNLS certificates run their rescue pass (amx_launch_noddi_gcert; AMX_RESCUE_FROM)
 
 struct amx_lut {
     amx_ctx *ctx = nullptr;
@@ -301,10 +351,9 @@ enum { ZC_CERT1 = 0, ZC_RESC1, ZC_CLIP, ZC_CERT2, ZC_CERT2W, ZC_CERT2W3, ZC_CERT
 static_assert(kFeedSets == Plan::kFeedSetsN, "Plan::zcount sits behind the feed sets");
 
 // AMX_DEBUG=1: synchronise after every launch and trace progress on stderr
-static inline bool amx_debug() { static int d = -1; if (d < 0) { const char *e = getenv("AMX_DEBUG"); d = (e && *e && *e != '0') ? 1 : 0; } return d == 1; }
 #define AMX_TRACE(ctx, s, what)                                                                   \
     do {                                                                                          \
-        if (amx_debug()) {                                                                        \
+        if ((ctx)->opt_debug) {                                                                   \
             fprintf(stderr, "[amx] %s ...", what); fflush(stderr);                                \
             hipError_t e_ = hipStreamSynchronize(s);                                              \
             fprintf(stderr, " %s\n", hipGetErrorString(e_)); fflush(stderr);                      \
@@ -327,7 +376,7 @@ int amx_launch_noddi_s2prep(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiAr
 int amx_gemm_ksteps(const amx_lut *lut);   // K-steps of the table kernels for this dictionary (25 / 40), 0 = shape not supported
 int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, bool wide);
 bool amx_gcert2_third(const amx_ctx *ctx, const amx_lut *lut, bool wide);
-int amx_gcert2_third_min_items(const amx_ctx *ctx, const amx_lut *lut);   // list entries a chunk must hold for that pass to work on it   // a third LASSO certificate pass for this dictionary? (amx_seed.hip)
+int amx_gcert2_third_min_items(const amx_ctx *ctx, const amx_lut *lut);   // list entries a chunk must hold for that pass to work on it (amx_seed.hip)
 size_t amx_gcert2_leftover_offset(const Plan &pl, bool wide, bool third);      // which half of ctx->rlist the LASSO certificate passes end in (amx_seed.hip)
 const int *amx_gcert2_leftover_counts(const Plan &pl, bool wide, bool third);  // ... and the per-chunk counts of those lists (Plan::zcount)
 static inline size_t amx_rlist_half(const Plan &pl) { return (size_t)pl.n + pl.max_schunks + 64; }   // ints per left-over list + counts
@@ -348,27 +397,25 @@ int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, amx::FwArgs &a, hipStream_t
 int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, amx::SandiArgs &a, hipStream_t s);   // before amx_launch_fw when the refill path runs
 int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
 // Lane-per-voxel solvers: start the active set from ALL atoms and drop the non-positive ones in blocks (unique optimum
-// with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  AMX_COLD_START=1: the
-// Lawson-Hanson start from the empty set.  Needs a ridge that keeps the full system well conditioned.
+// with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
+// the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.
 __host__ __device__ static inline bool amx_warm_start(double lam2, unsigned flags) { return lam2 >= 1e-5 && !(flags & 0x80000000u); }
 // FreeWater with lanes that never idle (k_freewater_refill, amx_small.hip): maps only (the error maps / corrected DWI
 // need the signal again and stay with k_freewater_lane), <= 12 atoms; chunks of up to 4096 voxels per workgroup
 // voxels of one orientation per workgroup of the refill kernel: large enough to keep the lanes fed (the buffer needs a
 // pool to draw from), small enough for ~3 rounds of workgroups over the chip (measured on 2 M voxels: 512 -> 1.83 ms,
 // 1024 -> 1.79, 2048 -> 1.93, 4096 -> 2.54)
-static inline int amx_refill_chunk(const amx_ctx *ctx, long long n_vox)
+static inline int amx_refill_chunk(long long n_vox)
 {
-    const int v = ctx->opt_refill_chunk;
-    if (v >= AMX_CHUNK) return v;                       // (make_plan sizes the chunk list for kChunk: smaller chunks would overrun it)
     const long long c = n_vox / 1536;
     return (int)(c < 512 ? 512 : (c > 2048 ? 2048 : c));
 }
-// (the projection + block-pivoting kernels assume the warm start: with lambda2 < 1e-5, or AMX_COLD_START=1, the fit goes to the
+// (the projection + block-pivoting kernels assume the warm start: with lambda2 < 1e-5 the fit goes to the
 //  Lawson-Hanson lane kernels -- single exchanges from the empty set, which is all block pivoting could do there, ran into
 //  the iteration cap on 15 % of the voxels at lambda2 = 1e-6)
 static inline bool amx_fw_use_refill(const amx_ctx *ctx, int n_atoms, int nS, unsigned flags, double lam2)
 {
-    if (!amx_warm_start(lam2, flags) || ctx->opt_cold_start) return false;
+    if (!amx_warm_start(lam2, flags)) return false;
     if (ctx->opt_no_refill || ctx->opt_wave_per_voxel) return false;
     return n_atoms <= 12 && (flags & (AMX_F_RMSE | AMX_F_NRMSE | AMX_F_CORRECTED)) == 0 &&
            ((size_t)nS * 12 + 144 + 4 * (16 * 65 + 12 * 64 + 32)) * sizeof(double) + 16 <= 80 * 1024;
@@ -383,5 +430,5 @@ static inline bool amx_use_lane_solver(const amx_ctx *ctx, int n_atoms, double l
 static inline bool amx_fw_native_f32(const amx_ctx *ctx, int n_atoms, int nS, unsigned flags, double lam2)
 {
     if (!amx_use_lane_solver(ctx, n_atoms, lam2)) return true;                     // wavefront per voxel: load_rows
-    return amx_fw_use_refill(ctx, n_atoms, nS, flags, lam2) && nS <= 96 && !ctx->opt_fw_proj_valu;
+    return amx_fw_use_refill(ctx, n_atoms, nS, flags, lam2) && nS <= 96;
 }

@@ -565,7 +565,7 @@ __device__ __forceinline__ void czb_voxel(const CzbArgs &a, const float *As, dou
     }
     if (ok) {
     typename std::conditional<QR, NNSolver<NR, NQ, MAXP, true, float>, GramSolver<NR, NQ, MAXP, float>>::type S;
-    // strong ridge, dense optimum: block principal pivoting from the full set; otherwise (or AMX_COLD_START) Lawson-Hanson
+    // strong ridge, dense optimum: block principal pivoting from the full set; otherwise (or flag bit 31: cold start) Lawson-Hanson
     const bool dense = NQ == 1 && n_atoms <= MAXP && a.c.lam2 >= 1e-2 && !(a.c.flags & 0x80000000u);
     int st_;
     if constexpr (QR) {
@@ -714,11 +714,6 @@ __global__ void __launch_bounds__(NW * 64, (NW <= 4 && !LIST && !GT) ? 2 : 1) k_
             for (int e = threadIdx.x; e < kSeedKD * kScreenLd; e += blockDim.x) Sf[e] = src[e];
         }
         __syncthreads();
-#ifdef AMX_STATIC_VOXELS
-        for (int k = wave; k < ck.count; k += nw_) {
-            noddi_voxel<STAGE, NR, NQ, MAXP, ATs>(a, reinterpret_cast<const ATs *>(At), rs, rl, wmask, a.c.perm[ck.start + k], ck.dir, lane);
-        }
-#else
         // voxels differ 2-3x in solver iterations: the wavefronts draw the next voxel of the chunk from an LDS ticket
         // (next_ticket keeps the control flow wave-uniform: every lane takes part in the atomic)
         if ((STAGE == 1 || STAGE == 3 || STAGE == 4) && a.rlist != nullptr) {
@@ -743,7 +738,6 @@ __global__ void __launch_bounds__(NW * 64, (NW <= 4 && !LIST && !GT) ? 2 : 1) k_
                 noddi_voxel<STAGE, NR, NQ, MAXP, ATs>(a, reinterpret_cast<const ATs *>(At), rs, rl, wmask, a.c.perm[ck.start + k], ck.dir, lane, ck.start + k, Sf);
             }
         }
-#endif
     } else {
         const int cnt = *a.c.list_count;
         for (int it = blockIdx.x; it < cnt; it += gridDim.x) {

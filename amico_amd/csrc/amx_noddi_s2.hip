@@ -18,22 +18,14 @@ template <int NR>
 static int go_gram(amx_ctx *ctx, NoddiArgs &a, const Plan &pl, hipStream_t s)
 {
     constexpr int NQ = 3, MP = 20, MB = 64;
-    constexpr int NW = AMX_S2_NW;
+    constexpr int NW = 16;
     const size_t scr = (a.scr2_S && a.seeds2) ? (size_t)kSeedKD * kScreenLd * sizeof(float) : 0;   // screening table (amx_gram_solver.hpp)
     if (a.rlist != nullptr && a.seeds2 != nullptr) {
         // left-over lists of the Gram certificates: few voxels, mostly seeds of more than 16 atoms -- half the wavefronts with
         // room for 32 atoms each, so that practically nothing is left for the (slow, one wavefront per voxel) re-run kernel
-        constexpr int MPL = 32, NWL = AMX_S2_NW / 2;
-        // small calls: two workgroups per CU (amx_noddi_s1.hip) -- two wavefronts with room for 32 atoms each and no screening table (the
-        // certificate of a seed then takes the exact sweep of the dual vector: same decisions, 9 KB of LDS less): 78 KB
-        if ((long long)pl.n < ctx->opt_left_small[1] && 2 * fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 2, MPL, true) <= kLdsPerCU) {
-            NoddiArgs b = a;
-            b.scr2_S = nullptr;
-            const int rc = launch_pair<2>(ctx, b, pl, s, k_noddi<4, NR, NQ, MPL, 2, false>, k_noddi<4, NR, NQ, MB, 1, true>,
-                                          [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MPL, true); }, fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, true),
-                                          1, 4, "k_noddi<4> (left-overs of k_lasso_gcert; small-call build: two workgroups per CU)", true);
-            return rc;
-        }
+        constexpr int MPL = 32, NWL = NW / 2;
+        // (a small-call build as in amx_noddi_s1.hip -- two wavefronts with room for 32 atoms each, no screening table, two workgroups per CU -- lost at
+        //  every call size, amx_host.hpp: kLeftSmall1, and is gone)
         return launch_pair<NWL>(ctx, a, pl, s, k_noddi<4, NR, NQ, MPL, NWL, false>, k_noddi<4, NR, NQ, MB, 1, true>,
                            [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MPL, true) + scr; }, fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, true),
                            1, 4, a.rlist ? "k_noddi<4|2> (left-overs of k_lasso_gcert)" : "k_noddi<4|2> (all voxels)", true);
@@ -63,7 +55,7 @@ static int go_global(amx_ctx *ctx, NoddiArgs &a, const Plan &pl, hipStream_t s, 
 
 int amx_launch_noddi_s2(amx_ctx *ctx, NoddiArgs &a, const Plan &pl, hipStream_t s)
 {
-    const bool gram = a.gram_dwi != nullptr && a.c.lam2 >= 1e-5 && !ctx->opt_lasso_qr;
+    const bool gram = a.gram_dwi != nullptr && a.c.lam2 >= 1e-5;
     int rc;
     // lambda1 = 0 (a pure ridge: set_solver(lambda1=0, ...)): the optimum holds most of the dictionary -- every voxel would walk Lawson-Hanson
     // to 20, then 64 atoms and overflow twice on its way to the solver that can hold it: straight there (AMX_BIG_ALL=0: the long way, diagnosis)

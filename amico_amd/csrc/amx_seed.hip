@@ -67,17 +67,13 @@ int amx_launch_noddi_seed2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
     sa.ytil = (double *)ctx->ytil2.p; sa.seeds = (unsigned long long *)ctx->seeds2.p;
     sa.nS = lut->nS; sa.n_wm = lut->n_wm; sa.iso_atom = lut->n_atoms - 1; sa.is_exvivo = lut->is_exvivo;
     sa.lam1 = a.c.lam1; sa.lam2 = a.c.lam2;
-    sa.trip_cap = ctx->opt_seed_tripcap[1];
+    sa.trip_cap = (int)ctx->opt_seed_tripcap[1];
     // supports of up to 24 atoms are certified lane-per-voxel where the third pass runs: the seed solver goes on to 26 atoms there
     // (and gets 2 atoms per trip: the trip cap grows with it); elsewhere 20 (the second pass ends at 18)
     sa.max_atoms = 20;
-    if (ctx->opt_seed2_maxatoms > 0) sa.max_atoms = ctx->opt_seed2_maxatoms;
-    else if (have_ytil2 && amx_gcert2_third(ctx, lut, !ctx->opt_no_gcert_wide)) { sa.max_atoms = 26; sa.trip_cap += 6; }
+    if (have_ytil2 && amx_gcert2_third(ctx, lut, !ctx->opt_no_gcert_wide)) { sa.max_atoms = 26; sa.trip_cap += 6; }
 #ifdef AMX_STATS
     sa.stats = a.c.status + ST_SEED + 20;
-#endif
-#ifdef SEED2_TRACE
-    sa.trace = (double *)ctx->seeds.p; hipMemsetAsync(ctx->seeds.p, 0, 8 * 8 * 80, s);
 #endif
     const dim3 grid(((pl.max_chunks + 7) / 8) * 8);
     if (!have_ytil2) {
@@ -111,7 +107,7 @@ static void fill(SeedArgs &sa, const amx_lut *lut, const NoddiArgs &a, const Pla
     sa.ytil = (double *)ctx->ytil.p; sa.seeds = (unsigned long long *)ctx->seeds.p;
     sa.nS = lut->nS; sa.n_atoms = lut->n_atoms; sa.iso_atom = lut->n_atoms - 1;
     sa.dot_atom = lut->is_exvivo ? lut->n_atoms - 2 : -1;
-    sa.trip_cap = ctx->opt_seed_tripcap[0];
+    sa.trip_cap = (int)ctx->opt_seed_tripcap[0];
 #ifdef AMX_STATS
     sa.stats = a.c.status + ST_SEED + 4;
 #endif
@@ -230,7 +226,7 @@ bool amx_gcert2_third(const amx_ctx *ctx, const amx_lut *lut, bool wide)
 int amx_gcert2_third_min_items(const amx_ctx *ctx, const amx_lut *lut)
 {
     if (ctx->opt_gcert2_third == 1 || amx_noddi_tile_global(lut->nS, lut->ldA, lut->n_atoms)) return 0;
-    return ctx->opt_gcert2_third_min;
+    return 16;                    // (tiles in LDS)
 }
 
 // Gram-space certificates of the LASSO seeds (k_lasso_gcert): support bits of the voxels it settles, left-over lists for k_noddi<4>
@@ -349,8 +345,9 @@ int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
     // (round 6: ... and protocols of more than 128 volumes, whose wavefront-per-voxel kernels hold four signal rows per lane -- a left-over voxel
     //  costs them 37 ns against 14 at 99 volumes: 150 volumes, 1 M voxels 11.23 -> 10.65 ms with the pass, stage-3 left-overs 38 219 -> 6 429;
     //  at 99 - 105 volumes it still loses below 2 M voxels, SNR 50 included: profiles/r06_protocols_ab.txt)
-    if ((ctx->in_host_fit ? ctx->host_total_vox : (int64_t)pl.n) >= (lut->is_exvivo ? ctx->opt_rescue_from / 4 : ctx->opt_rescue_from) ||
-        (lut->nS > 128 && ctx->opt_rescue_from > 0 && !ctx->opt_rescue_from_set) ||
+    const int64_t rescue_from = ctx->opt_rescue_from >= 0 ? ctx->opt_rescue_from : kRescueFrom;   // (AMX_RESCUE_FROM given: the caller's threshold alone decides)
+    if ((ctx->in_host_fit ? ctx->host_total_vox : (int64_t)pl.n) >= (lut->is_exvivo ? rescue_from / 4 : rescue_from) ||
+        (lut->nS > 128 && ctx->opt_rescue_from < 0) ||
         amx_noddi_tile_global(lut->nS, lut->ldA, lut->n_atoms)) {
         // second pass (large calls: below ~2 M voxels the launch costs more than the wavefront-per-voxel kernel saves -- 1 M voxels
         // 8.08 -> 8.24 ms with it, 4 M 24.99 -> 24.38): the supports refused for conditioning, corrected with the signal itself;
@@ -394,7 +391,7 @@ int amx_launch_noddi_seed(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a, 
     SeedArgs sa; fill(sa, lut, a, pl, ctx);
     sa.supp = stage == 3 ? a.supp : nullptr;
     if (stage == 3 && a.cand_lists && a.seeds2 != nullptr) { sa.cand8 = a.seeds2; sa.cdone = (const unsigned char *)ctx->done.p; sa.fork_skip = a.fork_l2; }
-    sa.trip_cap = ctx->opt_seed_tripcap[stage == 1 ? 0 : 2];
+    sa.trip_cap = (int)ctx->opt_seed_tripcap[stage == 1 ? 0 : 2];
     // S for the per-lane gathers + ticket; stage 1 adds S in MFMA operand order (10 x 3 x 64) and a residual block per wavefront
     const size_t lds = (size_t)lut->n_atoms * kSeedLd * sizeof(double) + 64 +
                        (stage == 1 ? ((size_t)10 * (kSeedKD / 4) * 64 + (size_t)4 * 64 * (kSeedKD + 1)) * sizeof(double)

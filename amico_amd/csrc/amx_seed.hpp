@@ -26,9 +26,7 @@ namespace amx {
 
 constexpr int kSeedMax = 8;      // passive-set capacity of the seed solver (= MAXP of the NNLS stage kernels)
 constexpr int kSeed3ListRow = 36;      // bytes per lane of the stage-3 candidate lists in LDS (k_nnls_seed<3>)
-#ifndef SEED3_SCAN_MAX
-#define SEED3_SCAN_MAX 32      // (diagnosis: a smaller value truncates the stage-3 candidate scan)
-#endif
+constexpr int kSeed3ScanMax = 32;      // (diagnosis: a smaller value truncates the stage-3 candidate scan)
 // one column of S for THIS lane from the LDS copy (row stride kSeedLd doubles = 112 bytes: 16-byte aligned rows): 16-byte reads --
 // the per-lane gathers are bound by the NUMBER of LDS instructions (a float32 copy with half the bytes changed nothing, reads of
 // twice the width took 9 % off the stage-3 seed solver)
@@ -36,13 +34,9 @@ constexpr int kSeed3ListRow = 36;      // bytes per lane of the stage-3 candidat
 // keeps ONE load per thread in flight -- it may not hoist a load over the guard of its iteration --, so staging a chunk was a chain
 // of 7 + 8 memory round trips: ~13 us per workgroup and chunk, all of it exposed in small calls and in the table GEMM, whose one
 // workgroup per CU multiplies nothing meanwhile.  Here the loads are unconditional at clamped indices and the guards sit on the stores.)
-#ifndef AMX_STAGE_UBN
-#define AMX_STAGE_UBN 2
-#endif
-#ifndef AMX_STAGE_UB
-#define AMX_STAGE_UB 4
-#endif
-template <int KD, int LD, int UB = AMX_STAGE_UB>
+constexpr int kStageUbNorm = 2;
+constexpr int kStageUb = 4;
+template <int KD, int LD, int UB = kStageUb>
 __device__ __forceinline__ void stage_rows(double *Sl, const double *__restrict__ Sg, int n, int src_ld)
 {
     const int N = n * KD;
@@ -62,7 +56,7 @@ __device__ __forceinline__ void stage_rows(double *Sl, const double *__restrict_
 }
 // the same rows in MFMA operand order: Aop[(mt KS + ks) 64 + l] = S[16 mt + (l & 15)][4 ks + (l >> 4)], 0 beyond n rows;
 // NORM: every row scaled to unit length (k_nnls_seed stage 1)
-template <int KS, int MT, bool NORM = false, int UB = AMX_STAGE_UB>
+template <int KS, int MT, bool NORM = false, int UB = kStageUb>
 __device__ __forceinline__ void stage_operand(double *Aop, const double *__restrict__ Sg, int n, int src_ld)
 {
     constexpr int KD = 4 * KS, N = MT * KS * 64;
@@ -580,9 +574,6 @@ struct SeedFeed {
 __device__ __forceinline__ int seed_next_chunk(int round, int own, const Chunk *schunks, int n_schunks, const int *gcount, int *steal, int *lds_slot, int min_left)
 {
     if (round == 0) return own;
-#ifdef AMX_SEED_NO_STEAL
-    return -1;
-#endif
     if (threadIdx.x == 0) {
         int pick = -1;
         for (int tries = 0; tries < 12 && pick < 0; tries++) {
@@ -632,24 +623,18 @@ struct BlockFeed {
 // (MS = 8: the compiler needs ~540 registers for this kernel; at two wavefronts per SIMD it spilled 290 of them and the kernel moved
 //  27 GB + 9 GB of scratch per 1 M voxels (rocprofv3 FETCH_SIZE / WRITE_SIZE) -- at one wavefront per SIMD, with the accumulation
 //  registers as overflow, none: 5.1 -> 3.4 ms)
-#ifndef AMX_SEED1_OCC
-#define AMX_SEED1_OCC 1
-#endif
+constexpr int kSeed1Occ = 1;
 // (stage 3: PINNED at two wavefronts per SIMD.  Left to itself -- bound 1 -- the compiler landed on either side of 256 registers
 //  with every unrelated edit of this file, and the kernel ran 0.81 or 1.16 ms per 1 M voxels accordingly.  Without the next-voxel
 //  prefetch: 204 VGPRs, 0.79 ms; with it 256 + 4 spilled, 0.82 ms.)
-#ifndef AMX_SEED3_OCC
-#define AMX_SEED3_OCC 2
-#endif
-#ifndef AMX_SEED3_PREF
-#define AMX_SEED3_PREF 0
-#endif
+constexpr int kSeed3Occ = 2;
+constexpr bool kSeed3Pref = false;
 // OCC2 (stage 1, calls of >= ~0.5 M voxels): two wavefronts per SIMD -- no next voxel reserved in registers, no software pipeline
 // in the scan (244 VGPRs, no scratch): a trip is a third longer, but two wavefronts hide each other's dependent chains and the
 // kernel is throughput bound at that size (1 M voxels: 2.80 -> 2.14 ms).  Small calls are bound by the longest single voxel's path:
 // there the one-wavefront build with the shorter trip wins (50 000 voxels: 0.54 against 0.73 ms).
 template <int STAGE, int MS, bool OCC2 = false>
-__global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AMX_SEED3_OCC)) k_nnls_seed(const SeedArgs a)
+__global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : kSeed1Occ) : kSeed3Occ)) k_nnls_seed(const SeedArgs a)
 {
     constexpr int KD = kSeedKD, LD = kSeedLd;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];
@@ -684,16 +669,11 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AM
         // residual best, not the one with the largest dual value -- Lawson-Hanson may admit any atom with a positive dual value, and
         // this rule needs 10.4 instead of 11.0 trips per voxel (95th percentile 15 instead of 17; tools/lab/two_add_lab.py rule 4).
         // The sign of a dual value, and with it the stopping test, is unchanged; the append below works on the atoms themselves.
-#ifndef AMX_SEED_SCAN_NORM
-#define AMX_SEED_SCAN_NORM 1
-#endif
-        stage_operand<KS, MT, AMX_SEED_SCAN_NORM != 0, AMX_STAGE_UBN>(Aop, Sg, n_atoms, KD);
+        stage_operand<KS, MT, true, kStageUbNorm>(Aop, Sg, n_atoms, KD);
     }
     __syncthreads();
-#ifndef AMX_SEED_ISO_FIRST
-#define AMX_SEED_ISO_FIRST 3          // bit 0: stage 1 (two-wavefront build), bit 1: stage 3
-#endif
-    constexpr bool iso_first = (STAGE == 1 && OCC2 && (AMX_SEED_ISO_FIRST & 1)) || (STAGE == 3 && (AMX_SEED_ISO_FIRST & 2));
+    constexpr int kIsoFirst = 3;          // bit 0: stage 1 (two-wavefront build), bit 1: stage 3
+    constexpr bool iso_first = (STAGE == 1 && OCC2 && (kIsoFirst & 1)) || (STAGE == 3 && (kIsoFirst & 2));
     const double tol = 1e-10, inf = __builtin_huge_val();
     const int trip_cap = a.trip_cap;
 
@@ -709,9 +689,9 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AM
     // Stage 1 (one wavefront per SIMD, registers to spare): the voxel's y~ stays in registers, and a lane RESERVES its next voxel
     // while it works on the current one -- the 12 loads of the next y~ are in flight for a whole solve instead of being waited
     // for in every trip in which some lane of the wavefront refills (measured: 15 % of the kernel).
-    // (stage 3 could do the same, AMX_SEED3_PREF=1, with the admissible-atom mask of the next voxel next to its y~: no gain at two
-    //  wavefronts per SIMD, see AMX_SEED3_OCC)
-    constexpr bool PREF = (MS > 6 && !OCC2 && AMX_SEED1_OCC == 1) || (STAGE == 3 && AMX_SEED3_PREF);
+    // (stage 3 could do the same, kSeed3Pref, with the admissible-atom mask of the next voxel next to its y~: no gain at two
+    //  wavefronts per SIMD, see kSeed3Occ)
+    constexpr bool PREF = (MS > 6 && !OCC2 && kSeed1Occ == 1) || (STAGE == 3 && kSeed3Pref);
     double yv[PREF ? KD : 1], ynext[PREF ? KD : 1];
     unsigned long long nallow[(PREF && STAGE == 3) ? 4 : 1];
     int next_pos = -1;
@@ -859,11 +839,9 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AM
                     for (int s = 0; s < MS; s++) gone = (s == kmin) ? V.idx[s] : gone;
                     if (gone == last_added) { ban1 = ban0; ban0 = gone; }
                 }
-#ifndef SEED_NO_REMOVE
                 __builtin_amdgcn_sched_barrier(0);
                 V.remove((active && kmin >= 0) ? kmin : MS);
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 V.solve(z);
                 if (active && kmin >= 0) {
                     if (!ok) scan = false;                     // (numerically dependent set: the next trip's step sorts it out)
@@ -899,11 +877,7 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AM
             int bj = -1;
             if (STAGE == 1) {
                 if (n_atoms <= 16 * MT) {
-#ifndef SEED_NO_MFMA
-                    seed_scan_mfma<KS, MT, (!OCC2 && AMX_SEED1_OCC == 1)>(Aop, Rb, r, lane, best, bj);
-#else
-                    best = r[0] + r[5]; bj = (int)(r[1] * 100.0) & 127;
-#endif
+                    seed_scan_mfma<KS, MT, (!OCC2 && kSeed1Occ == 1)>(Aop, Rb, r, lane, best, bj);
                 } else {
                     for (int j = 0; j < n_atoms; j++) {
                         const double *sp = Sg + (size_t)j * KD;              // wave-uniform address: scalar loads
@@ -933,7 +907,7 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : AMX_SEED1_OCC) : AM
                 // candidates = the lane's byte list (<= 32 atoms): per-lane gathers of their columns, two per step (two
                 // independent chains: the loop is a chain of LDS latencies and dependent FMAs otherwise)
 #pragma unroll
-                for (int it = 0; it < SEED3_SCAN_MAX; it += 2) {
+                for (int it = 0; it < kSeed3ScanMax; it += 2) {
                     if (__ballot(scan && it < ncand) == 0ull) break;
                     const int j0 = (int)((cand[STAGE == 3 ? (it >> 3) : 0] >> (8 * (it & 7))) & 0xffull);
                     const int j1 = (int)((cand[STAGE == 3 ? ((it + 1) >> 3) : 0] >> (8 * ((it + 1) & 7))) & 0xffull);
@@ -1562,9 +1536,7 @@ struct GcertArgs {
 // solve, screening, exact dual values) runs once more on the mended support.  tools/lab/repair_lab.py: at 288 volumes one such step
 // settles 2.8 of the 4.5 % (the left-over kernel reads its tile from L2 there: ~300 us per voxel); at 99 volumes 0.08 of 0.87 %, and
 // every third block would pay a second pass for it: off there.
-#ifndef AMX_REPAIR_ROUNDS
-#define AMX_REPAIR_ROUNDS 1
-#endif
+constexpr int kRepairRounds = 1;
 template <int STAGE, bool RESCUE = false, bool REPAIR = false>
 __global__ void __launch_bounds__(256, RESCUE ? 1 : 2) k_nnls_gcert(const GcertArgs a)
 {
@@ -1650,7 +1622,7 @@ __global__ void __launch_bounds__(256, RESCUE ? 1 : 2) k_nnls_gcert(const GcertA
         static_assert(!(RESCUE && REPAIR), "the rescue pass takes the first pass's lists as they are");
         bool cert_any = false, easy_any = false, live = true;
 #pragma unroll 1
-        for (int rep = 0; rep < (REPAIR ? AMX_REPAIR_ROUNDS + 1 : 1); rep++) {
+        for (int rep = 0; rep < (REPAIR ? kRepairRounds + 1 : 1); rep++) {
         unsigned long long cand[3] = {~0ull, ~0ull, ~0ull};          // admissible atoms outside the seed
         if (STAGE == 3) {
 #pragma unroll
@@ -1919,7 +1891,7 @@ __global__ void __launch_bounds__(256, RESCUE ? 1 : 2) k_nnls_gcert(const GcertA
                 for (int s = 0; s < MS; s++) if (s < V.np) dst[V.idx[s]] = V.x[s];
             }
         }
-        if (REPAIR && rep < AMX_REPAIR_ROUNDS) {
+        if (REPAIR && rep < kRepairRounds) {
             // who gets a second look: a well-conditioned block with a non-positive coefficient (those atoms leave), or with every
             // coefficient positive and a positive dual value outside (that atom enters)
             const bool base = live && valid && okv && !cert && piv && !ill && (yy <= 1.79769313486231570e308) && V.np > 0;
@@ -2036,18 +2008,9 @@ struct LeanLane {
     }
 };
 
-#ifndef AMX_GCERT2_MAX
-#define AMX_GCERT2_MAX 11      // (12: 37 spilled registers in the first pass, LASSO group 3.44 ms; 11: none, 3.37 ms; 10: 3.48 ms)
-#endif
-constexpr int kGcert2Max = AMX_GCERT2_MAX;
-#ifndef AMX_GCERT2_WIDE
-#define AMX_GCERT2_WIDE 18
-#endif
-constexpr int kGcert2Wide = AMX_GCERT2_WIDE;   // second pass (k_lasso_gcert<.., true>)
-#ifndef AMX_GCERT2_WIDE3
-#define AMX_GCERT2_WIDE3 24
-#endif
-constexpr int kGcert2Wide3 = AMX_GCERT2_WIDE3; // third pass over what the second left: a RUN-TIME choice (amx_launch_noddi_gcert2: shapes whose left-over kernel reads its tile from L2).  Round 3, 99 volumes, 1 M voxels, fit ms:
+constexpr int kGcert2Max = 11;      // (12: 37 spilled registers in the first pass, LASSO group 3.44 ms; 11: none, 3.37 ms; 10: 3.48 ms)
+constexpr int kGcert2Wide = 18;   // second pass (k_lasso_gcert<.., true>)
+constexpr int kGcert2Wide3 = 24; // third pass over what the second left: a RUN-TIME choice (amx_launch_noddi_gcert2: shapes whose left-over kernel reads its tile from L2).  Round 3, 99 volumes, 1 M voxels, fit ms:
                                                // 12 / 16: 10.46; 12 / 18: 10.33 (121 spilled registers, but the left-over kernel sees 1.0 % instead of 2.3 %
                                                // of the voxels); 12 / 19: 10.35; 12 / 20: 10.42; 12 / 16 / 18: 10.34; 12 / 16 / 20: 10.42
 struct Gcert2Args {
@@ -2084,11 +2047,9 @@ struct Gcert2Args {
 // WIDE = false: every voxel of the chunk, supports of up to 11 atoms, two wavefronts per SIMD.  WIDE = true: second pass over the
 // left-over lists of the first for the supports of 12 .. 18 atoms (another 22 % of the voxels at the default lambdas), one
 // wavefront per SIMD -- the triangle lives in the whole register file (18: 121 spilled registers); what it cannot settle goes on to k_noddi<4>.
-#ifndef AMX_GCERT2_OCC
-#define AMX_GCERT2_OCC 2
-#endif
+constexpr int kGcert2Occ = 2;
 template <int MS, bool WIDE, int LOW = kGcert2Max>
-__global__ void __launch_bounds__(256, WIDE ? 1 : AMX_GCERT2_OCC) k_lasso_gcert(const Gcert2Args a)
+__global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(const Gcert2Args a)
 {
     constexpr int KD = kSeedKD, KS = KD / 4, MT = 9, LD = kSeedLd, RBW = 16;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_c2[];
@@ -2404,7 +2365,7 @@ struct Seed2Args {
     int *gcount;                  // [max_schunks + 1]: see SeedArgs
     int n_gcount;
     int *stats;
-    double *trace;                // SEED2_TRACE: per-trip records of the voxel at bucket position 0
+    double *trace;                // unused (a retired per-trip trace); kept so that the kernel argument layout stays as it is
     int trip_cap;                 // see SeedArgs
     int max_atoms;                // a voxel whose passive set reaches this many atoms and wants more is given up (its set goes on as an incomplete seed)
 };
@@ -2465,11 +2426,9 @@ __global__ void __launch_bounds__(1024) k_noddi_project2(const Seed2Args a)
     }
 }
 
-#ifndef AMX_SEED2_OCC
-#define AMX_SEED2_OCC 1
-#endif
+constexpr int kSeed2Occ = 1;
 template <bool OCC2 = false>
-__global__ void __launch_bounds__(256, OCC2 ? 2 : AMX_SEED2_OCC) k_lasso_seed(const Seed2Args a)
+__global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const Seed2Args a)
 {
     constexpr int KD = kSeed2KD, KS = KD / 4, MT = 9, KDP = KD + 1, NT = KD * (KD + 1) / 2, LD = KD + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_l[];
@@ -2512,7 +2471,7 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : AMX_SEED2_OCC) k_lasso_seed(co
     feed.reset();
     // (one wavefront per SIMD: y~ of the voxel in registers, the next voxel reserved -- and its y~ loading -- one solve ahead, as in
     //  k_nnls_seed<1>)
-    constexpr bool PREF2 = !OCC2 && AMX_SEED2_OCC == 1;       // (see k_nnls_seed: 1 M voxels 1.67 -> 1.28 ms at two wavefronts per SIMD)
+    constexpr bool PREF2 = !OCC2 && kSeed2Occ == 1;       // (see k_nnls_seed: 1 M voxels 1.67 -> 1.28 ms at two wavefronts per SIMD)
     double yv[KD], ynext[PREF2 ? KD : 1];
     int next_pos = -1;
     bool have_next = false;
@@ -2758,9 +2717,6 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : AMX_SEED2_OCC) k_lasso_seed(co
                 }
             }
         }
-#ifdef SEED2_TRACE
-        if (active && pos == 0 && a.trace) { double *tr = a.trace + 8 * trips; tr[0] = trips; tr[1] = jj; tr[2] = sigma; tr[3] = best; tr[4] = bj; tr[5] = dj; tr[6] = r[0]; tr[7] = g[0]; }
-#endif
         if (done) {
             unsigned long long *sd = a.seeds + (size_t)pos * 4;
             sd[0] = P[0]; sd[1] = P[1]; sd[2] = P[2]; sd[3] = noseed ? ~0ull : 0ull;

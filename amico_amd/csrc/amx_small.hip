@@ -257,12 +257,7 @@ __global__ void __launch_bounds__(256) k_freewater_lane(const FwArgs a)
         }
 #pragma unroll
         for (int j = 0; j < N; j++) c[j] -= a.c.lam1;
-#ifdef AMX_FW_SKIP_SOLVE
-#pragma unroll
-        for (int j = 0; j < N; j++) x[j] = c[j] > 0.0 ? 1e-3 * c[j] : 0.0;
-#else
         if (lane_nnqp<N>(Hs, c, x, n_atoms, amx_warm_start(a.c.lam2, a.c.flags)) != 0) atomicAdd(&a.c.status[ST_ITCAP], 1);
-#endif
         if (a.c.xdbg) {
 #pragma unroll
             for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
@@ -454,7 +449,7 @@ __device__ __forceinline__ int lane_nnqp_rows(TP A, int ldA, TP T, TP G, TP g0, 
         // block principal pivoting: passive atoms with a non-positive coefficient leave, inactive atoms with a positive dual
         // value enter, all at once while the number of infeasibilities keeps falling (then kBackup more times); otherwise only
         // the infeasible atom with the largest index is exchanged (Murty's rule).  (Launched with the warm start only: smaller
-        // lambda2 / AMX_COLD_START=1 go to k_sandi_lane's Lawson-Hanson loop, amx_launch_sandi_small.)
+        // lambda2 / flag bit 31 (cold start) go to k_sandi_lane's Lawson-Hanson loop, amx_launch_sandi_small.)
         unsigned v1 = 0u, v2 = 0u;
 #pragma unroll
         for (int i = 0; i < M; i++) w[i] = y[i] - w[i];
@@ -540,14 +535,12 @@ __global__ void __launch_bounds__(64) k_sandi_tables(const double *__restrict__ 
 }
 constexpr int kSandiTableWords = 15 * kRowsTs + 15 * 6 + 16 + 8 * 16;
 
-#ifndef AMX_ROWS_OCC
-#define AMX_ROWS_OCC 3
-#endif
+constexpr int kRowsOcc = 3;
 
 // SANDI, nS == M (<= 8) values per voxel: row-space solver; the dictionary and its tables come through the scalar cache
 // (wave-uniform addresses), y from the voxel's row.
 template <int M, int N>
-__global__ void __launch_bounds__(256, AMX_ROWS_OCC) k_sandi_rows(const SandiArgs a)
+__global__ void __launch_bounds__(256, kRowsOcc) k_sandi_rows(const SandiArgs a)
 {
     Chunk ck;
     const bool linear = a.n_lin > 0;           // SANDI has one dictionary: nothing to bucket, the voxels are taken in order
@@ -713,11 +706,9 @@ __global__ void __launch_bounds__(64) k_fw_orient_prep(const float *__restrict__
 // the full set is z0 = H^-1 c, and all the solver needs from it is which coefficients came out positive -- the passive set
 // after the first block removal, p0 [ldC] (11 bits per voxel).  H^-1 is tabulated per orientation; the explicit inverse
 // (cond(H) ~ 1e5 with the ridge) is good enough for a starting guess, the solver's answer does not depend on it.
-#ifndef AMX_FW_PROJ_OCC
-#define AMX_FW_PROJ_OCC 4
-#endif
+constexpr int kFwProjOcc = 4;
 template <int N>
-__global__ void __launch_bounds__(256, AMX_FW_PROJ_OCC) k_fw_project(const FwArgs a)
+__global__ void __launch_bounds__(256, kFwProjOcc) k_fw_project(const FwArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_p[];
     const int cid = xcd_chunk((int)blockIdx.x, *a.c.n_chunks);
@@ -962,10 +953,7 @@ __global__ void __launch_bounds__(256, 2) k_fw_project_mfma(const FwArgs a)
 // ticket and keeps TWO H tables in its LDS block -- lanes still iterating on voxels of the previous sub-chunk keep theirs
 // while the free lanes already take voxels of the next one, so lanes only idle at the very end of the launch (a
 // workgroup-per-chunk version lost a third of its lane-trips to the tail of every chunk).
-#ifndef AMX_FW_SUBCHUNK
-#define AMX_FW_SUBCHUNK 256      // (measured: 128 -> 534 us, 256 -> 527 us, 512 -> 540 us for the solver on 2 M voxels)
-#endif
-constexpr int kSubChunk = AMX_FW_SUBCHUNK;
+constexpr int kSubChunk = 256;      // (measured: 128 -> 534 us, 256 -> 527 us, 512 -> 540 us for the solver on 2 M voxels)
 
 template <int N>
 __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
@@ -1101,7 +1089,7 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
         // KKT point is reached in 2.9 solves per voxel from P0 (3.2 for block removals followed by Lawson-Hanson steps; the
         // longest voxel needs 7 instead of 14), and no coefficient vector has to survive from one trip to the next.
         // (The kernel is only launched with the warm start: for lambda2 < 1e-5, where H may be nearly singular, and for
-        // AMX_COLD_START=1 the fit goes to k_freewater_lane's Lawson-Hanson loop -- amx_fw_use_refill.)
+        // flag bit 31 (cold start) the fit goes to k_freewater_lane's Lawson-Hanson loop -- amx_fw_use_refill.)
         bool done = false;
         if (active && !(c[0] == c[0])) done = true;             // non-finite signal: NaN maps, never iterate
         const bool slv = active && !done;
@@ -1194,14 +1182,8 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
 // eight -- was measured first: 0.84 - 0.88 ms per 2 M voxels whatever the number of tiles in flight, against 0.735 for the kernel pair:
 // the producer shares its SIMD with a consumer, both live on the fp64 pipe, and 7 k cycles of matrix instructions per batch at half a
 // SIMD are ~6 us, while seven consumers want a batch every 3.7 us.)
-#ifndef AMX_FUSE_RING
-#define AMX_FUSE_RING 5
-#endif
-constexpr int kFuseRing = AMX_FUSE_RING;   // batches between producer and consumers
-#ifndef AMX_FUSE_AHEAD
-#define AMX_FUSE_AHEAD 2
-#endif
-constexpr int kFuseAhead = AMX_FUSE_AHEAD; // signal tiles in flight behind the one being multiplied (2 x 8 KB per workgroup, 32 KB per CU)
+constexpr int kFuseRing = 5;   // batches between producer and consumers
+constexpr int kFuseAhead = 2; // signal tiles in flight behind the one being multiplied (2 x 8 KB per workgroup, 32 KB per CU)
 constexpr int kFuseTiles = kFuseAhead + 1;
 constexpr int kFuseHs = 3;                 // H tables per consumer wavefront (lanes may still work on voxels of the last two orientations)
 constexpr int kFuseSub = 1024;             // voxels per unit of the global queue (one orientation: the operand registers are loaded per unit,
@@ -1247,10 +1229,7 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
     // follow in the same order), and a workgroup's wavefront w runs on SIMD w & 3: wavefront 0 in the first half, wavefront 2 in the
     // second, so that the two producers of a CU -- matrix instructions on the fp64 pipe, like the consumers' vector work -- sit on
     // DIFFERENT SIMDs next to one consumer each (both on wavefront 0: a SIMD without any pivoting, 0.589 ms per 2 M voxels)
-#ifndef AMX_FUSE_PW
-#define AMX_FUSE_PW 2
-#endif
-    const int pw = ((int)blockIdx.x >= ((int)gridDim.x >> 1)) ? AMX_FUSE_PW : 0;
+    const int pw = ((int)blockIdx.x >= ((int)gridDim.x >> 1)) ? 2 : 0;
     if (wave == pw) {
         // ================================================================ producer
         __builtin_amdgcn_s_setprio(3);
@@ -1640,11 +1619,11 @@ static int launch_refill(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s,
     int rc;
     // one kernel (k_freewater_fused) when the protocol fits its pipeline: four or more full tiles of 16 values per voxel, dictionary
     // operand in registers (AMX_FW_NO_FUSE=1: the projection + solver pair, for A/B)
-    if (a.c.nS >= 64 && a.c.nS <= 4 * kProjKS && !ctx->opt_fw_proj_valu && !ctx->opt_fw_no_fuse) {
+    if (a.c.nS >= 64 && a.c.nS <= 4 * kProjKS && !ctx->opt_fw_no_fuse) {
         FwKernel k = a.c.y32 != nullptr ? fused32 : fused;
         if ((rc = set_lds(ctx, k, fused_lds))) return rc;
         a.queue = pl.n_chunks + 60;                            // (misc word 60: zeroed with the plan counters)
-        a.sub_per_chunk = (amx_refill_chunk(ctx, (long long)pl.n) + kFuseSub - 1) / kFuseSub;
+        a.sub_per_chunk = (amx_refill_chunk((long long)pl.n) + kFuseSub - 1) / kFuseSub;
         rec(ctx, 2, s);
         hipLaunchKernelGGL(k, dim3(2 * ctx->n_cu), dim3(64 * (kFuseConsumers + 1)), fused_lds, s, a);
         amx_note(ctx, N == 11 ? "k_freewater_fused<11>" : "k_freewater_fused<12>");
@@ -1659,13 +1638,13 @@ static int launch_refill(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s,
     if ((rc = amx_ensure(ctx, ctx->cproj, cbytes + (size_t)a.ldC * sizeof(unsigned)))) return rc;
     a.cproj = (double *)ctx->cproj.p;
     a.p0 = (unsigned *)((char *)ctx->cproj.p + cbytes);
-    const bool mfma = a.c.nS <= 4 * kProjKS && !ctx->opt_fw_proj_valu;
+    const bool mfma = a.c.nS <= 4 * kProjKS;
     const size_t lds_p = mfma ? (size_t)4 * (2 * 64 * 16 + 32) * sizeof(double) : project_lds_bytes(a.c.nS, N, 4), lds = refill_lds_bytes(N, 4);
     if ((rc = set_lds(ctx, proj, lds_p)) || (rc = set_lds(ctx, pmfma, lds_p)) || (rc = set_lds(ctx, pmfma32, lds_p)) || (rc = set_lds(ctx, kern, lds))) return rc;
     if (a.c.y32 != nullptr && !mfma) { ctx->err = "float32 signals need the matrix-core projection (amx_fw_native_f32)"; return AMX_E_BADARG; }
     const dim3 grid(((pl.max_chunks + 7) / 8) * 8);
     a.queue = pl.n_chunks + 60;                            // (misc word 60: zeroed with the plan counters)
-    a.sub_per_chunk = (amx_refill_chunk(ctx, (long long)pl.n) + kSubChunk - 1) / kSubChunk;
+    a.sub_per_chunk = (amx_refill_chunk((long long)pl.n) + kSubChunk - 1) / kSubChunk;
     rec(ctx, 2, s);
     if (mfma && a.c.y32 != nullptr) hipLaunchKernelGGL(pmfma32, grid, dim3(256), lds_p, s, a);
     else if (mfma) hipLaunchKernelGGL(pmfma, grid, dim3(256), lds_p, s, a);

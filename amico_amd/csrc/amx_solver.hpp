@@ -227,14 +227,12 @@ __device__ __forceinline__ void tile_sweep(const AT *ap, int ldA, int nS, const 
 // the column in flight together; `cond ? (double)As[..] : 0` makes the compiler wait inside every guard (the raw columns of a 12-atom
 // seed: 96 L2 round trips one after the other per left-over voxel of a 288-volume protocol, 24 LDS round trips at 99 volumes).
 // Measured (profiles/r05b_tile_column_ab.txt): nothing at 288 volumes (those kernels wait elsewhere), 0.5 - 1 % of the 99-volume fit
-// with the LDS tiles built the same way (AMX_TILE_COL_LDS=0: the guarded form).
-#ifndef AMX_TILE_COL_LDS
-#define AMX_TILE_COL_LDS 1
-#endif
+// with the LDS tiles built the same way (kTileColLds = false: the guarded form).
+constexpr bool kTileColLds = true;
 template <int NR, typename AT>
 __device__ __forceinline__ void tile_column(const AT *As, int ldA, int nS, int t, int lane, const bool (&rowok)[NR], double (&col)[NR])
 {
-    if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+    if constexpr (is_global_tile<AT>::value || kTileColLds) {
         AT raw[NR] = {};
 #pragma unroll
         for (int rr = 0; rr < NR; rr++) {
@@ -641,7 +639,7 @@ struct NNSolver {
                     for (int u = 0; u < 4; u++) {
                         p[u] = 0.0;
                         const int t = t4[u] < 0 ? t4[0] : t4[u];
-                        if constexpr (is_global_tile<AT>::value || AMX_TILE_COL_LDS != 0) {
+                        if constexpr (is_global_tile<AT>::value || kTileColLds) {
                             double col[NR];
                             tile_column<NR, AT>(As, ldA, nS, t, lane, rowok, col);
 #pragma unroll
@@ -729,7 +727,6 @@ struct NNSolver {
         if (!RIDGE && G != nullptr && seed != kSeedNone && lam1 == 0.0) {
             seeded = certify_seed(As, ldA, nS, yr, rowok, fl, seed, rs, lane, G, ldG, scr) ? 1 : 0;
             if (seeded == 1) return kSolved;
-#ifndef AMX_NO_WARM_ORDER
             // A refused seed is still the best guess at the support (it is wrong in an atom or two, or its Gram block was too
             // ill-conditioned for the semi-normal equations): its atoms get to ENTER FIRST.  Lawson-Hanson may admit any atom
             // whose dual value is positive -- the arg-max is a heuristic, the descent proof only needs w_t > 0 -- so this is
@@ -744,20 +741,13 @@ struct NNSolver {
                 }
                 prefer = true;
             }
-#endif
         }
 #ifdef AMX_PHASES
         if (seeded != 1) { for (int k = 0; k < 8; k++) ph[k] = 0; }
         pht = (long long)__builtin_readcyclecounter();
 #endif
-#ifndef AMX_GRAM_COLS
-#define AMX_GRAM_COLS 4
-#endif
-        constexpr int kGramCols = AMX_GRAM_COLS;   // Gram columns in flight per trip of the dual-vector update
-#ifndef AMX_GRAM_STEPS
-#define AMX_GRAM_STEPS 48
-#endif
-        constexpr int kMaxGramSteps = AMX_GRAM_STEPS;    // bound the drift of the Gram-updated dual vector
+        constexpr int kGramCols = 4;   // Gram columns in flight per trip of the dual-vector update
+        constexpr int kMaxGramSteps = 48;    // bound the drift of the Gram-updated dual vector
         const double kExactBelow = 1e-7;     // decisions on smaller dual values use the exact sweep
         double u[NQ];                        // atom space: A' r (unscaled, without the l1 shift)
         bool have_u = false, force_exact = false;
@@ -866,9 +856,7 @@ struct NNSolver {
                 if (!exact) {
                     // every admissible dual value is negative by far more than the Gram updates can have drifted:
                     // the exact sweep would confirm the KKT point and change nothing
-#ifndef AMX_ALWAYS_CONFIRM
                     if (uni(wmax < -kExactBelow)) break;
-#endif
                     if (uni(!(wmax > kExactBelow))) { force_exact = true; redo = true; break; }
                 }
                 if (!uni(wmax > tol)) break;                      // KKT point reached
@@ -902,10 +890,7 @@ struct NNSolver {
                 double rho = 0.0;                 // lane k: R[k][new]
                 // two Gram-Schmidt passes, 4 projections in flight at a time
 #pragma unroll
-#ifndef AMX_CGS_PASSES
-#define AMX_CGS_PASSES 2
-#endif
-                for (int pass = 0; pass < AMX_CGS_PASSES; pass++) {
+                for (int pass = 0; pass < 2; pass++) {
 #pragma unroll
                     for (int kb = 0; kb < MAXP; kb += 4) {
                         if (kb < np) {

@@ -84,7 +84,7 @@ static int count_phys(const cpu_set_t &cpus)
     return n;
 }
 // which of the devices that hang on `node` is `device` (by device number), and how many there are: the siblings of its pool
-static void device_siblings(int device, int node, int *idx, int *count)
+static void device_siblings(int device, int node, int local_rank, int local_world, int *idx, int *count)
 {
     *idx = 0; *count = 1;
     int nd = 0;
@@ -97,13 +97,12 @@ static void device_siblings(int device, int node, int *idx, int *count)
     }
     if (n > 1) { *idx = i; *count = n; return; }
     // one visible device per process (HIP_VISIBLE_DEVICES set by the launcher): the launcher's local rank / size say who else is there
-    const char *lr = getenv("LOCAL_RANK"), *lw = getenv("LOCAL_WORLD_SIZE");
-    if (lr && lw && atoi(lw) > 1) {
+    if (local_rank >= 0 && local_world > 1) {
         int nodes = 0;
         cpu_set_t cs;
         for (int k = 0; k < 16; k++) if (node_cpus(k, &cs)) nodes++;
-        const int per = (atoi(lw) + (nodes > 0 ? nodes : 1) - 1) / (nodes > 0 ? nodes : 1);
-        *count = per > 1 ? per : 1; *idx = atoi(lr) % *count;
+        const int per = (local_world + (nodes > 0 ? nodes : 1) - 1) / (nodes > 0 ? nodes : 1);
+        *count = per > 1 ? per : 1; *idx = local_rank % *count;
     }
 }
 
@@ -155,7 +154,7 @@ public:
         if (share < 2 * t) t = share / 2;
         return t < 4 ? (share >= 4 ? 4 : (share > 0 ? share : 1)) : t;
     }
-    static Pool *create(int threads, int node = -1, int sib_i = 0, int sib_n = 1)
+    static Pool *create(int threads, int node = -1, int sib_i = 0, int sib_n = 1, char pin_cores = 0)
     {
         if (node >= 0 && sib_n > 1) {
             cpu_set_t c0;
@@ -179,8 +178,8 @@ public:
         try {
             for (int t = 0; t < threads; t++) p->th_.emplace_back([p] { p->worker(); });
         } catch (...) { delete p; return nullptr; }
-        // Every thread gets its own STRIPE of the node's physical cores (P / T of them; AMX_HOST_PIN_CORES=0: all threads share the node's
-        // CPUs as one set, 1: one core per thread -- diagnosis).  Threads that wake together start on the waker's cache domain and are
+        // Every thread gets its own STRIPE of the node's physical cores (P / T of them; pin_cores (AMX_HOST_PIN_CORES) '0': all threads share the node's
+        // CPUs as one set, '1': one core per thread -- diagnosis).  Threads that wake together start on the waker's cache domain and are
         // spread by the load balancer over MILLISECONDS: with the node as one set the first batches of a call were narrowed at a third of
         // the rate of the later ones.  One core per thread cures that and has a failure of its own: a thread nailed to the core the CALLING
         // thread happens to run on shares it with that thread's copies -- 28 ms per call instead of 12.6, one process in five.  Within a
@@ -196,7 +195,6 @@ public:
                 if (FILE *f = fopen(path, "r")) { if (fscanf(f, "%d", &first) != 1) first = k; fclose(f); }
                 if (first == k || !CPU_ISSET(first, &cpus)) phys.push_back(k);
             }
-            const char *pc = getenv("AMX_HOST_PIN_CORES");
             if (sib_n > 1 && (int)phys.size() >= sib_n) {
                 // this pool's share of the node: cores [sib_i * share, (sib_i + 1) * share) in the node's order
                 const int share = (int)phys.size() / sib_n;
@@ -204,11 +202,11 @@ public:
             }
             const int P = (int)phys.size();
             p->share_first_ = P > 0 ? phys.front() : -1; p->share_cores_ = P;
-            if ((!pc || pc[0] != '0') && P >= 2 * threads) {
+            if (pin_cores != '0' && P >= 2 * threads) {
                 // (a pool alone on its node rotates its stripes with the process id -- processes that do not know of each other; a
                 //  sibling's share is its own: no rotation)
                 const int stride = P / threads, start = sib_n > 1 ? 0 : (int)(((unsigned)getpid() * 7u) % (unsigned)P);
-                const int width = (pc && pc[0] == '1') ? 1 : stride;
+                const int width = pin_cores == '1' ? 1 : stride;
                 for (int t = 0; t < threads; t++) {
                     cpu_set_t mine;
                     CPU_ZERO(&mine);

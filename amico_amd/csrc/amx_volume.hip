@@ -574,7 +574,7 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     a.n_gidx = p->n_gidx;
     if (dti != nullptr) { a.wt = dti->wt; a.min_signal = dti->min_signal; a.dirs = d_dirs; }
     const bool identity = p->identity != 0;
-    a.direct = (identity && p->layout != 2 && !ctx->opt_prep_no_direct) ? 1 : 0;
+    a.direct = (identity && p->layout != 2) ? 1 : 0;
     const size_t per_wave = identity ? (a.direct ? (size_t)a.nS * kDirectLd : (size_t)64 * a.ldt) : (size_t)64 * a.ldt * (a.inplace ? 1 : 2);
     const size_t lds = ((size_t)kPrepWaves * per_wave + (size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(float);
     if (lds > 160 * 1024) return amx_bad(ctx, "amx_prep_gather: scheme too long for the LDS tile");
@@ -596,7 +596,7 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     // be in flight together (two streams, double-buffered images sharing a mask) without sharing or resetting each other's ticket
     int *const my_counter = p->tile_counter + (p->launch_seq++ % amx_prep::kCounterRing);
     a.live = p->live64; a.n_live = p->n_live64; a.counter = my_counter;
-    if (!identity && !p->hazard && p->layout == 1 && !ctx->opt_prep_tile) {
+    if (!identity && !p->hazard && p->layout == 1) {
         // grouped outputs on a planar image: streaming kernel, no transposition tile
         const size_t lds_s = ((size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(int);
         long long g2 = (a.n_tiles + 3) / 4;
@@ -1007,7 +1007,7 @@ static int lut_gemm(amx_ctx *ctx, const float *d_lm, const float *d_z, const flo
     // both operands in LDS: plain input, even K, operator zone + four row tiles within the 160 KB of a CU
     const size_t yzone = ((((size_t)n_out * n_sh * 4) + 1023) & ~(size_t)1023) + 2048;
     const size_t lds_tile = yzone + 4 * ((((size_t)32 * n_sh * 4) + 1023) & ~(size_t)1023);
-    if (d_lm && (n_sh & 1) == 0 && n_sh <= 4 * amx::kLutKhMax && 4 * kh2t - n_sh <= 4 && lds_tile <= 160 * 1024 && !ctx->opt_lut_regs) {
+    if (d_lm && (n_sh & 1) == 0 && n_sh <= 4 * amx::kLutKhMax && 4 * kh2t - n_sh <= 4 && lds_tile <= 160 * 1024) {
         auto launch = [&](auto kern) -> int {
             HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile));
             long long blocks = (n_rows + 127) / 128;

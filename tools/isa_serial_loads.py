@@ -7,7 +7,7 @@ per block of 64 voxels in the seed solver's take, the LASSO certificates' Gram g
 loop).  This lists, per kernel of a device assembly file, the vector loads and how many of them are followed by a full wait before
 the next load is issued.
 
-    cd amico_amd/csrc && /opt/rocm/bin/hipcc -DAMX_S2_NW=16 -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o /tmp/seed.s amx_seed.hip
+    cd amico_amd/csrc && /opt/rocm/bin/hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -S -o /tmp/seed.s amx_seed.hip
     python tools/isa_serial_loads.py /tmp/seed.s
 
 The cure is one of: unconditional loads at clamped indices with the guard on the STORE / select (staging loops); loads under their
