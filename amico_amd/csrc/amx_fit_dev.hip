@@ -1,0 +1,373 @@
+// amx_fit_dev.hip -- the four model fits on device pointers.  One checked, prepared call (fit_check, fit_open, fit_args, fit_close) around
+// what is a model's own: NODDI's chain of three stages, FreeWater's refill decision, SANDI's row-space branch, CylinderZeppelinBall's fast route.
+#include "amx_host.hpp"
+
+using namespace amx;
+
+// (CylinderZeppelinBall: the Gram-space solver needs a ridge -- models.pyx:439 default: 4.0; lambda2 < 1e-6 runs the thin-QR solver in A-space)
+const FitSpec kFits[4] = {{1, "amx_noddi_fit", "NODDI", true, 3, AMX_F_MODULATED, 2, 3}, {2, "amx_freewater_fit", "FreeWater", true, 2, AMX_F_CORRECTED, 0, 1},
+                          {3, "amx_sandi_fit", "SANDI", false, 6, 0, 1, 1}, {4, "amx_czb_fit", "CylinderZeppelinBall", true, 3, 0, 1, 1}};
+
+namespace {
+
+// ------------------------------------------------------------------ the prologue and epilogue every fit shares
+// The checks, in the order they have always run; then the context learns where this fit stands in its call (amx_note, progress_tick,
+// enqueue_bucketing and every size-dependent path choice read it from there).  A call of no voxels passes: amx_fit_dev returns AMX_OK.
+int fit_check(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+{
+    if (ctx && c.batch.first()) ctx->path.clear();
+    if (!ctx) return AMX_E_BADARG;
+    if (!c.lut || c.lut->model != m.model || c.lut->ctx != ctx) return fit_bad(ctx, m, ": not a ", " dictionary of this ctx");
+    if (c.n < 0 || c.n > INT_MAX / 4) return fit_bad(ctx, m, ": bad n_vox");
+    if (c.n == 0) return AMX_OK;
+    if ((!c.y && !c.y32) || (m.dirs && !c.dirs) || !c.est) return fit_bad(ctx, m, ": null buffer");
+    if (((c.flags & AMX_F_RMSE) && !c.rmse) || ((c.flags & AMX_F_NRMSE) && !c.nrmse) || ((c.flags & m.extra_flag) && !c.extra)) return fit_bad(ctx, m, ": flag set but output buffer is null");
+    if (!(c.lam2 >= 0.0) || !(c.lam1 >= 0.0)) return fit_bad(ctx, m, ": need lambda1 >= 0 and lambda2 >= 0");
+    if (c.is_mouse && c.lut->n_iso < 2) return amx_bad(ctx, "amx_freewater_fit: Mouse needs two isotropic atoms");   // (is_mouse: FreeWater only)
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    ctx->batch = c.batch;
+    ctx->call_vox = c.batch.call_vox > 0 ? c.batch.call_vox : c.n;
+    return AMX_OK;
+}
+
+// the call's first event, and the voxels bucketed by orientation (a voxel whose direction is out of bounds is skipped by every kernel:
+// k_dir_to_lut gives it defined (zero) maps, so no fit clears its maps first -- test_*_fit_writes_every_voxel)
+int fit_open(amx_ctx *ctx, const FitSpec &m, const FitCall &c, Plan &pl, int chunk = kChunk)
+{
+    clear_events(ctx);
+    rec(ctx, 0, c.stream);
+    return m.dirs ? enqueue_bucketing(ctx, c.lut, c.dirs, c.n, pl, c.stream, chunk, c.est, fit_maps(m, c)) : AMX_OK;
+}
+
+// what every model's kernel arguments have in common; the outputs are gated by their flags
+template <typename Args>
+int fit_args(amx_ctx *ctx, const FitSpec &m, const FitCall &c, const Plan &pl, Args &a, double *Args::*extra = nullptr)
+{
+    const amx_lut *lut = c.lut;
+    memset(&a, 0, sizeof a);
+    fill_common(a.c, lut->tiles, c.y, c.y32, pl, ctx->status_d, lut->nS, lut->ldA, lut->n_atoms, lut->tile_stride, c.lam1, c.lam2, c.flags);
+    if (c.flags & AMX_F_DEBUG_X) {
+        if (!ctx->dbg_x) return fit_bad(ctx, m, ": AMX_F_DEBUG_X without a buffer (amx_set_debug_x)");
+        a.c.xdbg = ctx->dbg_x + (size_t)c.batch.base * m.x_per_atom * lut->n_atoms;
+    }
+    a.est = c.est; a.rmse = (c.flags & AMX_F_RMSE) ? c.rmse : nullptr; a.nrmse = (c.flags & AMX_F_NRMSE) ? c.nrmse : nullptr;
+    if (extra) a.*extra = (c.flags & m.extra_flag) ? c.extra : nullptr;
+    return AMX_OK;
+}
+
+// (fold: the kernels counted into the per-call counters.  A failed launch still ends the call's event pair: rc is what the solver launch gave)
+int fit_close(amx_ctx *ctx, const FitCall &c, int rc, bool fold = true)
+{
+    if (fold) fold_counters(ctx, c.stream);
+    rec(ctx, 1, c.stream);
+    if (!rc) progress_tick(ctx, c.stream, c.n, c.n);
+    return rc;
+}
+
+// ------------------------------------------------------------------ NODDI
+// What the three stages share.  Every stage is: [seed solver -> Gram certificate ->] the stage's wavefront-per-voxel kernel, which works
+// on all voxels of the first plan (walk_all) or, behind a certificate, on the lists that certificate left over (walk_leftovers).
+struct NoddiChain {
+    amx_ctx *ctx; const amx_lut *lut; int64_t n; hipStream_t s;
+    Plan pl; NoddiArgs a;
+    bool seeds = false;            // the seed -> certificate chain runs (a dictionary with a basis, a call of at least AMX_SEED_MIN_VOXELS)
+    int gemm_ks = 0;               // 0: no table kernels for this shape (seeds certified on the true residual only)
+    // AMX_FORK (a recorded negative result, kSwitches): the side stream and its events, what went there
+    hipStream_t fs = nullptr; hipEvent_t *fev = nullptr;
+    bool fork1 = false, joined1 = false, fork2 = false;
+    int late_rc = AMX_OK;          // of the LASSO stage's own launch: the epilogue still runs behind it, as it always has
+};
+
+// the stage kernel walks the left-over lists of the second plan
+void walk_leftovers(NoddiChain &q, const int *list, const int *counts, const unsigned char *done)
+{
+    q.a.done = done; q.a.rlist = list; q.a.rcount = counts;
+    q.a.c.chunks = q.pl.schunks; q.a.c.n_chunks = q.pl.n_chunks + 1;
+}
+
+// ... back to all voxels of the first plan
+void walk_all(NoddiChain &q)
+{
+    q.a.c.chunks = q.pl.chunks; q.a.c.n_chunks = q.pl.n_chunks;
+    q.a.rlist = nullptr; q.a.rcount = nullptr; q.a.done = nullptr;
+}
+
+// side stream + events of a forked fit, one set per workspace set (fit_host alternates two: swap_work)
+int fork_ready(NoddiChain &q)
+{
+    amx_ctx *ctx = q.ctx; const int w = ctx->work_idx;
+    if (!ctx->fork_s[w]) {
+        HIPCHK(ctx, hipStreamCreateWithPriority(&ctx->fork_s[w], hipStreamNonBlocking, 0));
+        for (int k = 0; k < 4; k++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->fork_ev[w][k], hipEventDisableTiming));
+    }
+    q.fs = ctx->fork_s[w];
+    return AMX_OK;
+}
+
+// what `launch` enqueues runs on the side stream, behind everything the main stream holds so far: events ev (fork) and ev + 1 (done)
+template <typename Launch>
+int fork_side(NoddiChain &q, int ev, Launch launch)
+{
+    amx_ctx *ctx = q.ctx;
+    HIPCHK(ctx, hipEventRecord(q.fev[ev], q.s));
+    HIPCHK(ctx, hipStreamWaitEvent(q.fs, q.fev[ev], 0));
+    ctx->side_launch = true;
+    const int rc = launch(q.fs);
+    ctx->side_launch = false;
+    if (rc) return rc;
+    HIPCHK(ctx, hipEventRecord(q.fev[ev + 1], q.fs));
+    return AMX_OK;
+}
+
+int fork_join(NoddiChain &q, int ev)
+{
+    HIPCHK(q.ctx, hipStreamWaitEvent(q.s, q.fev[ev + 1], 0));
+    return AMX_OK;
+}
+
+// NNLS on all atoms: x_iso (and x_dot)
+int noddi_stage1(NoddiChain &q)
+{
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; int rc;
+    if (q.seeds) {
+        ctx->seeded_vox += q.n;
+        // y~ = U'y once; the seed solver proposes the stage's support, the stage kernel certifies it (amx_seed.hpp)
+        rec(ctx, 10, s);
+        const bool gcert = !ctx->opt_no_gcert && q.gemm_ks > 0;
+        if (gcert && (rc = amx_launch_noddi_gemm(ctx, lut, a, pl, s, false))) return rc;
+        if (!gcert && (rc = amx_launch_noddi_project(ctx, lut, a, pl, s))) return rc;      // (the GEMM writes y~ as well)
+        if (!ctx->opt_no_screen) { a.scr_S = lut->screen_S; a.scr_kappa = lut->screen_kappa; a.scr_ytil = (const double *)ctx->ytil.p; a.scr_Sg = lut->basis_S; }
+        if (ctx->opt_seed_stages & 1) {
+            a.seeds = (const unsigned long long *)ctx->seeds.p;
+            rec(ctx, 16, s);
+            if ((rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, 1))) return rc;
+            rec(ctx, 17, s);
+            if (!gcert) ctx->uncert_vox[0] += q.n;
+            if (gcert) {
+                size_t off = 0; const int *cnt = nullptr;
+                if ((rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, 1, &off, &cnt))) return rc;
+                walk_leftovers(q, (const int *)ctx->rlist.p + off, cnt, ctx->opt_no_hard_first ? nullptr : (const unsigned char *)ctx->done.p);
+            }
+        }
+        rec(ctx, 11, s);
+    }
+    // AMX_FORK bit 0 (TIMING PROBE, not a fit): the stage-1 left-over kernel on the side stream beside the LASSO seed solver, which reads
+    // the x_iso the previous call left for those voxels; joined before the LASSO certificates
+    q.fork1 = (ctx->opt_fork & 1) && a.rlist != nullptr;
+    if (ctx->opt_fork && (rc = fork_ready(q))) return rc;
+    q.fev = ctx->fork_ev[ctx->work_idx];
+    if (q.fork1) rc = fork_side(q, 0, [&](hipStream_t side) { return amx_launch_noddi_s1(ctx, a, pl, side); });
+    else rc = amx_launch_noddi_s1(ctx, a, pl, s);
+    if (rc) return rc;
+    progress_tick(ctx, s, q.n / 3, q.n);                       // (three stages: a third of the work each, roughly)
+    walk_all(q);
+    return AMX_OK;
+}
+
+// LASSO on the white-matter atoms: the support
+int noddi_stage2(NoddiChain &q)
+{
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s;
+    const double lambda1 = a.c.lam1, lambda2 = a.c.lam2; int rc;
+    // the LASSO seeds need x_iso: Gram-space solver only (lambda2 >= 1e-5), with the default dictionary shape
+    if (q.seeds && (ctx->opt_seed_stages & 4) && lut->basis2_S != nullptr && lambda2 >= 1e-5 && (q.gemm_ks > 0 || lut->nS <= 128) &&
+        (lambda1 > 0.0 || ctx->opt_no_big_all || lut->n_wm <= 64)) {       // (lambda1 = 0: a dense optimum -- no seeds to propose, amx_launch_noddi_s2 goes to k_noddi_lasso_big)
+        const bool gcert2 = !ctx->opt_no_gcert && q.gemm_ks > 0 && lut->screen2_kappa0 != nullptr && lut->u2iso != nullptr;
+        rec(ctx, 12, s);
+        // y2~ of every voxel and c2 = A2'y2, ||y2||^2 of the unclipped ones derive from the stage-1 table; the clipped voxels' exactly
+        if (gcert2 && (rc = amx_launch_noddi_s2prep(ctx, lut, a, pl, s))) return rc;
+        rec(ctx, 18, s);
+        if ((rc = amx_launch_noddi_seed2(ctx, lut, a, pl, s, gcert2))) return rc;
+        rec(ctx, 19, s);
+        a.seeds2 = (const unsigned long long *)ctx->seeds2.p;
+        a.list_is_pos = 1;
+        if (!ctx->opt_no_screen && lut->screen2_S) { a.scr2_S = lut->screen2_S; a.scr2_kappa = lut->screen2_kappa; a.scr2_ytil = (const double *)ctx->ytil2.p; a.scr2_Sg = lut->basis2_S; }
+        if (!gcert2) ctx->uncert_vox[1] += q.n;
+        if (q.fork1) { if ((rc = fork_join(q, 0))) return rc; q.joined1 = true; }
+        if (gcert2) {
+            const bool wide = !ctx->opt_no_gcert_wide;
+            if ((rc = amx_launch_noddi_gcert2(ctx, lut, a, pl, s, wide))) return rc;
+            a.cand_lists = 1;       // (k_lasso_gcert: the candidate lists of stage 3 wait in seeds2 for the voxels it settled)
+            const bool third = amx_gcert2_third(ctx, lut, wide);
+            walk_leftovers(q, (const int *)ctx->rlist.p + amx_gcert2_leftover_offset(pl, wide, third), amx_gcert2_leftover_counts(pl, wide, third), nullptr);   // (two wide passes end in the first half again)
+            // AMX_FORK bit 1: the voxels these certificates left over (0.6 %) do not come back to the lane kernels -- k_noddi<4> and then
+            // k_noddi<3> (no seed: Lawson-Hanson on the support it has just found, plus iso) finish them, a wavefront per voxel, on the side
+            // stream, while k_nnls_seed<3> / k_nnls_gcert<3> work on everybody else (they skip the voxels whose certificate flag is not 1)
+            q.fork2 = (ctx->opt_fork & 2) && (ctx->opt_seed_stages & 2) && !ctx->opt_no_gcert && q.gemm_ks > 0;
+        }
+        rec(ctx, 13, s);
+    }
+    if (q.fork1 && !q.joined1 && (rc = fork_join(q, 0))) return rc;
+    if (!q.fork2) { q.late_rc = amx_launch_noddi_s2(ctx, a, pl, s); return AMX_OK; }
+    rc = fork_side(q, 2, [&](hipStream_t side) {
+        NoddiArgs b = a;
+        int r = amx_launch_noddi_s2(ctx, b, pl, side);
+        if (r) return r;
+        b = a;      // (same left-over lists, same chunks: now stage 3 without seeds)
+        b.seeds = nullptr; b.done = nullptr; b.seeds2 = nullptr; b.cand_lists = 0;
+        return amx_launch_noddi_s3(ctx, b, pl, side);
+    });
+    if (!rc) a.fork_l2 = 1;
+    return rc;
+}
+
+// NNLS on the support + iso: the maps
+int noddi_stage3(NoddiChain &q)
+{
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; int rc = AMX_OK;
+    progress_tick(ctx, s, 2 * (q.n / 3), q.n);
+    a.seeds = nullptr;
+    walk_all(q);
+    if (q.seeds && (ctx->opt_seed_stages & 2)) {
+        a.seeds = (const unsigned long long *)ctx->seeds.p;
+        rec(ctx, 14, s);
+        rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, 3);
+        const bool gcert3 = !ctx->opt_no_gcert && q.gemm_ks > 0;
+        if (!gcert3) ctx->uncert_vox[2] += q.n;
+        if (!rc && gcert3) {
+            size_t off = 0; const int *cnt = nullptr;
+            rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, 3, &off, &cnt);
+            walk_leftovers(q, (const int *)ctx->rlist.p + off, cnt, ctx->opt_no_hard_first ? nullptr : (const unsigned char *)ctx->done.p);
+        }
+        rec(ctx, 15, s);
+    }
+    return rc ? rc : amx_launch_noddi_s3(ctx, a, pl, s);
+}
+
+int noddi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+{
+    const amx_lut *lut = c.lut; int rc;
+    NoddiChain q{ctx, lut, c.n, c.stream};
+    q.seeds = lut->basis_S != nullptr && lut->gram != nullptr && !ctx->opt_no_seed && ctx->call_vox >= ctx->opt_seed_min_voxels;
+    q.gemm_ks = q.seeds ? amx_gemm_ksteps(lut) : 0;
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, q.pl, q.seeds, gemm_rows(lut->n_atoms)))) return rc;
+    if ((rc = amx_ensure(ctx, ctx->xiso, (size_t)c.n * 2 * sizeof(double)))) return rc;
+    if ((rc = amx_ensure(ctx, ctx->supp, (size_t)c.n * 4 * sizeof(unsigned long long)))) return rc;
+    // (every voxel's maps are written by the kernel that settles its stage 3 -- tests/test_gpu_parity.py::test_noddi_fit_writes_every_voxel)
+    if ((rc = fit_open(ctx, m, c, q.pl)) || (rc = fit_args(ctx, m, c, q.pl, q.a, &NoddiArgs::mod))) return rc;
+    NoddiArgs &a = q.a;
+    a.rowdwi = lut->rowdwi; a.colscale = lut->colscale; a.icvf = lut->icvf; a.kappa = lut->kappa;
+    a.n_wm = lut->n_wm; a.is_exvivo = lut->is_exvivo; a.n_maps = fit_maps(m, c);
+    a.gram = lut->gram; a.gram_dwi = lut->gram_dwi; a.ldG = lut->ldG;
+    a.xiso = (double *)ctx->xiso.p; a.supp = (unsigned long long *)ctx->supp.p;
+    if ((rc = noddi_stage1(q)) || (rc = noddi_stage2(q))) return rc;      // (a failure up to the LASSO certificates leaves the call at once)
+    // the launch of the LASSO stage's own kernels on the main stream reports through late_rc: behind it the counters still fold and the call's
+    // event pair still ends (fit_close), so a profiled or polled call sees a finished call and the error, as it always has
+    rc = q.late_rc ? q.late_rc : noddi_stage3(q);
+    if (q.fork2) { const int rj = fork_join(q, 2); if (rj) return rj; }      // the side stream's voxels are part of this fit
+    return fit_close(ctx, c, rc);
+}
+
+// ------------------------------------------------------------------ FreeWater
+int freewater_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+{
+    const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl))) return rc;
+    const bool refill = amx_use_lane_solver(ctx, lut->n_atoms, c.lam2) && amx_fw_use_refill(ctx, lut->n_atoms, lut->nS, c.flags, c.lam2);
+    FwArgs a;
+    if ((rc = fit_open(ctx, m, c, pl, refill ? amx_refill_chunk(c.n) : kChunk)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
+    a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = c.is_mouse; a.n_maps = fit_maps(m, c);
+    if (refill && (rc = amx_fw_prepare(ctx, lut, a, s))) return rc;
+    return fit_close(ctx, c, amx_launch_fw(ctx, a, pl, s));
+}
+
+// ------------------------------------------------------------------ SANDI
+int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+{
+    const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
+    if ((rc = make_plan(ctx, c.n, 1, pl))) return rc;
+    SandiArgs a;
+    if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;      // (one dictionary: no bucketing)
+    a.norms = lut->norms; a.Rs = lut->Rs; a.d_in = lut->d_in; a.d_isos = lut->d_isos;
+    a.n_rs = lut->n_rs; a.n_in = lut->n_in; a.n_iso = lut->n_isos;
+    if ((rc = amx_sandi_prepare(ctx, lut, a, s))) return rc;
+    // the row-space kernel (default protocol) takes the voxels in order and counts straight into the status words: one launch
+    // per fit; the other SANDI kernels walk the (trivial) plan and use the per-call counters
+    const bool rows = a.tables && amx_use_lane_solver(ctx, a.c.n_atoms, a.c.lam2) && !ctx->opt_sandi_atom_space;
+    if (rows) a.n_lin = (int)c.n;
+    else if ((rc = enqueue_linear_plan(ctx, c.n, pl, s))) return rc;
+    return fit_close(ctx, c, amx_launch_sandi(ctx, a, pl, s), !rows);
+}
+
+// ------------------------------------------------------------------ CylinderZeppelinBall
+int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+{
+    const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
+    // the default problem (strong ridge, <= 32 atoms, maps only): complementary form, one voxel per lane (amx_czb.hip)
+    const bool fast = lut->n_atoms <= 32 && c.lam2 >= 1e-2 && !(c.flags & (AMX_F_RMSE | AMX_F_NRMSE)) &&
+                      !ctx->opt_wave_per_voxel && lut->nS <= 160 && lut->gram != nullptr;
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl, false, 64, fast ? 2048 : 0))) return rc;
+    CzbArgs a;
+    if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;
+    a.n_rs = lut->n_rs; a.n_perp = lut->n_perp; a.Rs = lut->Rs; a.gram = lut->gram; a.ldG = lut->ldG;
+    if (fast) { if (!(rc = amx_czb_prepare(ctx, lut, c.lam2, s))) rc = amx_launch_czb_fast(ctx, lut, a, pl, s); }
+    else rc = amx_launch_czb(ctx, a, pl, s);
+    return fit_close(ctx, c, rc);
+}
+
+}  // namespace
+
+// float32 signals in HBM (the image's dtype, core.py:136; lossless) are read in place by the NODDI kernels, by every wavefront-per-voxel
+// kernel and by FreeWater's matrix-core projection; the other lane kernels get a float64 copy made on the device first.
+int amx_fit_dev(amx_ctx *ctx, const FitSpec &m, FitCall c)
+{
+    int rc;
+    const bool f32 = ctx && c.lut && c.lut->model == m.model && c.y32 && c.n > 0;      // (else: fit_check says what is wrong)
+    if (f32 && ((m.model == 2 && !amx_fw_native_f32(ctx, c.lut->n_atoms, c.lut->nS, c.flags, c.lam2)) ||
+                (m.model == 3 && amx_use_lane_solver(ctx, c.lut->n_atoms, c.lam2)))) {
+        const size_t nel = (size_t)c.n * c.lut->nS;
+        HIPCHK(ctx, hipSetDevice(ctx->device));
+        if ((rc = amx_ensure(ctx, ctx->wy, nel * sizeof(double)))) return rc;
+        widen_on_device(c.y32, (double *)ctx->wy.p, nel, c.stream);
+        HIPCHK(ctx, hipGetLastError());
+        c.y = (const double *)ctx->wy.p; c.y32 = nullptr;
+    }
+    if ((rc = fit_check(ctx, m, c)) || c.n == 0) return rc;
+    switch (m.model) {
+    case 1: return noddi_fit_dev(ctx, m, c);
+    case 2: return freewater_fit_dev(ctx, m, c);
+    case 3: return sandi_fit_dev(ctx, m, c);
+    default: return czb_fit_dev(ctx, m, c);
+    }
+}
+
+// ------------------------------------------------------------------ the C entry points: float64 signals, or the float32 the image holds
+extern "C" {
+
+int amx_noddi_fit_device(amx_ctx *ctx, const amx_lut *lut, const double *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, double *d_mod, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[0], {lut, d_y, nullptr, d_dirs, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, d_mod, (hipStream_t)hip_stream, {}});
+}
+int amx_noddi_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, double *d_mod, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[0], {lut, nullptr, d_y, d_dirs, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, d_mod, (hipStream_t)hip_stream, {}});
+}
+
+int amx_freewater_fit_device(amx_ctx *ctx, const amx_lut *lut, const double *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, int is_mouse, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, double *d_ycorr, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[1], {lut, d_y, nullptr, d_dirs, n_vox, lambda1, lambda2, is_mouse, flags, d_estimates, d_rmse, d_nrmse, d_ycorr, (hipStream_t)hip_stream, {}});
+}
+int amx_freewater_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, int is_mouse, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, double *d_ycorr, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[1], {lut, nullptr, d_y, d_dirs, n_vox, lambda1, lambda2, is_mouse, flags, d_estimates, d_rmse, d_nrmse, d_ycorr, (hipStream_t)hip_stream, {}});
+}
+
+int amx_sandi_fit_device(amx_ctx *ctx, const amx_lut *lut, const double *d_y, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[2], {lut, d_y, nullptr, nullptr, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, nullptr, (hipStream_t)hip_stream, {}});
+}
+int amx_sandi_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *d_y, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[2], {lut, nullptr, d_y, nullptr, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, nullptr, (hipStream_t)hip_stream, {}});
+}
+
+int amx_czb_fit_device(amx_ctx *ctx, const amx_lut *lut, const double *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[3], {lut, d_y, nullptr, d_dirs, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, nullptr, (hipStream_t)hip_stream, {}});
+}
+int amx_czb_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *d_y, const double *d_dirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, double *d_estimates, double *d_rmse, double *d_nrmse, void *hip_stream)
+{
+    return amx_fit_dev(ctx, kFits[3], {lut, nullptr, d_y, d_dirs, n_vox, lambda1, lambda2, 0, flags, d_estimates, d_rmse, d_nrmse, nullptr, (hipStream_t)hip_stream, {}});
+}
+
+}  // extern "C"

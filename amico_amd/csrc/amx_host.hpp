@@ -1,4 +1,4 @@
-// amx_host.hpp -- host-side context shared by amx_api.hip and the per-model launch units.
+// amx_host.hpp -- host-side context shared by the entry-point units (amx_api / amx_plan / amx_lut / amx_fit_dev / amx_fit_host) and the per-model launch units.
 #pragma once
 #include "../../include/amico_amd.h"
 #include "amx_kernels.hpp"
@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <utility>
 #include <vector>
 
 constexpr int kChunk = 256;        // voxels of one orientation per workgroup
@@ -18,28 +19,50 @@ struct DevBuf {
     void *p = nullptr; size_t cap = 0;
 };
 
-struct amx_ctx {
+// The per-call workspace (stream-ordered, grow-only): ONE list.  A buffer added here is swapped between the two streams of a host-buffer call
+// and freed with the context; nothing else names the members.
+#define AMX_WORK_BUFS(X) X(lutidx) X(perm) X(counts) X(dir_start) X(cursor) X(chunks) X(misc) X(xiso) X(supp) X(ovf) X(cproj) X(ytil) X(seeds) \
+    X(schunks) X(ytil2) X(seeds2) X(cgemm) X(done) X(rlist) X(cgemm2) X(clip) X(feed)
+struct WorkSet {
+#define X(name) DevBuf name;
+    AMX_WORK_BUFS(X)
+#undef X
+    template <typename F> void for_each(F f) {
+#define X(name) f(name);
+        AMX_WORK_BUFS(X)
+#undef X
+    }
+};
+
+// Where a device fit stands in the call it belongs to: a device-pointer call is its own call (the default); fit_host enqueues the batches of a
+// host-buffer call with theirs.  Batches of one call all take the paths the WHOLE call's size asks for (bit-identical to the one-shot call).
+struct Batch {
+    int64_t call_vox = 0;          // voxels of the whole call (0: this fit's own)
+    int64_t base = 0;              // index of this batch's first voxel in the call
+    bool host = false;             // inside a host-buffer call: it reports progress per batch itself
+    bool first() const { return base == 0; }
+};
+
+struct amx_ctx : WorkSet {
     int device = 0;
     int n_cu = 256;                // compute units of the device (persistent-grid launches)
     std::string err;
-    // stream-ordered workspace (grow-only)
+    WorkSet alt;                   // second workspace set for the batch in flight on the other stream
+    void swap_work() { std::swap(static_cast<WorkSet &>(*this), alt); work_idx ^= 1; }
     DevBuf big;                    // factor blocks of k_noddi_lasso_big for dictionaries of more than 176 candidate atoms (amx_big.hip)
-    DevBuf lutidx, perm, counts, dir_start, cursor, chunks, misc, xiso, supp, ovf, cproj, ytil, seeds, schunks, ytil2, seeds2, cgemm, done, rlist, cgemm2, clip, feed;
     DevBuf hy, hdirs, hest, hrmse, hnrmse, hextra;   // staging for the host-pointer entry points
     int *status_d = nullptr;       // ST_WORDS ints
     int *status_h = nullptr;       // pinned mirror (+16 words: copy of the misc counters)
     int profiling = 0;             // 0 off, 1 every event pair of a call, 2 + w: pair w only (amx_set_profiling)
-    int64_t host_total_vox = 0;    // voxels of the whole host-buffer call while its batches are enqueued
-    int64_t call_vox = 0;          // voxels of the call being enqueued (the whole host-buffer call for its batches): size-dependent path choices made below noddi_fit_dev
+    int64_t call_vox = 0;          // voxels of the call being enqueued (the whole host-buffer call for its batches): every size-dependent path choice reads this
+    Batch batch;                   // of the fit being enqueued (fit_check sets both; fit_host clears it when the call is over)
     int64_t call_total_vox = 0;    // amx_set_call_voxels: the host-buffer calls on this ctx are shards of a call of this many voxels (0: they are the call)
-    bool in_host_fit = false;      // the host-buffer entry points report progress per batch themselves
     hipEvent_t ev[kEv];
     bool ev_valid[kEv];
     int64_t stats[4] = {0, 0, 0, 0};
     int64_t seed_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // amx_last_seed_stats
     int64_t uncert_vox[3] = {0, 0, 0};   // ... of which a stage ran without its Gram-space certificate (shape gate, AMX_NO_GCERT)
     int64_t seeded_vox = 0;        // voxels enqueued on the seed -> certificate chain since the last amx_sync_status
-    int64_t vox_base = 0;          // index of the first voxel of the batch being enqueued (chunked host entry points)
     double *dbg_x = nullptr;       // AMX_F_DEBUG_X destination (caller-owned device buffer, amx_set_debug_x)
     void (*progress)(int64_t, int64_t, void *) = nullptr;   // amx_set_progress
     void *progress_user = nullptr;
@@ -49,22 +72,12 @@ struct amx_ctx {
     std::thread stage_thread;      // makes the pool beside the dictionary upload (prefetch_stage_pool); joined by the first host-buffer fit that needs it
     amx_stage::Pool *stage_bg = nullptr;
     bool stage_bg_started = false;
-    bool host_native32 = false;    // set by a model's host entry point whose kernels read float32 signals in place (fit_host then skips k_widen)
-    const float *host_y32 = nullptr;   // the current batch's float32 signals in HBM (fit_host -> the model's enqueue), or null: float64 in the staging buffer
     bool stage_failed = false;     // the pool could not be made: host signals are copied as they are
     int host_narrowed = 0;         // batches of the last host-buffer call that travelled as float32 (amx_last_host_narrowed)
     hipStream_t hs = nullptr;      // non-blocking compute streams of the chunked host entry points: batches alternate
     hipStream_t hs2 = nullptr;     // between the two, so the tail of one batch's kernels is filled by the next batch's
     hipEvent_t hev[3] = {nullptr, nullptr, nullptr};
     hipEvent_t up_ev = nullptr;    // recorded on the null stream behind a batch's uploads; the batch's compute stream waits for it
-    // second workspace set for the batch in flight on the other stream (swap_work exchanges it with the named buffers)
-    DevBuf alt[22];
-    void swap_work()
-    {
-        DevBuf *named[22] = {&lutidx, &perm, &counts, &dir_start, &cursor, &chunks, &misc, &xiso, &supp, &ovf, &cproj, &ytil, &seeds, &schunks, &ytil2, &seeds2, &cgemm, &done, &rlist, &cgemm2, &clip, &feed};
-        for (int i = 0; i < 22; i++) { DevBuf t = *named[i]; *named[i] = alt[i]; alt[i] = t; }
-        work_idx ^= 1;
-    }
     // environment switches: read ONCE, by amx_ctx_create on the caller's thread, through kSwitches below -- the table is their documentation
     bool opt_no_seed, opt_no_gcert, opt_no_gcert_wide, opt_no_screen, opt_s2_exact, opt_no_chunk_order, opt_no_hard_first, opt_no_big_all;
     bool opt_wave_per_voxel, opt_no_refill, opt_sandi_atom_space, opt_fw_no_fuse, opt_prep_scalar, opt_debug;
@@ -301,7 +314,7 @@ struct amx_prep {
 // amx_last_path: every launch site names its kernel (the first batch of a host-buffer call only)
 static inline void amx_note(amx_ctx *ctx, const char *kernel)
 {
-    if ((ctx->in_host_fit && ctx->vox_base > 0) || ctx->path.size() > 1500) return;
+    if (!ctx->batch.first() || ctx->path.size() > 1500) return;
     if (!ctx->path.empty()) ctx->path += " -> ";
     ctx->path += kernel;
 }
@@ -432,3 +445,62 @@ static inline bool amx_fw_native_f32(const amx_ctx *ctx, int n_atoms, int nS, un
     if (!amx_use_lane_solver(ctx, n_atoms, lam2)) return true;                     // wavefront per voxel: load_rows
     return amx_fw_use_refill(ctx, n_atoms, nS, flags, lam2) && nS <= 96;
 }
+
+// ------------------------------------------------------------------ what the entry-point units share (library-internal: not exported)
+#pragma GCC visibility push(hidden)
+// One row per model: what the shared prologue / epilogue of a fit needs to know
+struct FitSpec {
+    int model;                     // amx_lut::model
+    const char *name, *what;       // in messages: "<name>: not a <what> dictionary"
+    bool dirs;                     // takes DIRs (a plan by orientation); SANDI has one dictionary
+    int maps;                      // per voxel (+ 1 for an ex-vivo NODDI dictionary, + 2 for FreeWater's Mouse)
+    unsigned extra_flag;           // the flag of the optional fourth output (0: none), its columns (0: the dictionary's nS)
+    int extra_cols;
+    int x_per_atom;                // coefficients per atom and voxel that AMX_F_DEBUG_X stores
+};
+extern const FitSpec kFits[4];     // by model - 1 (amx_fit_dev.hip)
+inline int fit_bad(amx_ctx *ctx, const FitSpec &m, const char *a, const char *b = nullptr) { return amx_bad(ctx, (std::string(m.name) + a + (b ? m.what : "") + (b ? b : "")).c_str()); }
+
+// the arguments of one device fit, whichever the model (y or y32 is set; extra: NODDI's modulated maps / FreeWater's corrected DWI)
+struct FitCall {
+    const amx_lut *lut; const double *y; const float *y32; const double *dirs; int64_t n;
+    double lam1, lam2; int is_mouse; unsigned flags;
+    double *est, *rmse, *nrmse, *extra; hipStream_t stream;
+    Batch batch;
+};
+inline int fit_maps(const FitSpec &m, const FitCall &c) { return m.maps + (c.lut->is_exvivo ? 1 : 0) + (c.is_mouse ? 2 : 0); }
+int amx_fit_dev(amx_ctx *ctx, const FitSpec &spec, FitCall c);                     // amx_fit_dev.hip
+
+// the ONE place that fills the arguments every solver kernel shares (the overflow lists are launch_pair's)
+inline void fill_common(amx::FitCommon &c, const void *tiles, const double *y, const float *y32, const Plan &pl, int *status, int nS, int ldA,
+                        int n_atoms, int tile_stride, double lam1, double lam2, unsigned flags)
+{
+    c.tiles = tiles; c.y = y; c.y32 = y32; c.perm = pl.perm; c.chunks = pl.chunks; c.n_chunks = pl.n_chunks;
+    c.lutidx = pl.lutidx; c.status = status; c.nS = nS; c.ldA = ldA;
+    c.n_atoms = n_atoms; c.tile_stride = tile_stride; c.lam1 = lam1; c.lam2 = lam2; c.flags = flags;
+}
+
+// amx_plan.hip: the per-call plan and the small launches around the solvers
+int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, bool seeds = false, int table_rows = 0, int blocks_chunk = 0);
+int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, Plan &pl, hipStream_t s, int chunk = kChunk,
+                      double *zero_rows = nullptr, int zero_cols = 0);
+int enqueue_index_bucketing(amx_ctx *ctx, const int32_t *d_idx, int n_dicts, int64_t n, Plan &pl, hipStream_t s);   // the batched solvers' plan
+int enqueue_linear_plan(amx_ctx *ctx, int64_t n, Plan &pl, hipStream_t s);                                          // SANDI's: the voxels in order
+void fold_counters(amx_ctx *ctx, hipStream_t s);
+void widen_on_device(const float *d_y32, double *dst, size_t nel, hipStream_t s);
+void clear_events(amx_ctx *ctx);
+void progress_tick(amx_ctx *ctx, hipStream_t s, int64_t done, int64_t total);
+// amx_fit_host.hip: the host threads of the float32 transport are made beside a dictionary upload
+void prefetch_stage_pool(amx_ctx *ctx);
+
+template <typename T>
+static int amx_upload(amx_ctx *ctx, T **dst, const T *src, size_t n)
+{
+    HIPCHK(ctx, hipMalloc((void **)dst, n * sizeof(T) + 16));
+    HIPCHK(ctx, hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+    return AMX_OK;
+}
+#define AMX_H2D(buf, src, bytes)                                                     \
+    if ((rc = amx_ensure(ctx, buf, bytes))) return rc;                               \
+    HIPCHK(ctx, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, nullptr));
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// amx_kernels.hpp -- gfx950 kernels of the AMICO fit path (included by amx_api.hip only).
+// amx_kernels.hpp -- gfx950 kernels of the AMICO fit path (through amx_host.hpp: every unit).
 //
 //   k_dir_to_lut      lut.pyx:316-356 per voxel + histogram of LUT indices
 //   k_plan            exclusive scan of the histogram, chunk list (<= CH voxels of ONE

@@ -346,7 +346,7 @@ int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
     //  costs them 37 ns against 14 at 99 volumes: 150 volumes, 1 M voxels 11.23 -> 10.65 ms with the pass, stage-3 left-overs 38 219 -> 6 429;
     //  at 99 - 105 volumes it still loses below 2 M voxels, SNR 50 included: profiles/r06_protocols_ab.txt)
     const int64_t rescue_from = ctx->opt_rescue_from >= 0 ? ctx->opt_rescue_from : kRescueFrom;   // (AMX_RESCUE_FROM given: the caller's threshold alone decides)
-    if ((ctx->in_host_fit ? ctx->host_total_vox : (int64_t)pl.n) >= (lut->is_exvivo ? rescue_from / 4 : rescue_from) ||
+    if (ctx->call_vox >= (lut->is_exvivo ? rescue_from / 4 : rescue_from) ||
         (lut->nS > 128 && ctx->opt_rescue_from < 0) ||
         amx_noddi_tile_global(lut->nS, lut->ldA, lut->n_atoms)) {
         // second pass (large calls: below ~2 M voxels the launch costs more than the wavefront-per-voxel kernel saves -- 1 M voxels

@@ -7,7 +7,7 @@
 // to 6.5 ms of kernels -- the copy IS the call.  So the copy is halved where that is exact: host threads narrow the caller's
 // buffer chunk by chunk into a ring of four pinned buffers, CHECKING every element ((double)(float)v == v; 144 - 260 GB/s of
 // float64 on the box's cores, tools/probes/h2d_probe.hip), the calling thread sends chunk k with the blocking copy it always
-// used while the chunks behind it are being narrowed, and the device widens the batch again (k_widen, amx_api.hip).  One element that is not a
+// used while the chunks behind it are being narrowed, and the device widens the batch again (k_widen, amx_plan.hip).  One element that is not a
 // float32 (or is a NaN: it never compares equal) and the batch -- and every later batch of the call -- is copied as it is.
 // The values the kernels read are the caller's, bit for bit, either way.
 // (Measured and dropped: every host thread sending its own slices on its own stream -- 100 GB/s of float64 alone on the box,

@@ -1,6 +1,6 @@
 """Every device route of CylinderZeppelinBall against the CPU oracle and the Kuhn-Tucker certificate of its own coefficients.
 
-amx_czb_fit_device has two routes (amx_api.hip, czb_fit_dev).  The product path -- default ridge, no error maps, <= 32 atoms,
+amx_czb_fit_device has two routes (amx_fit_dev.hip, czb_fit_dev).  The product path -- default ridge, no error maps, <= 32 atoms,
 <= 160 volumes -- is k_czb_tables -> k_czb_project<25|40> -> k_czb_lane (+ the wavefront-per-voxel kernel over the overflow list);
 everything else is k_czb, or k_czb_qr below lambda2 = 1e-6.  The tests of test_gpu_czb.py that have a reference ask for an error map
 and therefore run k_czb.  Here every case first asserts its route from ctx.last_path(), then holds EVERY voxel to:
