@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('AMICO_AMD_LIB') or os.path.join(_HERE, 'csrc', 'libamico_amd.so')   # override: A/B builds
 
 AMX_OK, AMX_E_BADARG, AMX_E_HIP, AMX_E_DIR_OOB, AMX_E_OVERFLOW, AMX_E_NODEVICE = 0, -1, -2, -3, -4, -5
-F_RMSE, F_NRMSE, F_MODULATED, F_CORRECTED, F_DEBUG_X = 1, 2, 4, 8, 16
+F_RMSE, F_NRMSE, F_MODULATED, F_CORRECTED, F_DEBUG_X, F_FW_ISO = 1, 2, 4, 8, 16, 32
 
 # every symbol include/amico_amd.h declares (tests check that the library exports them all)
 SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxels', 'amx_ctx_create', 'amx_ctx_destroy', 'amx_last_error',
@@ -20,7 +20,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_dir_to_lut_idx', 'amx_noddi_fit', 'amx_freewater_fit', 'amx_sandi_fit',
            'amx_noddi_fit_device', 'amx_freewater_fit_device', 'amx_sandi_fit_device', 'amx_sync_status',
            'amx_noddi_fit_device_f32', 'amx_freewater_fit_device_f32', 'amx_sandi_fit_device_f32', 'amx_czb_fit_device_f32',
-           'amx_set_debug_x', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
+           'amx_set_debug_x', 'amx_set_fw_iso', 'amx_freewater_corrected_device', 'amx_prep_corrected_device', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
            'amx_set_profiling', 'amx_last_kernel_ms', 'amx_last_stats', 'amx_last_seed_stats', 'amx_last_host_narrowed', 'amx_last_path', 'amx_host_pool_info', 'amx_selftest',
            'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
@@ -113,6 +113,9 @@ def lib():
                                        c_vp, c_vp, c_vp, c_vp]
     L.amx_sync_status.argtypes = [c_vp, c_vp]
     L.amx_set_debug_x.argtypes = [c_vp, c_vp]
+    L.amx_set_fw_iso.argtypes = [c_vp, c_vp]
+    L.amx_freewater_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]      # ctx, lut, y32, y64, x_iso, n, ycorr, stream
+    L.amx_prep_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, C.c_int, c_vp, c_vp]  # ctx, plan, lut, y32, x_iso, mean_b0, b0_cols (host), n, volume, stream
     L.amx_debug_fetch.argtypes = [c_vp, c_vp, C.c_int, c_vp, C.c_size_t]
     L.amx_noddi_fit_f32.argtypes = [c_vp, c_vp, c_fp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp, c_dp]
     L.amx_freewater_fit_f32.argtypes = [c_vp, c_vp, c_fp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_uint,
@@ -361,7 +364,9 @@ def upload_freewater(ctx, kernels, htable):
     h = c_vp()
     ctx.check(lib().amx_lut_upload_freewater(ctx._h, _p(D, c_fp), _p(CSF, c_fp), _p(ht, c_i16p), D.shape[0],
                                              CSF.shape[0], D.shape[1], D.shape[2], C.byref(h)))
-    return Lut(ctx, h, 'FreeWater', D.shape[2], D.shape[0] + CSF.shape[0])
+    lut = Lut(ctx, h, 'FreeWater', D.shape[2], D.shape[0] + CSF.shape[0])
+    lut.n_iso = CSF.shape[0]
+    return lut
 
 
 def upload_sandi(ctx, kernels, Rs, d_in, d_isos):
@@ -545,20 +550,44 @@ def noddi_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, n_maps, rmse=False
 
 
 def freewater_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, is_mouse, rmse=False, nrmse=False, corrected=False,
-                         stream=None, return_x=False):
+                         stream=None, return_x=False, iso=False):
+    """iso=True: the isotropic coefficients of every voxel, f64 [n_vox, n_iso], come back as one more element (AMX_F_FW_ISO: what
+    freewater_corrected_device / Prep.corrected_device make the corrected DWI from; the flag changes no path, unlike corrected=True)"""
     import torch
     _check_dev(lut, y_t, dirs_t)
     n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
     xd, fx = _debug_x(ctx, (n, lut.n_atoms), y_t, return_x)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_CORRECTED if corrected else 0) | fx
+    xi = torch.empty((n, lut.n_iso), **f64) if iso else None
+    if iso:
+        ctx.check(lib().amx_set_fw_iso(ctx._h, _dptr(xi)))
+    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_CORRECTED if corrected else 0) | fx | (F_FW_ISO if iso else 0)
     est = torch.empty((n, 4 if is_mouse else 2), **f64)
     r = torch.empty(n, **f64) if rmse else None
     nr = torch.empty(n, **f64) if nrmse else None
     yc = torch.empty((n, lut.nS), **f64) if corrected else None
-    ctx.check(_dev_fn('freewater', y_t)(ctx._h, lut._h, _dptr(y_t), _dptr(dirs_t), n, float(lambda1), float(lambda2),
-                                             int(bool(is_mouse)), flags, _dptr(est), _dptr(r), _dptr(nr), _dptr(yc),
-                                             c_vp(stream or 0)))
-    return (est, r, nr, yc, xd) if return_x else (est, r, nr, yc)
+    try:
+        ctx.check(_dev_fn('freewater', y_t)(ctx._h, lut._h, _dptr(y_t), _dptr(dirs_t), n, float(lambda1), float(lambda2),
+                                                 int(bool(is_mouse)), flags, _dptr(est), _dptr(r), _dptr(nr), _dptr(yc),
+                                                 c_vp(stream or 0)))
+    finally:
+        if iso:
+            lib().amx_set_fw_iso(ctx._h, None)       # (the kernels enqueued above carry the pointer; the tensor is the caller's from here)
+    return (est, r, nr, yc) + ((xd,) if return_x else ()) + ((xi,) if iso else ())
+
+
+def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None):
+    """y f32 | f64 [n, nS] and x_iso f64 [n, n_iso] (device tensors) -> y_corrected f64 [n, nS] (models.pyx:1264-1274): the rows
+    AMX_F_CORRECTED writes, from the coefficients a fit with iso=True left (amx_freewater_corrected_device); enqueued on `stream`"""
+    import torch
+    _check_dev(lut, y_t)
+    n = y_t.shape[0]
+    if xiso_t.dtype != torch.float64 or tuple(xiso_t.shape) != (n, lut.n_iso) or not xiso_t.is_contiguous() or xiso_t.device != y_t.device:
+        raise ValueError(f'x_iso must be a contiguous float64 device tensor [n_vox, {lut.n_iso}] on the device of y')
+    yc = torch.empty((n, lut.nS), dtype=torch.float64, device=y_t.device)
+    f32 = y_t.dtype == torch.float32
+    ctx.check(lib().amx_freewater_corrected_device(ctx._h, lut._h, _dptr(y_t) if f32 else None, None if f32 else _dptr(y_t), _dptr(xiso_t),
+                                                   n, _dptr(yc), c_vp(stream or 0)))
+    return yc
 
 
 def czb_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, rmse=False, nrmse=False, stream=None, return_x=False):
@@ -809,6 +838,25 @@ class Prep:
         """device pointer (int) of the image's element buffer, enqueued on `stream`; the count: Context.sanitize_last()"""
         self.ctx.check(lib().amx_prep_sanitize_device(self.ctx._h, self._h, c_vp(d_img), int(replace is not None), _replacement(replace, np.float32),
                                                       c_vp(stream or 0)))
+
+    def corrected_device(self, lut, y_t, xiso_t, volume_t, mean_b0_t=None, b0_cols=(), stream=None):
+        """RESULTS['DWI_corrected'] (core.py:488-498) in HBM: y f32 [n_vox, n_out], x_iso f64 [n_vox, n_iso] (rows in the plan's masked
+        order) -> volume f32 [X, Y, Z, n_out], every element written once; mean_b0_t f32 [n_vox]: rescale by it (None: no rescaling);
+        b0_cols: columns that keep y * mean_b0 (doKeepb0Intact).  Device tensors, enqueued on `stream` (amx_prep_corrected_device)"""
+        import torch
+        n = self.n_vox
+        if y_t.dtype != torch.float32 or tuple(y_t.shape) != (n, self.n_out) or not y_t.is_contiguous():
+            raise ValueError(f'y must be a contiguous float32 device tensor [{n}, {self.n_out}]')
+        if xiso_t.dtype != torch.float64 or tuple(xiso_t.shape) != (n, lut.n_iso) or not xiso_t.is_contiguous():
+            raise ValueError(f'x_iso must be a contiguous float64 device tensor [{n}, {lut.n_iso}]')
+        if mean_b0_t is not None and (mean_b0_t.dtype != torch.float32 or tuple(mean_b0_t.shape) != (n,) or not mean_b0_t.is_contiguous()):
+            raise ValueError(f'mean_b0 must be a contiguous float32 device tensor [{n}]')
+        if volume_t.dtype != torch.float32 or tuple(volume_t.shape) != self.shape[:3] + (self.n_out,) or not volume_t.is_contiguous():
+            raise ValueError('volume must be a contiguous float32 device tensor [X, Y, Z, n_out]')
+        b0 = np.ascontiguousarray(b0_cols, dtype=np.int32).ravel()
+        self.ctx.check(lib().amx_prep_corrected_device(self.ctx._h, self._h, lut._h, _dptr(y_t), _dptr(xiso_t), _dptr(mean_b0_t),
+                                                       _p(b0, c_i32p) if len(b0) else None, len(b0), _dptr(volume_t), c_vp(stream or 0)))
+        return volume_t
 
     def scatter(self, values):
         v = np.ascontiguousarray(values, dtype=np.float64)

@@ -277,7 +277,7 @@ class Evaluation:
             if self.get_config('debias_unconverged'):
                 warnings.warn(f"Rician debias: {self.get_config('debias_unconverged')} samples did not converge")
         self._y, self._DIRs = None, None
-        self._dev = {'y': d_y, 'dirs': d_dirs}
+        self._dev = {'y': d_y, 'dirs': d_dirs, 'mb0': d_mb0}
         self.mean_b0s = d_mb0.cpu().numpy() if self._prep.do_normalize else None
         self.set_config('dirs_precomputing_time', time.time() - t)
         t = time.time()
@@ -319,12 +319,27 @@ class Evaluation:
         if self.model.name == 'NODDI' and self.get_config('doSaveModulatedMaps'):
             self.RESULTS['MAPs_mod'] = sc('estimates_mod', results['estimates_mod'])
         if self.model.name == 'Free-Water' and self.get_config('doSaveCorrectedDWI'):
-            y_corrected = results['y_corrected']                      # core.py:488-498
-            b0_idx = self.scheme.b0_idx
-            if self.get_config('doNormalizeSignal') and self.scheme.b0_count > 0:
-                y_corrected = y_corrected * np.reshape(self.mean_b0s, (-1, 1))
-            if self.get_config('doKeepb0Intact') and self.scheme.b0_count > 0:
-                y_corrected[:, b0_idx] = self.y[:, b0_idx] * np.reshape(self.mean_b0s, (-1, 1))
-            self.RESULTS['DWI_corrected'] = self._prep.scatter(y_corrected)
+            b0_idx = self.scheme.b0_idx                               # core.py:488-498
+            rescale = bool(self.get_config('doNormalizeSignal')) and self.scheme.b0_count > 0
+            keep_b0 = bool(self.get_config('doKeepb0Intact')) and self.scheme.b0_count > 0
+            x_iso = out.get('x_iso')
+            # (amx_prep_corrected_device keeps at most 128 b0 columns -- kCorrMaxB0, like the debias kernel's limit; a scheme with more and
+            #  doKeepb0Intact takes the rows results['y_corrected'] -- still the GPU kernel's -- through the host block below)
+            if x_iso is not None and not (keep_b0 and self.scheme.b0_count > 128):
+                # the fit left the isotropic coefficients in HBM: y, x_iso (and mean_b0) -> the float32 volume in one kernel, one copy home;
+                # neither y nor the rows results['y_corrected'] come to the host (amx_prep_corrected_device)
+                vol = torch.empty(img.shape[:3] + (self._prep.n_out,), dtype=torch.float32, device=dev)
+                plan.corrected_device(self._dev['lut'], self._dev['y'], x_iso, vol, self._dev['mb0'] if rescale else None,
+                                      b0_idx if keep_b0 else ())
+                ctx.sync()
+                self.RESULTS['DWI_corrected'] = vol.cpu().numpy()
+            else:
+                y_corrected = results['y_corrected']
+                if rescale:
+                    y_corrected = y_corrected * np.reshape(self.mean_b0s, (-1, 1))
+                if keep_b0:
+                    y_corrected[:, b0_idx] = self.y[:, b0_idx] * np.reshape(self.mean_b0s, (-1, 1))
+                self.RESULTS['DWI_corrected'] = self._prep.scatter(y_corrected)
         self._dev.pop('out', None)
+        self._dev.pop('lut', None)
         return results

@@ -251,6 +251,13 @@ int amx_set_debug_x(amx_ctx *ctx, double *d_x)
     return AMX_OK;
 }
 
+int amx_set_fw_iso(amx_ctx *ctx, double *d_xiso)
+{
+    if (!ctx) return AMX_E_BADARG;
+    ctx->fw_iso = d_xiso;
+    return AMX_OK;
+}
+
 int amx_selftest(amx_ctx *ctx, double *out512)
 {
     if (!ctx || !out512) return AMX_E_BADARG;

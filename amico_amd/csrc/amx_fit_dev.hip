@@ -5,8 +5,9 @@
 using namespace amx;
 
 // (CylinderZeppelinBall: the Gram-space solver needs a ridge -- models.pyx:439 default: 4.0; lambda2 < 1e-6 runs the thin-QR solver in A-space)
-const FitSpec kFits[4] = {{1, "amx_noddi_fit", "NODDI", true, 3, AMX_F_MODULATED, 2, 3}, {2, "amx_freewater_fit", "FreeWater", true, 2, AMX_F_CORRECTED, 0, 1},
-                          {3, "amx_sandi_fit", "SANDI", false, 6, 0, 1, 1}, {4, "amx_czb_fit", "CylinderZeppelinBall", true, 3, 0, 1, 1}};
+const FitSpec kFits[4] = {{1, "amx_noddi_fit", "NODDI", true, 3, AMX_F_MODULATED, 2, 3, 0}, {2, "amx_freewater_fit", "FreeWater", true, 2, AMX_F_CORRECTED, 0, 1, AMX_F_FW_ISO},
+                          {3, "amx_sandi_fit", "SANDI", false, 6, 0, 1, 1, 0}, {4, "amx_czb_fit", "CylinderZeppelinBall", true, 3, 0, 1, 1, 0}};
+constexpr unsigned kModelFlags = AMX_F_FW_ISO;       // every flag that belongs to one model (FitSpec::model_flags)
 
 namespace {
 
@@ -22,6 +23,8 @@ int fit_check(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if (c.n == 0) return AMX_OK;
     if ((!c.y && !c.y32) || (m.dirs && !c.dirs) || !c.est) return fit_bad(ctx, m, ": null buffer");
     if (((c.flags & AMX_F_RMSE) && !c.rmse) || ((c.flags & AMX_F_NRMSE) && !c.nrmse) || ((c.flags & m.extra_flag) && !c.extra)) return fit_bad(ctx, m, ": flag set but output buffer is null");
+    if (c.flags & kModelFlags & ~m.model_flags) return fit_bad(ctx, m, ": AMX_F_FW_ISO is a flag of the FreeWater fit");
+    if ((c.flags & m.model_flags & AMX_F_FW_ISO) && !ctx->fw_iso) return fit_bad(ctx, m, ": AMX_F_FW_ISO without a buffer (amx_set_fw_iso)");
     if (!(c.lam2 >= 0.0) || !(c.lam1 >= 0.0)) return fit_bad(ctx, m, ": need lambda1 >= 0 and lambda2 >= 0");
     if (c.is_mouse && c.lut->n_iso < 2) return amx_bad(ctx, "amx_freewater_fit: Mouse needs two isotropic atoms");   // (is_mouse: FreeWater only)
     HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -32,11 +35,11 @@ int fit_check(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
 
 // the call's first event, and the voxels bucketed by orientation (a voxel whose direction is out of bounds is skipped by every kernel:
 // k_dir_to_lut gives it defined (zero) maps, so no fit clears its maps first -- test_*_fit_writes_every_voxel)
-int fit_open(amx_ctx *ctx, const FitSpec &m, const FitCall &c, Plan &pl, int chunk = kChunk)
+int fit_open(amx_ctx *ctx, const FitSpec &m, const FitCall &c, Plan &pl, int chunk = kChunk, double *zero_rows2 = nullptr, int zero_cols2 = 0)
 {
     clear_events(ctx);
     rec(ctx, 0, c.stream);
-    return m.dirs ? enqueue_bucketing(ctx, c.lut, c.dirs, c.n, pl, c.stream, chunk, c.est, fit_maps(m, c)) : AMX_OK;
+    return m.dirs ? enqueue_bucketing(ctx, c.lut, c.dirs, c.n, pl, c.stream, chunk, c.est, fit_maps(m, c), zero_rows2, zero_cols2) : AMX_OK;
 }
 
 // what every model's kernel arguments have in common; the outputs are gated by their flags
@@ -265,8 +268,10 @@ int freewater_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = make_plan(ctx, c.n, lut->ndirs, pl))) return rc;
     const bool refill = amx_use_lane_solver(ctx, lut->n_atoms, c.lam2) && amx_fw_use_refill(ctx, lut->n_atoms, lut->nS, c.flags, c.lam2);
     FwArgs a;
-    if ((rc = fit_open(ctx, m, c, pl, refill ? amx_refill_chunk(c.n) : kChunk)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
-    a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = c.is_mouse; a.n_maps = fit_maps(m, c);
+    // AMX_F_FW_ISO: the isotropic coefficients of every voxel, at the voxel's index in the caller's buffer (fit_check has seen the buffer)
+    double *xiso = (c.flags & AMX_F_FW_ISO) ? ctx->fw_iso + (size_t)c.batch.base * lut->n_iso : nullptr;
+    if ((rc = fit_open(ctx, m, c, pl, refill ? amx_refill_chunk(c.n) : kChunk, xiso, lut->n_iso)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
+    a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = c.is_mouse; a.n_maps = fit_maps(m, c); a.xiso = xiso;
     if (refill && (rc = amx_fw_prepare(ctx, lut, a, s))) return rc;
     return fit_close(ctx, c, amx_launch_fw(ctx, a, pl, s));
 }

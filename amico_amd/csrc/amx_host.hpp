@@ -64,6 +64,7 @@ struct amx_ctx : WorkSet {
     int64_t uncert_vox[3] = {0, 0, 0};   // ... of which a stage ran without its Gram-space certificate (shape gate, AMX_NO_GCERT)
     int64_t seeded_vox = 0;        // voxels enqueued on the seed -> certificate chain since the last amx_sync_status
     double *dbg_x = nullptr;       // AMX_F_DEBUG_X destination (caller-owned device buffer, amx_set_debug_x)
+    double *fw_iso = nullptr;      // AMX_F_FW_ISO destination (caller-owned device buffer, amx_set_fw_iso)
     void (*progress)(int64_t, int64_t, void *) = nullptr;   // amx_set_progress
     void *progress_user = nullptr;
     DevBuf wy;                     // float64 copy of float32 device signals for the lane kernels that read float64 only (amx_*_fit_device_f32)
@@ -413,8 +414,8 @@ int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipS
 // with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
 // the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.
 __host__ __device__ static inline bool amx_warm_start(double lam2, unsigned flags) { return lam2 >= 1e-5 && !(flags & 0x80000000u); }
-// FreeWater with lanes that never idle (k_freewater_refill, amx_small.hip): maps only (the error maps / corrected DWI
-// need the signal again and stay with k_freewater_lane), <= 12 atoms; chunks of up to 4096 voxels per workgroup
+// FreeWater with lanes that never idle (k_freewater_refill, amx_small.hip): maps only (the error maps / AMX_F_CORRECTED
+// need the signal again and stay with k_freewater_lane; AMX_F_FW_ISO needs only x and selects nothing), <= 12 atoms; chunks of up to 4096 voxels per workgroup
 // voxels of one orientation per workgroup of the refill kernel: large enough to keep the lanes fed (the buffer needs a
 // pool to draw from), small enough for ~3 rounds of workgroups over the chip (measured on 2 M voxels: 512 -> 1.83 ms,
 // 1024 -> 1.79, 2048 -> 1.93, 4096 -> 2.54)
@@ -457,6 +458,7 @@ struct FitSpec {
     unsigned extra_flag;           // the flag of the optional fourth output (0: none), its columns (0: the dictionary's nS)
     int extra_cols;
     int x_per_atom;                // coefficients per atom and voxel that AMX_F_DEBUG_X stores
+    unsigned model_flags;          // flags only this model's fit takes (FreeWater: AMX_F_FW_ISO); on any other model's they are AMX_E_BADARG
 };
 extern const FitSpec kFits[4];     // by model - 1 (amx_fit_dev.hip)
 inline int fit_bad(amx_ctx *ctx, const FitSpec &m, const char *a, const char *b = nullptr) { return amx_bad(ctx, (std::string(m.name) + a + (b ? m.what : "") + (b ? b : "")).c_str()); }
@@ -483,7 +485,7 @@ inline void fill_common(amx::FitCommon &c, const void *tiles, const double *y, c
 // amx_plan.hip: the per-call plan and the small launches around the solvers
 int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, bool seeds = false, int table_rows = 0, int blocks_chunk = 0);
 int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, Plan &pl, hipStream_t s, int chunk = kChunk,
-                      double *zero_rows = nullptr, int zero_cols = 0);
+                      double *zero_rows = nullptr, int zero_cols = 0, double *zero_rows2 = nullptr, int zero_cols2 = 0);
 int enqueue_index_bucketing(amx_ctx *ctx, const int32_t *d_idx, int n_dicts, int64_t n, Plan &pl, hipStream_t s);   // the batched solvers' plan
 int enqueue_linear_plan(amx_ctx *ctx, int64_t n, Plan &pl, hipStream_t s);                                          // SANDI's: the voxels in order
 void fold_counters(amx_ctx *ctx, hipStream_t s);

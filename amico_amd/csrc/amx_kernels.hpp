@@ -360,6 +360,7 @@ struct FwArgs {
     int ldC;
     int *queue;                    // global ticket of the persistent solver wavefronts (sub-chunks)
     int sub_per_chunk;
+    double *xiso;                  // AMX_F_FW_ISO: the isotropic coefficients x[n_perp .. n_atoms - 1], [n_vox][n_iso] (null = off)
 };
 
 template <int NR, int NQ, int MAXP>
@@ -385,6 +386,7 @@ __device__ __forceinline__ void fw_voxel(const FwArgs &a, const float *As, doubl
         if (lane == 0 && a.nrmse) a.nrmse[vox] = __builtin_nan("");
         if (a.ycorr)
             for (int i = lane; i < nS; i += kWave) a.ycorr[(size_t)vox * nS + i] = __builtin_nan("");
+        if (a.xiso && lane < a.n_iso) a.xiso[(size_t)vox * a.n_iso + lane] = __builtin_nan("");
     }
     if (ok) {
     NNSolver<NR, NQ, MAXP, true, float> S;
@@ -397,6 +399,12 @@ __device__ __forceinline__ void fw_voxel(const FwArgs &a, const float *As, doubl
     const bool act = lane < S.np;
     const double xs = act ? S.x : 0.0;
     if (a.c.xdbg) store_x_dense<NQ>(a.c.xdbg + (size_t)vox * n_atoms, n_atoms, lane, S.np, S.idx, S.x);
+    if (a.xiso) {                  // (one passive slot holds atom n_perp + k, or none does: the sum IS that coefficient, or an exact zero)
+        for (int k = 0; k < a.n_iso; k++) {
+            const double xk = wave_sum((act && S.idx == n_perp + k) ? xs : 0.0);
+            if (lane == 0) a.xiso[(size_t)vox * a.n_iso + k] = xk;
+        }
+    }
     // models.pyx:1241-1256
     const double x_sum = wave_sum(xs) + 1e-16;
     const double v = wave_sum((act && S.idx < n_perp) ? xs : 0.0) / x_sum;

@@ -71,7 +71,7 @@ int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, bool seeds, int tabl
 }
 
 int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, Plan &pl, hipStream_t s, int chunk,
-                      double *zero_rows, int zero_cols)
+                      double *zero_rows, int zero_cols, double *zero_rows2, int zero_cols2)
 {
     // (four launches: the counters cleared in one, the chunk order in k_plan's tail; they were three memsets and five kernels --
     //  ~11 us a node in a small call, profiles/r06_launch_nodes.txt)
@@ -81,7 +81,7 @@ int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, in
     const int nb = (int)((n + span - 1) / span);
     const int use_lds = lut->ndirs <= 8192 ? 1 : 0;          // LDS histograms: 2 * ndirs ints
     hipLaunchKernelGGL(k_dir_to_lut, dim3(nb), dim3(1024), use_lds ? (size_t)lut->ndirs * sizeof(int) : 0, s, d_dirs,
-                       (int)n, lut->htable, lut->ndirs, pl.lutidx, pl.counts, ctx->status_d, use_lds, (int)ctx->batch.base, span, zero_rows, zero_cols);
+                       (int)n, lut->htable, lut->ndirs, pl.lutidx, pl.counts, ctx->status_d, use_lds, (int)ctx->batch.base, span, zero_rows, zero_cols, zero_rows2, zero_cols2);
     AMX_TRACE(ctx, s, "k_dir_to_lut");
     hipLaunchKernelGGL(k_plan, dim3(1), dim3(1024), 0, s, pl.counts, lut->ndirs, chunk, pl.dir_start,
                        pl.cursor, pl.chunks, pl.n_chunks, pl.schunks ? pl.seed_chunk : 0, pl.schunks, (pl.schunks && !ctx->opt_no_chunk_order) ? 1 : 0);
@@ -205,7 +205,7 @@ extern "C" int amx_dir_to_lut_idx(amx_ctx *ctx, const amx_lut *lut, const double
     if ((rc = amx_ensure(ctx, ctx->lutidx, (size_t)n * sizeof(int)))) return rc;
     hipLaunchKernelGGL(k_dir_to_lut, dim3((unsigned)((n + kPrepSpan - 1) / kPrepSpan)), dim3(1024), 0, nullptr,
                        (const double *)ctx->hdirs.p, (int)n, lut->htable, lut->ndirs, (int *)ctx->lutidx.p, (int *)nullptr,
-                       ctx->status_d, 0, 0, kPrepSpan, (double *)nullptr, 0);
+                       ctx->status_d, 0, 0, kPrepSpan, (double *)nullptr, 0, (double *)nullptr, 0);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(out_idx, ctx->lutidx.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, nullptr));
     return amx_sync_status(ctx, nullptr);

@@ -35,11 +35,11 @@ constexpr int kPrepSpan = 8192;
 inline int prep_span(int64_t n) { const int64_t s = ((n + 255) / 256 + 1023) / 1024 * 1024; return (int)(s < 1024 ? 1024 : (s > kPrepSpan ? kPrepSpan : s)); }
 
 // zrows (optional): the output rows [n][zcols] of the voxels that are SKIPPED (direction out of bounds: the call returns an error) are
-// zeroed here, so that a fit need not clear its whole output first
+// zeroed here, so that a fit need not clear its whole output first (zrows2: a second such output, FreeWater's x_iso)
 __global__ __launch_bounds__(1024) void k_dir_to_lut(const double *__restrict__ dirs, int n, const short *__restrict__ ht,
                                                      int ndirs, int *__restrict__ lutidx, int *__restrict__ counts,
                                                      int *__restrict__ status, int use_lds, int vbase, int span,
-                                                     double *__restrict__ zrows, int zcols)
+                                                     double *__restrict__ zrows, int zcols, double *__restrict__ zrows2, int zcols2)
 {
     extern __shared__ int hist[];
     if (use_lds) {
@@ -57,6 +57,7 @@ __global__ __launch_bounds__(1024) void k_dir_to_lut(const double *__restrict__ 
             atomicMin(reinterpret_cast<unsigned long long *>(status + ST_ERRPACK),
                       ((unsigned long long)(unsigned)(v + vbase) << 32) | (unsigned long long)(((unsigned)(ii1 + 1) << 16) | (unsigned)(ii2 + 1)));
             if (zrows) for (int j = 0; j < zcols; j++) zrows[(size_t)v * zcols + j] = 0.0;
+            if (zrows2) for (int j = 0; j < zcols2; j++) zrows2[(size_t)v * zcols2 + j] = 0.0;
         } else if (counts) {
             atomicAdd(use_lds ? &hist[idx] : &counts[idx], 1);
         }

@@ -253,6 +253,7 @@ __global__ void __launch_bounds__(256) k_freewater_lane(const FwArgs a)
             if (a.rmse) a.rmse[vox] = nan;
             if (a.nrmse) a.nrmse[vox] = nan;
             if (a.ycorr) for (int i = 0; i < nS; i++) a.ycorr[(size_t)vox * nS + i] = nan;
+            if (a.xiso) for (int k = 0; k < a.n_iso; k++) a.xiso[(size_t)vox * a.n_iso + k] = nan;
             continue;
         }
 #pragma unroll
@@ -261,6 +262,10 @@ __global__ void __launch_bounds__(256) k_freewater_lane(const FwArgs a)
         if (a.c.xdbg) {
 #pragma unroll
             for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
+        }
+        if (a.xiso) {
+#pragma unroll
+            for (int j = 0; j < N; j++) if (j >= n_perp && j < n_atoms) a.xiso[(size_t)vox * a.n_iso + (j - n_perp)] = x[j];
         }
         // models.pyx:1241-1256
         double x_sum = 0.0, x_perp = 0.0;
@@ -1130,6 +1135,7 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
                 if (!(c[0] == c[0])) {
                     const double nan = __builtin_nan("");
                     for (int m = 0; m < a.n_maps; m++) e[m] = nan;
+                    if (a.xiso) for (int k = 0; k < a.n_iso; k++) a.xiso[(size_t)vox * a.n_iso + k] = nan;
                 } else {
                     if (its > 4 * N + 16) {          // (the last block-pivoting iterate may be infeasible: the maps get a feasible one)
                         atomicAdd(&a.c.status[ST_ITCAP], 1);
@@ -1139,6 +1145,10 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
                     if (a.c.xdbg) {
 #pragma unroll
                         for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
+                    }
+                    if (a.xiso) {                 // AMX_F_FW_ISO: what the corrected DWI needs of x, while it is in registers
+#pragma unroll
+                        for (int j = 0; j < N; j++) if (j >= n_perp && j < n_atoms) a.xiso[(size_t)vox * a.n_iso + (j - n_perp)] = x[j];
                     }
                     double x_sum = 0.0, x_perp = 0.0;
 #pragma unroll
@@ -1558,6 +1568,7 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
                 if (!(c[0] == c[0])) {
                     const double nan = __builtin_nan("");
                     for (int m = 0; m < a.n_maps; m++) e[m] = nan;
+                    if (a.xiso) for (int k = 0; k < a.n_iso; k++) a.xiso[(size_t)vox * a.n_iso + k] = nan;
                 } else {
                     if (its > 4 * N + 16) {
                         atomicAdd(&a.c.status[ST_ITCAP], 1);
@@ -1567,6 +1578,10 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
                     if (a.c.xdbg) {
 #pragma unroll
                         for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
+                    }
+                    if (a.xiso) {                 // AMX_F_FW_ISO: what the corrected DWI needs of x, while it is in registers
+#pragma unroll
+                        for (int j = 0; j < N; j++) if (j >= n_perp && j < n_atoms) a.xiso[(size_t)vox * a.n_iso + (j - n_perp)] = x[j];
                     }
                     double x_sum = 0.0, x_perp = 0.0;
 #pragma unroll

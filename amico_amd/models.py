@@ -137,6 +137,75 @@ def _verified_fit(fit):
     return wrapper
 
 
+class _LazyResults(dict):
+    """The dict a fit returns, with ONE value that is made when it is first read (FreeWater's device-resident fit holds `y_corrected`
+    this way: Evaluation.fit() builds the corrected volume on the GPU and never reads the rows).  `key in results`, `keys()`,
+    iteration and `len()` see the key from the start and make nothing; every way of reading the value -- `results[key]`, `get`, `pop`,
+    `values()`, `items()`, `copy()`, `dict(results)`, `{**results}`, `==` -- runs the thunk first, once, and keeps what it returns."""
+
+    def __init__(self, *args, **kwargs):
+        super().__init__(*args, **kwargs)
+        self._lazy = None                    # (key, thunk) until the value is made or replaced
+
+    def set_lazy(self, key, thunk):
+        dict.__setitem__(self, key, None)
+        self._lazy = (key, thunk)
+
+    def _force(self, key=None):
+        if self._lazy is not None and key in (None, self._lazy[0]):
+            (k, thunk), self._lazy = self._lazy, None
+            dict.__setitem__(self, k, thunk())
+
+    def _drop(self, key):
+        if self._lazy is not None and self._lazy[0] == key:
+            self._lazy = None
+
+    def __getitem__(self, key):
+        self._force(key)
+        return dict.__getitem__(self, key)
+
+    def __setitem__(self, key, value):
+        self._drop(key)
+        dict.__setitem__(self, key, value)
+
+    def __delitem__(self, key):
+        self._drop(key)
+        dict.__delitem__(self, key)
+
+    def __iter__(self):                      # (an overridden __iter__ also takes dict(results) / {**results} off CPython's raw-copy path: they go through keys() and [])
+        return iter(dict.keys(self))
+
+    def get(self, key, default=None):
+        self._force(key)
+        return dict.get(self, key, default)
+
+    def pop(self, key, *default):
+        self._force(key)
+        return dict.pop(self, key, *default)
+
+    def values(self):
+        self._force()
+        return dict.values(self)
+
+    def items(self):
+        self._force()
+        return dict.items(self)
+
+    def copy(self):
+        self._force()
+        return dict(dict.items(self))
+
+    def __eq__(self, other):
+        self._force()
+        return dict.__eq__(self, other)
+
+    def __ne__(self, other):
+        self._force()
+        return dict.__ne__(self, other)
+
+    __hash__ = None
+
+
 class BaseModel(ABC):
     """models.pyx:75-217"""
 
@@ -591,11 +660,29 @@ class FreeWater(BaseModel):
         lut = self._lut(evaluation, lambda: _capi.upload_freewater(ctx, evaluation.KERNELS, evaluation.htable))
         dev = getattr(evaluation, '_dev', None)
         if dev is not None:
-            est, rmse, nrmse, yc = _capi.freewater_fit_device(
+            # doSaveCorrectedDWI asks the fit for the isotropic coefficients only (AMX_F_FW_ISO: the fit stays on its fast kernel and reads
+            # the float32 signals in place); Evaluation.fit makes the corrected volume from them on the GPU, and the rows
+            # results['y_corrected'] (models.pyx:1264-1274) are made by the same kernel if somebody reads them
+            want_yc = bool(self.configs['save_corrected_DWI'])
+            out = _capi.freewater_fit_device(
                 ctx, lut, dev['y'], self._dev_dirs(evaluation, dev), self.solver_params['lambda1'], self.solver_params['lambda2'],
-                self.type == 'Mouse', rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']),
-                corrected=bool(self.configs['save_corrected_DWI']))
-            return self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse, 'y_corrected': yc})
+                self.type == 'Mouse', rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']), iso=want_yc)
+            est, rmse, nrmse = out[:3]
+            results = _LazyResults(self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse}))
+            if want_yc:
+                d_y, x_iso = dev['y'], out[-1]
+                dev['out']['x_iso'], dev['lut'] = x_iso, lut
+
+                def rows():
+                    # (the thunk keeps y, x_iso and the dictionary alive as long as the dict lives unread; what it cannot keep is the context)
+                    if getattr(ctx, '_h', None) is None or getattr(lut, '_h', None) is None:
+                        raise RuntimeError("results['y_corrected'] of this fit was not read before its GPU context / dictionary was closed "
+                                           "(reset_context()): read it first, or fit again")
+                    yc = _capi.freewater_corrected_device(ctx, lut, d_y, x_iso)
+                    ctx.sync()
+                    return yc.cpu().numpy()
+                results.set_lazy('y_corrected', rows)
+            return results
         kw = dict(rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']), corrected=bool(self.configs['save_corrected_DWI']))
         mouse = self.type == 'Mouse'
         if len(get_contexts()) > 1:

@@ -6,7 +6,9 @@
                                         AND the principal directions (log-linear tensor fit)            core.py:428-436, 456-458
     amx_sanitize_device_f32             NaN / Inf values of y replaced (optional: replace_bad_voxels)     core.py:270-274
     amx_noddi_fit_device        NNLS -> LASSO -> NNLS, maps                                        models.pyx:816-991
+      | amx_freewater_fit_device  lasso, maps (+ the isotropic coefficients, AMX_F_FW_ISO)           models.pyx:1168-1286
     amx_prep_scatter_device     maps / directions into float32 volumes                             core.py:472-498
+    amx_prep_corrected_device   FreeWater: the corrected DWI volume (optional: corrected)          models.pyx:1264-1274, core.py:488-498
 
 Everything is enqueued on one HIP stream; the only host synchronisation is `amx_sync_status` at the end.  torch is
 used for device buffers only.  `amico_amd.core.Evaluation` is the host-array (numpy in / numpy out) face of the
@@ -18,14 +20,11 @@ from . import _capi, dti as _dti, prep as _prep
 from .models import get_context
 
 
-class NoddiVolumePipeline:
-    def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
-                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None):
-        """replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
-        the scan of the image ahead of everything else and the scan of y behind the gather, both replacing what they find, on
-        the same stream and without a host wait; run() then leaves the two counts in `bad_samples` (image) and
-        `bad_samples_preprocessed` (y).  With fused=True the gather computes the directions in the same kernel as y, so the
-        directions of a voxel whose y is replaced afterwards come from the unreplaced values (fused=False fits them from the replaced y)."""
+class _VolumePipeline:
+    """what the model pipelines share: the plan, the buffers of the prepared signals and the directions, the chain up to the fit
+    (scan, debias, gather + directions, scan of y) and run()"""
+
+    def _setup(self, scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels):
         import torch
         self.fused = bool(fused)           # False: gather, then the tensor fit as its own pass over y (the round-4 chain; A/B)
         self.torch = torch
@@ -40,22 +39,21 @@ class NoddiVolumePipeline:
         if b0_min_signal != 0.0:
             raise NotImplementedError('b0_min_signal needs the whole-volume b0 mean on the host: use Evaluation')
         self.tensor = _dti.TensorDirections.from_scheme(scheme, ctx=self.ctx)
-        self.lut = _capi.upload_noddi(self.ctx, kernels, htable, scheme.dwi_idx)
-        self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
+
+    def _buffers(self, n_maps):
+        torch = self.torch
         n = self.prep.n_vox
-        self.n_vox, self.shape = n, tuple(img_like.shape[:3])
+        self.n_vox = n
         f64 = dict(dtype=torch.float64, device=self.dev)
-        self.y = torch.empty((n, scheme.nS), dtype=torch.float32, device=self.dev)      # float32 like the image (core.py:136)
+        self.y = torch.empty((n, self.scheme.nS), dtype=torch.float32, device=self.dev)      # float32 like the image (core.py:136)
         self.dirs = torch.empty((n, 3), **f64)
-        self.est = torch.empty((n, 3), **f64)
+        self.est = torch.empty((n, n_maps), **f64)
         self.mean_b0 = torch.empty(n, dtype=torch.float32, device=self.dev)
-        self.maps = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
+        self.maps = torch.empty(self.shape + (n_maps,), dtype=torch.float32, device=self.dev)
         self.dirs_vol = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
 
-    def enqueue(self, d_img, stream=None):
-        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`); with debias_snr
-        set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere; with replace_bad_voxels set its
-        NaN / Inf samples are overwritten before that"""
+    def _enqueue_signals(self, d_img, stream):
+        """image -> y, mean_b0, dirs (everything ahead of the model fit)"""
         L, c, p = _capi.lib(), self.ctx, self.prep._plan
         s = _capi.c_vp(stream or 0)
         r = self.replace_bad_voxels
@@ -75,9 +73,11 @@ class NoddiVolumePipeline:
             self.tensor.fit_device(self.y.data_ptr(), self.n_vox, self.dirs.data_ptr(), stream, f32=True)
         if r is not None and self.fused:
             _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
-        c.check(L.amx_noddi_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox,
-                                       self.lambda1, self.lambda2, 0, self.est.data_ptr(), None, None, None, s))
-        c.check(L.amx_prep_scatter_device(c._h, p._h, self.est.data_ptr(), 3, self.maps.data_ptr(), s))
+
+    def _enqueue_scatter(self, stream):
+        L, c, p = _capi.lib(), self.ctx, self.prep._plan
+        s = _capi.c_vp(stream or 0)
+        c.check(L.amx_prep_scatter_device(c._h, p._h, self.est.data_ptr(), self.est.shape[1], self.maps.data_ptr(), s))
         c.check(L.amx_prep_scatter_device(c._h, p._h, self.dirs.data_ptr(), 3, self.dirs_vol.data_ptr(), s))
 
     def run(self, d_img, stream=None):
@@ -87,3 +87,72 @@ class NoddiVolumePipeline:
             # the chain's two scans are the last two sanitize calls of the context: image first, y second
             self.bad_samples, self.bad_samples_preprocessed = self.ctx.sanitize_previous(), self.ctx.sanitize_last()
         return self.maps, self.dirs_vol
+
+
+class NoddiVolumePipeline(_VolumePipeline):
+    def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None):
+        """replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
+        the scan of the image ahead of everything else and the scan of y behind the gather, both replacing what they find, on
+        the same stream and without a host wait; run() then leaves the two counts in `bad_samples` (image) and
+        `bad_samples_preprocessed` (y).  With fused=True the gather computes the directions in the same kernel as y, so the
+        directions of a voxel whose y is replaced afterwards come from the unreplaced values (fused=False fits them from the replaced y)."""
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels)
+        self.lut = _capi.upload_noddi(self.ctx, kernels, htable, scheme.dwi_idx)
+        self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
+        self.shape = tuple(img_like.shape[:3])
+        self._buffers(3)
+
+    def enqueue(self, d_img, stream=None):
+        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`); with debias_snr
+        set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere; with replace_bad_voxels set its
+        NaN / Inf samples are overwritten before that"""
+        L, c = _capi.lib(), self.ctx
+        s = _capi.c_vp(stream or 0)
+        self._enqueue_signals(d_img, stream)
+        c.check(L.amx_noddi_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox,
+                                       self.lambda1, self.lambda2, 0, self.est.data_ptr(), None, None, None, s))
+        self._enqueue_scatter(stream)
+
+
+class FreeWaterVolumePipeline(_VolumePipeline):
+    def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.0, lambda2=1e-3, do_normalize=True,
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None,
+                 corrected=False, keep_b0=False, is_mouse=False):
+        """The chain of NoddiVolumePipeline (same arguments, same meaning) with the Free-Water fit: leaves `maps` [X, Y, Z, 2 | 4 (Mouse)]
+        and `dirs_vol` in HBM.  corrected=True (doSaveCorrectedDWI): also `corrected` [X, Y, Z, nS], the free-water-corrected DWI of
+        core.py:488-498 -- rescaled by the b0 mean when do_normalize is set; keep_b0=True (doKeepb0Intact) leaves its b0 volumes
+        as they were.  The fit stays on its fast kernel: it hands over the isotropic coefficients only (AMX_F_FW_ISO)."""
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels)
+        self.lut = _capi.upload_freewater(self.ctx, kernels, htable)
+        self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
+        self.is_mouse = bool(is_mouse)
+        self.shape = tuple(img_like.shape[:3])
+        self._buffers(4 if self.is_mouse else 2)
+        torch = self.torch
+        self.want_corrected = bool(corrected)
+        self.b0_cols = np.asarray(scheme.b0_idx, dtype=np.int32) if (keep_b0 and scheme.b0_count > 0) else np.zeros(0, dtype=np.int32)
+        self.x_iso = self.corrected = None
+        if self.want_corrected:
+            self.x_iso = torch.empty((self.n_vox, self.lut.n_iso), dtype=torch.float64, device=self.dev)
+            self.corrected = torch.empty(self.shape + (scheme.nS,), dtype=torch.float32, device=self.dev)
+
+    def enqueue(self, d_img, stream=None):
+        """d_img: as for NoddiVolumePipeline.enqueue"""
+        L, c, p = _capi.lib(), self.ctx, self.prep._plan
+        s = _capi.c_vp(stream or 0)
+        self._enqueue_signals(d_img, stream)
+        flags = 0
+        if self.want_corrected:
+            c.check(L.amx_set_fw_iso(c._h, self.x_iso.data_ptr()))
+            flags = _capi.F_FW_ISO
+        try:
+            c.check(L.amx_freewater_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox, self.lambda1,
+                                                   self.lambda2, int(self.is_mouse), flags, self.est.data_ptr(), None, None, None, s))
+        finally:
+            if self.want_corrected:
+                L.amx_set_fw_iso(c._h, None)
+        self._enqueue_scatter(stream)
+        if self.want_corrected:
+            rescale = self.prep.do_normalize and self.scheme.b0_count > 0
+            p.corrected_device(self.lut, self.y, self.x_iso, self.corrected, self.mean_b0 if rescale else None, self.b0_cols, stream)

@@ -37,6 +37,7 @@ extern "C" {
 #define AMX_F_MODULATED     4u  /* doSaveModulatedMaps  -> out_mod    f64[n_vox][2]   */
 #define AMX_F_CORRECTED     8u  /* doSaveCorrectedDWI   -> out_ycorr  f64[n_vox][nS]  */
 #define AMX_F_DEBUG_X      16u  /* solver coefficients  -> the buffer registered with amx_set_debug_x */
+#define AMX_F_FW_ISO       32u  /* FreeWater only: the isotropic coefficients -> the buffer registered with amx_set_fw_iso */
 
 typedef struct amx_ctx amx_ctx;   /* one per process+GPU: stream-ordered workspace, error state */
 typedef struct amx_lut amx_lut;   /* device-resident dictionary (KERNELS) of one model          */
@@ -171,7 +172,7 @@ int amx_sandi_fit_device(amx_ctx *ctx, const amx_lut *lut, const double *d_y, in
 /* The same with float32 signals in HBM -- the dtype the image has before core.py:451-452 widen it (core.py:136: float32), so
  * the maps are bit-identical to the float64 calls on the widened values.  NODDI (A'y GEMM, left-over kernels), every
  * wavefront-per-voxel kernel, CylinderZeppelinBall and FreeWater's matrix-core projection read the float32 rows in place (FreeWater:
- * 260 instead of 520 bytes per voxel); for the remaining lane kernels (FreeWater with error maps / corrected signal, SANDI) a float64
+ * 260 instead of 520 bytes per voxel); for the remaining lane kernels (FreeWater with error maps / AMX_F_CORRECTED, SANDI) a float64
  * copy is made on the device first.                                                                                            */
 int amx_noddi_fit_device_f32(amx_ctx *ctx, const amx_lut *lut, const float *d_y, const double *d_dirs,
                              int64_t n_vox, double lambda1, double lambda2, unsigned flags,
@@ -197,6 +198,27 @@ int amx_sync_status(amx_ctx *ctx, void *hip_stream);
  *   FreeWater  f64[n_vox][n_atoms]    the lasso solution (models.pyx:1238)
  *   SANDI      f64[n_vox][n_atoms]    the lasso solution rescaled by KERNELS['norms'] (models.pyx:1570-1571)   */
 int amx_set_debug_x(amx_ctx *ctx, double *d_x);
+
+/* ---- FreeWater's corrected DWI (models.pyx:1264-1274, core.py:488-498) without the fit leaving its fast kernels:
+ *     y_corrected[i, j] = max(0, y[i, j] - sum_k CSF[k, j] x[i, n_perp + k])
+ * needs only the one (Human) or two (Mouse) isotropic coefficients of each voxel.  A FreeWater fit whose flags carry AMX_F_FW_ISO
+ * writes them -- entries n_perp .. n_atoms - 1 of the lasso solution, as the solver leaves them, before the maps normalise anything --
+ * into d_xiso f64[n_vox][n_iso] at the voxel's own index (a DEVICE buffer the caller owns; NULL unregisters; a host-buffer call offsets
+ * it per batch like the AMX_F_DEBUG_X buffer).  A voxel with a non-finite signal gets NaN, one skipped for an out-of-bounds direction 0,
+ * as their maps do.  The flag selects no path: every kernel that writes FreeWater maps writes the coefficients, so a float32 fit
+ * with it still runs k_freewater_fused in place on the float32 signals (AMX_F_CORRECTED keeps its own, slower route).  The flag without
+ * a registered buffer, or on a fit of another model, is AMX_E_BADARG. */
+int amx_set_fw_iso(amx_ctx *ctx, double *d_xiso);
+/* The corrected signal from y and x_iso: one streaming kernel, lanes along the flattened (voxel, volume) index so that reads of y and
+ * writes of the result are whole lines and voxels of few volumes share a wavefront.  Per sample, fp64 in the reference's order with
+ * separately rounded products and sums (no fused multiply-add: the result equals the elementwise numpy expression bit for bit):
+ *     fw = 0; for k: fw += (double)CSF[k][j] * x_iso[r][k];   yc = (double)y[r][j] - fw;   yc = yc < 0 ? 0 : yc   (NaN stays NaN)
+ * CSF = the isotropic columns of the dictionary `lut` holds (at most 8).  Device pointers, enqueued on hip_stream, no synchronisation.
+ * rows form:   d_y32 f32[n_vox][nS] or d_y64 f64[n_vox][nS] (exactly one is not NULL) -> d_ycorr f64[n_vox][nS]: what AMX_F_CORRECTED
+ *              writes, one coalesced row per voxel. */
+int amx_freewater_corrected_device(amx_ctx *ctx, const amx_lut *lut, const float *d_y32, const double *d_y64, const double *d_xiso,
+                                   int64_t n_vox, double *d_ycorr, void *hip_stream);
+/* (volume form: amx_prep_corrected_device, beside amx_prep_scatter_device below) */
 
 /* ---- diagnosis / tests of the support seeds (csrc/amx_seed.hpp; no counterpart in the reference): copies a workspace
  * buffer of the LAST NODDI fit of this ctx -- which = 0: voxel permutation int32[n] (bucket order), 1: projected signals
@@ -335,6 +357,15 @@ int amx_prep_mean_b0_device(amx_ctx *ctx, const amx_prep *p, const float *d_img,
 int amx_prep_scatter(amx_ctx *ctx, const amx_prep *p, const double *values, int n_cols, float *out_volume);
 int amx_prep_scatter_device(amx_ctx *ctx, const amx_prep *p, const double *d_values, int n_cols,
                             float *d_volume, void *hip_stream);
+/* FreeWater's corrected DWI, volume form (rows form, arithmetic: amx_freewater_corrected_device): RESULTS['DWI_corrected'] of
+ *              core.py:488-498 -> d_volume f32[X][Y][Z][n_out] (C order; n_out = the plan's prepared
+ *              volumes = the dictionary's nS; d_y32 / d_xiso rows in the plan's masked order).  A masked voxel of rank r gets
+ *              out[j] = (float)(m * yc) with m = (double)d_mean_b0[r], or 1 when d_mean_b0 is NULL (core.py:493-494); the columns listed
+ *              in b0_cols (HOST int32[n_b0_cols], at most 128; 0 = none) get (float)((double)y[r][j] * m) instead (doKeepb0Intact,
+ *              core.py:495-496); every other voxel gets zeros from this same kernel: each element of the volume is written exactly
+ *              once and no memset precedes it. */
+int amx_prep_corrected_device(amx_ctx *ctx, const amx_prep *p, const amx_lut *lut, const float *d_y32, const double *d_xiso,
+                              const float *d_mean_b0, const int32_t *b0_cols, int n_b0_cols, float *d_volume, void *hip_stream);
 
 /* (f0) Rician debias of the raw signal, core.py:201-206 (doDebiasSignal, DWI-SNR) -> preproc.py:23-36 `debiasRician`:
  *     per voxel with mask != 0:  sigma = DWI[ix,iy,iz,b0_idx].mean() / SNR;  E = argmin_E sum_i (S_i - mu(E_i))^2  from E = S,
