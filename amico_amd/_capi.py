@@ -13,6 +13,9 @@ LIB_PATH = os.environ.get('AMICO_AMD_LIB') or os.path.join(_HERE, 'csrc', 'libam
 
 AMX_OK, AMX_E_BADARG, AMX_E_HIP, AMX_E_DIR_OOB, AMX_E_OVERFLOW, AMX_E_NODEVICE = 0, -1, -2, -3, -4, -5
 F_RMSE, F_NRMSE, F_MODULATED, F_CORRECTED, F_DEBUG_X, F_FW_ISO = 1, 2, 4, 8, 16, 32
+# AMX_T_*: the stored dtypes amx_prep_ingest* converts to float32 on the GPU
+RAW_DTYPES = {np.dtype(np.uint8): 1, np.dtype(np.int16): 2, np.dtype(np.uint16): 3, np.dtype(np.int32): 4, np.dtype(np.float32): 5,
+              np.dtype(np.float64): 6}
 
 # every symbol include/amico_amd.h declares (tests check that the library exports them all)
 SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxels', 'amx_ctx_create', 'amx_ctx_destroy', 'amx_last_error',
@@ -29,6 +32,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
+           'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device']
 
@@ -186,6 +190,8 @@ def lib():
     L.amx_sanitize.argtypes = [c_vp, c_dp, C.c_int64, C.c_int, C.c_double, C.POINTER(C.c_int64)]
     L.amx_sanitize_last.argtypes = [c_vp, C.POINTER(C.c_int64)]
     L.amx_sanitize_previous.argtypes = [c_vp, C.POINTER(C.c_int64)]
+    L.amx_prep_ingest_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, c_vp, c_vp]   # ctx, plan, raw, dtype, slope, inter, replace, value, img, stream
+    L.amx_prep_ingest.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, c_fp, C.POINTER(C.c_int64)]
     L.amx_lut_resample.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     L.amx_lut_rotate_resample.argtypes = [c_vp, c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     for name in SYMBOLS:
@@ -838,6 +844,32 @@ class Prep:
         """device pointer (int) of the image's element buffer, enqueued on `stream`; the count: Context.sanitize_last()"""
         self.ctx.check(lib().amx_prep_sanitize_device(self.ctx._h, self._h, c_vp(d_img), int(replace is not None), _replacement(replace, np.float32),
                                                       c_vp(stream or 0)))
+
+    def _raw_buffer(self, raw):
+        """the image in its stored dtype as the flat element buffer the plan's strides refer to, counted in its own elements"""
+        if raw.dtype not in RAW_DTYPES or raw.shape != self.shape or tuple(s // raw.itemsize for s in raw.strides) != self.strides \
+                or any(s % raw.itemsize for s in raw.strides):
+            raise ValueError('raw image does not match the plan (one of uint8 / int16 / uint16 / int32 / float32 / float64, shape, strides)')
+        return np.lib.stride_tricks.as_strided(raw, shape=(self.extent,), strides=(raw.itemsize,))
+
+    def ingest_device(self, d_raw, raw_dtype, d_img, scaling=None, replace=None, stream=None):
+        """device pointers (ints): the image in its stored dtype (the plan's element strides) -> the float32 image of core.py:136, NaN / Inf
+        scan and replacement included (amx_prep_ingest_device); enqueued on `stream`; the count: Context.sanitize_last().
+        scaling: (slope, inter) of the NIfTI header or None; a layout that cannot be streamed is a ValueError"""
+        slope, inter = (1.0, 0.0) if scaling is None else scaling
+        self.ctx.check(lib().amx_prep_ingest_device(self.ctx._h, self._h, c_vp(d_raw), RAW_DTYPES[np.dtype(raw_dtype)], float(slope), float(inter),
+                                                    int(replace is not None), _replacement(replace, np.float32), c_vp(d_img), c_vp(stream or 0)))
+
+    def ingest(self, raw, scaling=None, replace=None):
+        """host image in its stored dtype -> (float32 image in the same layout, number of NaN / Inf samples found) (amx_prep_ingest)"""
+        buf = self._raw_buffer(raw)
+        slope, inter = (1.0, 0.0) if scaling is None else scaling
+        flat = np.empty(self.extent, dtype=np.float32)
+        out = C.c_int64()
+        self.ctx.check(lib().amx_prep_ingest(self.ctx._h, self._h, buf.ctypes.data_as(c_vp), RAW_DTYPES[raw.dtype], float(slope), float(inter),
+                                             int(replace is not None), _replacement(replace, np.float32), _p(flat, c_fp), C.byref(out)))
+        img = np.lib.stride_tricks.as_strided(flat, shape=self.shape, strides=tuple(4 * s for s in self.strides))
+        return img, int(out.value)
 
     def corrected_device(self, lut, y_t, xiso_t, volume_t, mean_b0_t=None, b0_cols=(), stream=None):
         """RESULTS['DWI_corrected'] (core.py:488-498) in HBM: y f32 [n_vox, n_out], x_iso f64 [n_vox, n_iso] (rows in the plan's masked

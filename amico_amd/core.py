@@ -2,8 +2,9 @@
 ``DIRs``, ``htable``, ``KERNELS``, ``nthreads``, ``get_config`` -- and the caller contract around the hot path for
 in-memory volumes, every per-voxel step on the GPU:
 
-  set_data   ~ load_data's preprocessing inputs (core.py:201-268): raw float32 image, scheme, mask
-  fit        NaN / Inf scan of the raw image, replacement with replace_bad_voxels (core.py:152-158)    (amx_prep_sanitize);
+  set_data   ~ load_data's preprocessing inputs (core.py:201-268): raw image (float32, or as it is stored + the NIfTI scaling), scheme, mask
+  fit        an image kept in its stored dtype -> float32 in HBM (core.py:136), the scan below in the same kernel (amx_prep_ingest);
+             NaN / Inf scan of the raw image, replacement with replace_bad_voxels (core.py:152-158)    (amx_prep_sanitize);
              CONFIG['bad_samples_raw'] = samples found; the same for ``y`` after the gather (core.py:270-276) (amx_sanitize),
              CONFIG['bad_samples_preprocessed']
              Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
@@ -29,6 +30,8 @@ from .synthetic import SimpleScheme
 
 class Evaluation:
     def __init__(self, study_path='.', subject='.', output_path=None):
+        self._raw = None              # the image as set_data received it, when fit() uploads it in its stored dtype
+        self._raw_scaling = None
         self.niiDWI_img = None
         self.scheme = None
         self.niiMASK_img = None
@@ -62,6 +65,19 @@ class Evaluation:
         self.set_config('DTI_fit_method', 'OLS')
         self.set_config('BLAS_nthreads', 1)
 
+    # `niiDWI_img` (core.py:136) is the raw float32 image.  When set_data kept the image in its stored dtype the float32 array is made
+    # on first read, by the numpy expression the ingest kernel is held to, and cached; fit() itself never needs it
+    @property
+    def niiDWI_img(self):
+        if self._img32 is None and self._raw is not None:
+            self._img32 = _prep.to_float32(self._raw, self._raw_scaling)
+        return self._img32
+
+    @niiDWI_img.setter
+    def niiDWI_img(self, value):
+        self._img32 = value
+        self._raw = self._raw_scaling = None              # an image assigned by the caller is the float32 image from here on
+
     # `y` / `DIRs` (core.py:451-458) are produced on the GPU by fit() and stay there for model.fit (self._dev); the
     # numpy arrays the reference exposes are fetched on first access
     @property
@@ -94,7 +110,7 @@ class Evaluation:
         return self.CONFIG.get(key)
 
     # ---- in-memory replacement of load_data (core.py:107-278): volumes are given directly
-    def set_data(self, dwi, scheme, mask=None, directions=None, b0_min_signal=0, replace_bad_voxels=None):
+    def set_data(self, dwi, scheme, mask=None, directions=None, b0_min_signal=0, replace_bad_voxels=None, scaling=None):
         """dwi [X,Y,Z,nS] raw signal (C or Fortran order), mask [X,Y,Z], directions [X,Y,Z,3] (optional peaks,
         core.py:438-447: when absent they come from the tensor fit).  The options doDebiasSignal / DWI-SNR /
         doNormalizeSignal / doMergeB0 / doDirectionalAverage are read here, like load_data reads them.
@@ -109,8 +125,15 @@ class Evaluation:
         Two deliberate differences from load_data: (1) the second check covers the rows of the masked voxels, not the whole
         pre-processed image -- nothing outside the mask reaches a result; (2) it runs after the gather's clip (core.py:452), so a
         -Inf has already become 0 like every negative sample where the reference would flag it first (-Inf can only come from
-        float32 overflow in the normalisation of a negative sample)."""
+        float32 overflow in the normalisation of a negative sample).
+        scaling: (scl_slope, scl_inter) of the NIfTI header when `dwi` holds the stored values; None, or a slope of None as nibabel
+        reports an unscaled image, means none.  An image of dtype uint8 / int16 / uint16 / int32 / float64 (or float32 with a scaling)
+        in C or Fortran order is kept as it is: fit() uploads those bytes and its first kernel makes the float32 image of
+        core.py:136 in HBM -- np.float32(dwi), or np.float32(np.float64(dwi) * slope + inter) as nibabel scales -- bit for bit, and
+        scans it in the same pass.  `niiDWI_img` is then made by that numpy expression when it is first read.  Any other dtype or
+        layout is converted here, on the host, by the same expression.  float32 without scaling is uploaded as it is."""
         _prep.check_replace_bad_voxels(replace_bad_voxels)                       # before any context is made or anything uploaded
+        scaling = _prep.check_scaling(scaling)
         self.set_config('replace_bad_voxels', replace_bad_voxels)               # core.py:134
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
@@ -124,16 +147,21 @@ class Evaluation:
         img = np.asarray(dwi)
         if img.ndim != 4:
             raise ValueError('DWI file is not a 4D image')                       # core.py:138-139
-        self.niiDWI_img = img.astype(np.float32, copy=False)                     # core.py:136
-        if any(st % 4 or st <= 0 for st in self.niiDWI_img.strides):
-            self.niiDWI_img = np.ascontiguousarray(self.niiDWI_img)
-        self.set_config('dim', self.niiDWI_img.shape[:3])
+        if (img.dtype != np.float32 or scaling is not None) and _prep.streamable(img):
+            self.niiDWI_img = None
+            self._raw, self._raw_scaling = img, scaling                          # as stored: no float32 copy on the host
+        else:
+            self.niiDWI_img = _prep.to_float32(img, scaling)                     # core.py:136
+            if any(st % 4 or st <= 0 for st in self.niiDWI_img.strides):
+                self.niiDWI_img = np.ascontiguousarray(self.niiDWI_img)
+            img = self.niiDWI_img
+        self.set_config('dim', img.shape[:3])
         self.set_config('b0_min_signal', b0_min_signal)
-        if scheme.nS != self.niiDWI_img.shape[3]:
+        if scheme.nS != img.shape[3]:
             raise ValueError('Scheme does not match with DWI data')
-        self.niiMASK_img = np.ones(self.niiDWI_img.shape[:3], dtype=np.uint8) if mask is None \
+        self.niiMASK_img = np.ones(img.shape[:3], dtype=np.uint8) if mask is None \
             else np.asarray(mask, dtype=np.uint8)
-        if self.niiMASK_img.shape != self.niiDWI_img.shape[:3]:
+        if self.niiMASK_img.shape != img.shape[:3]:
             raise ValueError('MASK geometry does not match with DWI data')
         if directions is not None and (np.ndim(directions) != 4 or np.shape(directions)[:3] != self.niiMASK_img.shape
                                        or np.shape(directions)[3] < 3):
@@ -142,9 +170,10 @@ class Evaluation:
         self._dirs_img = None if directions is None else np.ascontiguousarray(np.asarray(directions, dtype=np.float32)[..., :3])   # core.py:442
         self._raw_scheme = scheme
         self._prep = _prep.SignalPreparation(
-            scheme, self.niiDWI_img, self.niiMASK_img, do_normalize=self.get_config('doNormalizeSignal'),
+            scheme, img, self.niiMASK_img, do_normalize=self.get_config('doNormalizeSignal'),
             do_merge_b0=self.get_config('doMergeB0'), do_directional_average=self.get_config('doDirectionalAverage'),
-            b0_min_signal=b0_min_signal, debias_snr=debias_snr, replace_bad_voxels=replace_bad_voxels)
+            b0_min_signal=b0_min_signal, debias_snr=debias_snr, replace_bad_voxels=replace_bad_voxels,
+            scaling=scaling if self._raw is not None else None)
         # the scheme the model sees: one row per shell after the directional average (core.py:254-255)
         self.scheme = SimpleScheme(_prep.directional_average_table(scheme), scheme.b0_thr) \
             if self.get_config('doDirectionalAverage') else scheme
@@ -211,7 +240,7 @@ class Evaluation:
         self.set_config('load_kernels_time', time.time() - t)
 
     def fit(self):
-        if self.niiDWI_img is None:
+        if self._raw is None and self._img32 is None:
             raise RuntimeError('Data not loaded; call "set_data()" first')
         if self.model is None:
             raise RuntimeError('Model not set; call "set_model()" first')
@@ -229,14 +258,23 @@ class Evaluation:
         L, ctx, plan = _capi.lib(), self._prep.ctx, self._prep._plan
         t = time.time()
         # ---- raw image -> HBM once; everything up to the map volumes stays there (one stream, default)
-        img = self.niiDWI_img
-        d_img = torch.from_numpy(np.lib.stride_tricks.as_strided(img, shape=(plan.extent,), strides=(4,))).to(dev)
+        raw = self._raw
+        shape3 = self.niiMASK_img.shape
         n = self._prep.n_vox
         # core.py:152-158: the first kernel of the chain; its count comes home before anything else is enqueued (one small wait), so
         # that nothing downstream ever reads a NaN / Inf image.  A refusal leaves RESULTS and the device state as they were.
         bad_value = self.get_config('replace_bad_voxels')
-        plan.sanitize_device(d_img.data_ptr(), bad_value)
+        if raw is not None:
+            # the bytes as they are stored cross the link; core.py:136 and the scan are one kernel, and no separate scan follows
+            d_raw = torch.from_numpy(plan._raw_buffer(raw).view(np.uint8)).to(dev)
+            d_img = torch.empty(plan.extent, dtype=torch.float32, device=dev)
+            plan.ingest_device(d_raw.data_ptr(), raw.dtype, d_img.data_ptr(), self._raw_scaling, bad_value)
+        else:
+            img = self._img32
+            d_img = torch.from_numpy(np.lib.stride_tricks.as_strided(img, shape=(plan.extent,), strides=(4,))).to(dev)
+            plan.sanitize_device(d_img.data_ptr(), bad_value)
         self.set_config('bad_samples_raw', ctx.sanitize_last())
+        d_raw = None
         _prep.refuse_or_warn(self.get_config('bad_samples_raw'), bad_value, _prep.BAD_RAW)
         if self._prep.debias_snr is not None:
             # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
@@ -247,7 +285,7 @@ class Evaluation:
         d_mb0 = torch.empty(n, dtype=torch.float32, device=dev)
         thr = 0.0
         if self._prep.do_normalize and self._prep.b0_min_signal != 0.0:              # core.py:217
-            d_vol = torch.empty(img.shape[:3], dtype=torch.float32, device=dev)
+            d_vol = torch.empty(shape3, dtype=torch.float32, device=dev)
             ctx.check(L.amx_prep_mean_b0_device(ctx._h, plan._h, d_img.data_ptr(), d_vol.data_ptr(), None))
             mean_b0s = d_vol.cpu().numpy()
             thr = float(self._prep.b0_min_signal * mean_b0s[mean_b0s > 0].mean())
@@ -301,7 +339,7 @@ class Evaluation:
             if t_ is None:
                 return self._prep.scatter(host_values)
             k = 1 if t_.dim() == 1 else t_.shape[1]
-            vol = torch.empty(img.shape[:3] + (k,), dtype=torch.float32, device=dev)
+            vol = torch.empty(shape3 + (k,), dtype=torch.float32, device=dev)
             ctx.check(L.amx_prep_scatter_device(ctx._h, plan._h, t_.data_ptr(), k, vol.data_ptr(), None))
             ctx.sync()
             v = vol.cpu().numpy()
@@ -328,7 +366,7 @@ class Evaluation:
             if x_iso is not None and not (keep_b0 and self.scheme.b0_count > 128):
                 # the fit left the isotropic coefficients in HBM: y, x_iso (and mean_b0) -> the float32 volume in one kernel, one copy home;
                 # neither y nor the rows results['y_corrected'] come to the host (amx_prep_corrected_device)
-                vol = torch.empty(img.shape[:3] + (self._prep.n_out,), dtype=torch.float32, device=dev)
+                vol = torch.empty(shape3 + (self._prep.n_out,), dtype=torch.float32, device=dev)
                 plan.corrected_device(self._dev['lut'], self._dev['y'], x_iso, vol, self._dev['mb0'] if rescale else None,
                                       b0_idx if keep_b0 else ())
                 ctx.sync()

@@ -14,7 +14,7 @@
 // launch function zeroes on the same stream and copies to pinned host memory behind the kernel.  The ctx keeps two counters with an event each and alternates between them, so the counts
 // of the last TWO calls can be read (amx_sanitize_last / amx_sanitize_previous): a chain enqueues the image scan and the scan of y on
 // one stream and reads both after its only wait.
-#include "amx_host.hpp"
+#include "amx_sanitize.hpp"
 #include <cmath>
 
 namespace amx {
@@ -30,21 +30,6 @@ template <> struct SanBits<double> {
     static constexpr U kExp = 0x7ff0000000000000ull;
     static constexpr int kPerVec = 2;
 };
-
-// block sum of per-lane counts -> one atomicAdd (none when the block found nothing)
-__device__ __forceinline__ void san_block_add(unsigned int mine, unsigned long long *counter)
-{
-    __shared__ unsigned int part[4];
-    unsigned int w = mine;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) w += __shfl_down(w, off, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned long long tot = (unsigned long long)part[0] + part[1] + part[2] + part[3];
-        if (tot) atomicAdd(counter, tot);
-    }
-}
 
 // one element through its integer pattern; returns 1 when it was bad (and has been replaced when asked to)
 template <typename U>
@@ -134,41 +119,6 @@ using namespace amx;
 
 namespace {
 
-// the counter and the event of this call; the launch function zeroes the counter on the call's stream
-int san_begin(amx_ctx *ctx, hipStream_t s, unsigned long long **counter)
-{
-    if (!ctx->san_count) {
-        HIPCHK(ctx, hipMalloc((void **)&ctx->san_count, 2 * sizeof(unsigned long long)));
-        HIPCHK(ctx, hipHostMalloc((void **)&ctx->san_host, 2 * sizeof(unsigned long long)));
-        ctx->san_host[0] = ctx->san_host[1] = 0;
-        for (int k = 0; k < 2; k++) HIPCHK(ctx, hipEventCreateWithFlags(&ctx->san_ev[k], hipEventDisableTiming));
-    }
-    const int slot = (int)(ctx->san_seq & 1u);
-    *counter = ctx->san_count + slot;
-    HIPCHK(ctx, hipMemsetAsync(*counter, 0, sizeof(unsigned long long), s));
-    return AMX_OK;
-}
-
-int san_end(amx_ctx *ctx, hipStream_t s, const char *kernel)
-{
-    HIPCHK(ctx, hipGetLastError());
-    // the count goes home behind the kernel, into pinned memory: reading it is a wait for the event and a load, not a blocking copy
-    const unsigned slot = ctx->san_seq & 1u;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->san_host + slot, ctx->san_count + slot, sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    HIPCHK(ctx, hipEventRecord(ctx->san_ev[slot], s));      // amx_sanitize_last waits for this, not for the caller's stream
-    ctx->san_seq++;
-    amx_note(ctx, kernel);
-    return AMX_OK;
-}
-
-unsigned san_grid(const amx_ctx *ctx, long long items)
-{
-    long long grid = (items + 255) / 256;
-    const long long cap = (long long)ctx->n_cu * 8;
-    if (grid > cap) grid = cap;
-    return (unsigned)(grid < 1 ? 1 : grid);
-}
-
 template <typename T>
 int sanitize_flat(amx_ctx *ctx, T *d_buf, int64_t count, int replace, T value, hipStream_t s, const char *who)
 {
@@ -191,24 +141,6 @@ int sanitize_flat(amx_ctx *ctx, T *d_buf, int64_t count, int replace, T value, h
         hipLaunchKernelGGL((k_sanitize_flat<T>), dim3(san_grid(ctx, (nvec + 3) / 4)), dim3(256), 0, s, d_buf, head, nvec, tail, replace ? 1 : 0, vb, counter);
     }
     return san_end(ctx, s, who);
-}
-
-// the four (extent, stride) pairs of a plan's image sorted by stride, axes of extent 1 dropped; dense: together they tile a contiguous block
-bool san_axes(const amx_prep *p, long long d[4], long long st[4])
-{
-    long long dd[4] = {p->d[0], p->d[1], p->d[2], (long long)p->nS}, ss[4] = {p->s[0], p->s[1], p->s[2], p->sv};
-    int n = 0;
-    for (int k = 0; k < 4; k++) {
-        if (dd[k] == 1) continue;
-        int j = n++;
-        for (; j > 0 && st[j - 1] > ss[k]; j--) { st[j] = st[j - 1]; d[j] = d[j - 1]; }
-        st[j] = ss[k]; d[j] = dd[k];
-    }
-    bool dense = true;
-    long long expect = 1;
-    for (int k = 0; k < n; k++) { if (st[k] != expect) dense = false; expect *= d[k]; }
-    for (int k = n; k < 4; k++) { d[k] = 1; st[k] = 0; }
-    return dense;
 }
 
 }  // namespace

@@ -1,5 +1,6 @@
 """Device-resident chain of the per-voxel steps: raw float32 image (in HBM) -> float32 map volumes (in HBM).
 
+    amx_prep_ingest_device              the image in its stored dtype -> float32, scan included (optional: raw_dtype / scaling) core.py:136
     amx_prep_sanitize_device            NaN / Inf samples of the image replaced (optional: replace_bad_voxels) core.py:152-156
     amx_prep_debias_device              Rician debias in place (optional: debias_snr)                     core.py:201-206, preproc.py:23-36
     amx_prep_gather_directions_device   b0 normalisation (+ merge / shell average), mask gather, clip     core.py:209-268, 451-452
@@ -24,8 +25,19 @@ class _VolumePipeline:
     """what the model pipelines share: the plan, the buffers of the prepared signals and the directions, the chain up to the fit
     (scan, debias, gather + directions, scan of y) and run()"""
 
-    def _setup(self, scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels):
+    def _setup(self, scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels,
+               raw_dtype=None, scaling=None):
         import torch
+        # raw_dtype: run() is given the image in that stored dtype (the plan's geometry and element strides) and starts with the ingest
+        # kernel, which makes the float32 image `self.img` and does the scan of the image in the same pass; a scaling alone means float32
+        self.scaling = _prep.check_scaling(scaling)
+        if raw_dtype is None and (self.scaling is not None or img_like.dtype != np.float32):
+            raw_dtype = img_like.dtype if img_like.dtype in _capi.RAW_DTYPES else np.float32
+        self.raw_dtype = None if raw_dtype is None else np.dtype(raw_dtype)
+        if self.raw_dtype is not None and self.raw_dtype not in _capi.RAW_DTYPES:
+            raise ValueError('raw_dtype must be one of uint8, int16, uint16, int32, float32, float64')
+        if self.raw_dtype == np.float32 and self.scaling is None:
+            self.raw_dtype = None          # float32 as it is: the chain of today, nothing more is launched
         self.fused = bool(fused)           # False: gather, then the tensor fit as its own pass over y (the round-4 chain; A/B)
         self.torch = torch
         self.ctx = get_context()
@@ -39,6 +51,9 @@ class _VolumePipeline:
         if b0_min_signal != 0.0:
             raise NotImplementedError('b0_min_signal needs the whole-volume b0 mean on the host: use Evaluation')
         self.tensor = _dti.TensorDirections.from_scheme(scheme, ctx=self.ctx)
+        self.img = None
+        if self.raw_dtype is not None:
+            self.img = torch.empty(self.prep._plan.extent, dtype=torch.float32, device=self.dev)
 
     def _buffers(self, n_maps):
         torch = self.torch
@@ -57,7 +72,11 @@ class _VolumePipeline:
         L, c, p = _capi.lib(), self.ctx, self.prep._plan
         s = _capi.c_vp(stream or 0)
         r = self.replace_bad_voxels
-        if r is not None:
+        if self.raw_dtype is not None:
+            # core.py:136 and the scan of the image in one kernel; everything below reads the float32 image it leaves in self.img
+            p.ingest_device(d_img.data_ptr(), self.raw_dtype, self.img.data_ptr(), self.scaling, r, stream)
+            d_img = self.img
+        elif r is not None:
             p.sanitize_device(d_img.data_ptr(), r, stream)
         if self.prep.debias_snr is not None:
             p.debias_device(d_img.data_ptr(), self.prep.debias_snr, stream)
@@ -86,25 +105,31 @@ class _VolumePipeline:
         if self.replace_bad_voxels is not None:
             # the chain's two scans are the last two sanitize calls of the context: image first, y second
             self.bad_samples, self.bad_samples_preprocessed = self.ctx.sanitize_previous(), self.ctx.sanitize_last()
+        elif self.raw_dtype is not None:
+            self.bad_samples = self.ctx.sanitize_last()       # the ingest kernel counts whether or not it replaces
         return self.maps, self.dirs_vol
 
 
 class NoddiVolumePipeline(_VolumePipeline):
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
-                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None):
-        """replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None, raw_dtype=None, scaling=None):
+        """raw_dtype / scaling: run() takes the image as it is stored (uint8, int16, uint16, int32, float32 or float64 elements in the
+        layout of `img_like`, which must be C or Fortran ordered) plus the NIfTI header's (slope, inter); the chain then starts with the
+        kernel that makes the float32 image in HBM (amx_prep_ingest_device) and counts its NaN / Inf samples into `bad_samples`.
+        replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
         the scan of the image ahead of everything else and the scan of y behind the gather, both replacing what they find, on
         the same stream and without a host wait; run() then leaves the two counts in `bad_samples` (image) and
         `bad_samples_preprocessed` (y).  With fused=True the gather computes the directions in the same kernel as y, so the
         directions of a voxel whose y is replaced afterwards come from the unreplaced values (fused=False fits them from the replaced y)."""
-        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels)
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling)
         self.lut = _capi.upload_noddi(self.ctx, kernels, htable, scheme.dwi_idx)
         self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
         self.shape = tuple(img_like.shape[:3])
         self._buffers(3)
 
     def enqueue(self, d_img, stream=None):
-        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`); with debias_snr
+        """d_img: torch float32 tensor holding the image's element buffer (same strides as `img_like`) -- with raw_dtype set, a tensor
+        holding the elements of that dtype instead (any torch dtype: only its memory is used), which is left as it is; with debias_snr
         set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere; with replace_bad_voxels set its
         NaN / Inf samples are overwritten before that"""
         L, c = _capi.lib(), self.ctx
@@ -118,12 +143,12 @@ class NoddiVolumePipeline(_VolumePipeline):
 class FreeWaterVolumePipeline(_VolumePipeline):
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.0, lambda2=1e-3, do_normalize=True,
                  b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None,
-                 corrected=False, keep_b0=False, is_mouse=False):
+                 corrected=False, keep_b0=False, is_mouse=False, raw_dtype=None, scaling=None):
         """The chain of NoddiVolumePipeline (same arguments, same meaning) with the Free-Water fit: leaves `maps` [X, Y, Z, 2 | 4 (Mouse)]
         and `dirs_vol` in HBM.  corrected=True (doSaveCorrectedDWI): also `corrected` [X, Y, Z, nS], the free-water-corrected DWI of
         core.py:488-498 -- rescaled by the b0 mean when do_normalize is set; keep_b0=True (doKeepb0Intact) leaves its b0 volumes
         as they were.  The fit stays on its fast kernel: it hands over the isotropic coefficients only (AMX_F_FW_ISO)."""
-        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels)
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling)
         self.lut = _capi.upload_freewater(self.ctx, kernels, htable)
         self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
         self.is_mouse = bool(is_mouse)

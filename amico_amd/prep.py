@@ -38,6 +38,53 @@ def check_replace_bad_voxels(value):
     return value
 
 
+def check_scaling(scaling):
+    """The NIfTI header's (scl_slope, scl_inter) as set_data takes it -> (slope, inter) as floats, or None for "no scaling": None,
+    a pair whose slope is None (what nibabel reports for an unscaled image) or the identity (1, 0).  A missing intercept is 0.
+    A value that is not finite, or a zero slope, is refused here -- on the host, before any context exists."""
+    if scaling is None:
+        return None
+    try:
+        slope, inter = scaling
+    except (TypeError, ValueError):
+        raise ValueError(f'scaling must be None or the pair (slope, inter), not {scaling!r}') from None
+    if slope is None:
+        return None
+    inter = 0.0 if inter is None else inter
+    for name, v in (('slope', slope), ('inter', inter)):
+        if not isinstance(v, (numbers.Real, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f'scaling: {name} must be a finite number, not {v!r}')
+    if slope == 0:
+        raise ValueError('scaling: slope must not be 0')
+    slope, inter = float(slope), float(inter)
+    return None if (slope == 1.0 and inter == 0.0) else (slope, inter)
+
+
+def to_float32(raw, scaling=None):
+    """core.py:136 on the host, the statement the ingest kernel is held to: np.float32(raw), or with the header's scaling
+    np.float32(np.float64(raw) * slope + inter) -- nibabel's scaling in float64, then the cast.  `scaling` as check_scaling returns it."""
+    raw = np.asarray(raw)
+    with np.errstate(over='ignore', invalid='ignore'):
+        if scaling is None:
+            return raw.astype(np.float32, copy=False)
+        return (raw.astype(np.float64) * scaling[0] + scaling[1]).astype(np.float32)
+
+
+def streamable(raw):
+    """can the image cross the link as it is stored?  One of the six dtypes amx_prep_ingest converts, and a layout that is a
+    permutation of a contiguous block (C order, nibabel's Fortran order)"""
+    if raw.dtype not in _capi.RAW_DTYPES or raw.ndim != 4 or raw.size == 0:
+        return False
+    if any(st <= 0 or st % raw.itemsize for st in raw.strides):
+        return False
+    expect = raw.itemsize
+    for st, d in sorted((st, d) for st, d in zip(raw.strides, raw.shape) if d != 1):
+        if st != expect:
+            return False
+        expect *= d
+    return True
+
+
 def refuse_or_warn(count, replace, sentence):
     """core.py:153-158 / 271-276 once the scan has counted `count` bad samples: nothing to do, a warning, or the refusal"""
     if count == 0:
@@ -73,10 +120,12 @@ def directional_average_table(scheme):
 
 
 class SignalPreparation:
-    """image [X, Y, Z, nS] float32 (any strides) + mask -> y f64[n_vox, n_out]; per-voxel results -> volumes."""
+    """image [X, Y, Z, nS] float32 (any strides) + mask -> y f64[n_vox, n_out]; per-voxel results -> volumes.
+    The image may also be given as it is stored (uint8 / int16 / uint16 / int32 / float64, or float32 with a scaling) in a streamable
+    layout: the plan is made on its shape and element strides and the float32 image is made on the GPU (amx_prep_ingest)."""
 
     def __init__(self, scheme, img_like, mask, do_normalize=True, do_merge_b0=False, do_directional_average=False,
-                 b0_min_signal=0.0, ctx=None, debias_snr=None, replace_bad_voxels=None):
+                 b0_min_signal=0.0, ctx=None, debias_snr=None, replace_bad_voxels=None, scaling=None):
         """debias_snr (DWI-SNR, or None = doDebiasSignal off): the image is debiased first, on the voxels with mask != 0
         (preproc.py:29), and is zero elsewhere (preproc.py:24).
         replace_bad_voxels (core.py:122-123; None = no scan at all): gather() replaces the NaN / Inf samples of a private copy of
@@ -84,14 +133,19 @@ class SignalPreparation:
         voxels' rows); the counts are left in bad_samples_raw / bad_samples_preprocessed and a warning is raised when one is not 0"""
         from .models import get_context
         self.replace_bad_voxels = check_replace_bad_voxels(replace_bad_voxels)      # (before a context is made)
+        self.scaling = check_scaling(scaling)
         self.bad_samples_raw = self.bad_samples_preprocessed = None
-        if img_like.ndim != 4 or img_like.dtype != np.float32:
+        self.raw = img_like.dtype != np.float32 or self.scaling is not None       # the float32 image is made by the ingest kernel
+        if img_like.ndim != 4 or (img_like.dtype != np.float32 and not streamable(img_like)):
             raise ValueError('DWI image must be a 4D float32 array')
+        if self.raw and not streamable(img_like):
+            raise ValueError('an image with a scaling must have a streamable layout (C or Fortran order)')
+        isz = img_like.itemsize
         if img_like.shape[3] != scheme.nS:
             raise ValueError('Scheme does not match with DWI data')                     # core.py:177-178
         if mask.shape != img_like.shape[:3]:
             raise ValueError('MASK geometry does not match with DWI data')              # core.py:191-192
-        if any(s % 4 or s <= 0 for s in img_like.strides):
+        if any(s % isz or s <= 0 for s in img_like.strides):
             raise ValueError('image strides must be positive multiples of the element size')
         if do_normalize and scheme.b0_count == 0:
             raise RuntimeError('No b0 volume to normalize signal with')                 # core.py:214-215
@@ -108,7 +162,7 @@ class SignalPreparation:
         rank = np.full(self.sel.shape, -1, dtype=np.int32)
         rank[self.sel] = np.arange(int(self.sel.sum()), dtype=np.int32)                 # C-order enumeration
         self.ctx = ctx if ctx is not None else get_context()
-        self._plan = _capi.Prep(self.ctx, img_like.shape, tuple(s // 4 for s in img_like.strides), rank, self.groups,
+        self._plan = _capi.Prep(self.ctx, img_like.shape, tuple(s // isz for s in img_like.strides), rank, self.groups,
                                 scheme.b0_idx, overwrite_in_order=bool(do_directional_average))
         self.n_vox, self.n_out = self._plan.n_vox, self._plan.n_out
         self.mean_b0s = None
@@ -132,7 +186,13 @@ class SignalPreparation:
     def gather(self, img):
         """-> (y f64[n_vox, n_out], mean_b0 f32[n_vox] of the masked voxels or None)"""
         r = self.replace_bad_voxels
-        if r is not None:
+        if self.raw:
+            # the stored image -> float32, scanned (and replaced) by the same kernel: core.py:136 + 152-156
+            img, bad = self._plan.ingest(img, self.scaling, r)
+            if r is not None:
+                self.bad_samples_raw = bad
+                refuse_or_warn(bad, r, BAD_RAW)
+        elif r is not None:
             img = np.lib.stride_tricks.as_strided(np.array(self._plan._img_buffer(img)), shape=img.shape, strides=img.strides)
             self.bad_samples_raw = self._plan.sanitize(img, r)                          # core.py:152-156
             refuse_or_warn(self.bad_samples_raw, r, BAD_RAW)

@@ -416,7 +416,9 @@ int amx_debias_last_unconverged(amx_ctx *ctx, int64_t *out);
  * The device forms are enqueued on `hip_stream` and wait for nothing.  amx_sanitize_last gives the count of the last sanitize call on
  * this ctx, amx_sanitize_previous that of the call before it (a chain scans the image and then y on one stream and reads both at
  * its end); each waits for its call through an event recorded behind the kernel and gives 0 when there was no such call.  The ctx
- * keeps those two counters: a third call reuses the first one's, so calls on different streams must not leave more than two in flight. */
+ * keeps those two counters: a third call reuses the first one's, so calls on different streams must not leave more than two in flight.
+ * An amx_prep_ingest* call (below) takes one of the two counters exactly like a sanitize call: it counts as one of the two in flight,
+ * and amx_sanitize_last / amx_sanitize_previous read its count. */
 int amx_prep_sanitize(amx_ctx *ctx, const amx_prep *p, float *img, int replace, float value, int64_t *out_count);   /* host image, in place */
 int amx_prep_sanitize_device(amx_ctx *ctx, const amx_prep *p, float *d_img, int replace, float value, void *hip_stream);
 int amx_sanitize_device_f32(amx_ctx *ctx, float *d_buf, int64_t count, int replace, float value, void *hip_stream);
@@ -424,6 +426,35 @@ int amx_sanitize_device(amx_ctx *ctx, double *d_buf, int64_t count, int replace,
 int amx_sanitize(amx_ctx *ctx, double *buf, int64_t count, int replace, double value, int64_t *out_count);          /* host buffer, in place */
 int amx_sanitize_last(amx_ctx *ctx, int64_t *out_count);
 int amx_sanitize_previous(amx_ctx *ctx, int64_t *out_count);
+
+/* (f0'') The image in its STORED dtype -> the float32 image, core.py:136 `niiDWI_img = img.astype(np.float32)` in HBM, fused with the
+ * scan above: the raw bytes cross the link as they are stored (int16 with scl_slope / scl_inter: half the bytes of float32; the
+ * float64 of nibabel's get_fdata() needs no host pass to narrow it), are read once and every float32 element is written once.
+ * raw_dtype: one of AMX_T_*.  d_raw has the plan's geometry and the plan's ELEMENT strides -- those of the float32 image, counted in
+ * elements of its own type; d_img receives the float32 image in the plan's layout.  The two buffers must not overlap; d_raw is
+ * aligned to its element size (a block of 2-byte elements may start at any multiple of 2 bytes), d_img to 4 bytes.
+ * Value rule -- the reference is numpy:
+ *     slope == 1 && inter == 0:   out = np.float32(raw)       round to nearest even from int32 and float64; float64 beyond float32's range
+ *                                                             -> +-Inf; denormals and -0.0 are preserved; NaN stays NaN; float32 keeps its bits
+ *     otherwise:                  out = np.float32(np.float64(raw) * slope + inter)       product and sum each rounded in fp64 (no fused
+ *                                                             multiply-add), as nibabel scales and core.py:136 then narrows
+ * slope and inter must be finite (AMX_E_BADARG).  The same kernel counts the non-finite float32 RESULTS (integer pattern; NaN, +Inf, -Inf)
+ * and with replace != 0 stores `value` in their place, exactly what amx_prep_sanitize_device does on that float32 image; a non-finite
+ * value with replace != 0 is AMX_E_BADARG.  The count is read through amx_sanitize_last / amx_sanitize_previous (see above).
+ * Layout: a plan whose image is a permutation of a contiguous block (C order, nibabel's Fortran order) is streamed as that block,
+ * every element inside and outside the mask.  Any other view is refused (AMX_E_BADARG, message in amx_last_error): its caller converts
+ * on the host and takes amx_prep_sanitize_device.  The device form is enqueued on `hip_stream` and waits for nothing; the host form
+ * uploads `raw`, converts, writes the float32 image to `img` and returns the count (blocking). */
+#define AMX_T_U8   1
+#define AMX_T_I16  2
+#define AMX_T_U16  3
+#define AMX_T_I32  4
+#define AMX_T_F32  5
+#define AMX_T_F64  6
+int amx_prep_ingest_device(amx_ctx *ctx, const amx_prep *p, const void *d_raw, int raw_dtype, double slope, double inter, int replace,
+                           float value, float *d_img, void *hip_stream);
+int amx_prep_ingest(amx_ctx *ctx, const amx_prep *p, const void *raw, int raw_dtype, double slope, double inter, int replace, float value,
+                    float *img, int64_t *out_count);
 
 /* (f4) LUT resampling to the subject's scheme, lut.pyx:274-311 `resample_kernel` (called per atom by
  * NODDI.resample models.pyx:754-792, FreeWater.resample :1113-1144, ...):
