@@ -4,8 +4,10 @@ There is NO CPU fallback: if the HIP library is missing or no gfx950 GPU is visi
 entry point raises.  Device memory for the ``*_device`` calls is plain pointers (e.g.
 ``torch.Tensor.data_ptr()``) -- torch is plumbing, never part of the signatures.
 """
+import contextlib
 import ctypes as C
 import os
+from collections import namedtuple
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -35,6 +37,42 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device']
+
+# one row per model fit: what the C entry points amx_<stem>_fit[_f32] / amx_<stem>_fit_device[_f32] differ in.  lib() makes their argtypes
+# from it, _fit_host / _fit_device their calls, models.BaseModel._run the results dict.
+#   dirs     the call takes DIRs behind y
+#   extras   ctypes of the model's own scalars between lambda2 and flags; the wrappers' `extras` tuple starts with their values and may go
+#            on with values only the row's own functions read (NODDI's n_maps)
+#   outputs  in ABI order: (result name, wrapper keyword that switches it on (None: always), AMX_F_* flag, trailing shape(lut, extras))
+#   x_shape  trailing shape of the AMX_F_DEBUG_X coefficients (return_x)
+#   check    the model's own argument check, behind those of y and DIRs (or None)
+FitRow = namedtuple('FitRow', 'stem dirs extras outputs x_shape check')
+Output = namedtuple('Output', 'name key flag shape')
+
+
+def _check_n_maps(lut, extras):
+    if lut.n_maps is not None and extras[0] != lut.n_maps:      # (the library writes what the DICTIONARY says: a short buffer would be overrun)
+        raise ValueError(f'the dictionary writes {lut.n_maps} maps per voxel, the model expects {extras[0]} (isExvivo changed?)')
+
+
+def _outputs(width, *more):
+    return (Output('estimates', None, 0, width), Output('rmse', 'rmse', F_RMSE, lambda lut, ex: ()),
+            Output('nrmse', 'nrmse', F_NRMSE, lambda lut, ex: ())) + more
+
+
+def _atoms(lut):
+    return (lut.n_atoms,)
+
+
+FITS = (
+    FitRow('noddi', True, (), _outputs(lambda lut, ex: (ex[0],), Output('estimates_mod', 'mod', F_MODULATED, lambda lut, ex: (2,))),
+           lambda lut: (3, lut.n_atoms), _check_n_maps),
+    FitRow('freewater', True, (C.c_int,), _outputs(lambda lut, ex: (4 if ex[0] else 2,),
+                                                   Output('y_corrected', 'corrected', F_CORRECTED, lambda lut, ex: (lut.nS,))), _atoms, None),
+    FitRow('sandi', False, (), _outputs(lambda lut, ex: (6,)), _atoms, None),
+    FitRow('czb', True, (), _outputs(lambda lut, ex: (3,)), _atoms, None),
+)
+FIT = {row.stem: row for row in FITS}
 
 _lib = None
 c_vp, c_dp, c_fp = C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_float)
@@ -88,7 +126,6 @@ def lib():
     except ImportError:
         pass
     L = C.CDLL(LIB_PATH)
-    L.amx_version.restype = C.c_int
     L.amx_build_id.restype = C.c_char_p
     L.amx_ctx_create.argtypes = [C.c_int, C.POINTER(c_vp)]
     L.amx_ctx_destroy.argtypes = [c_vp]
@@ -104,36 +141,20 @@ def lib():
     L.amx_lut_destroy.argtypes = [c_vp]
     L.amx_lut_destroy.restype = None
     L.amx_dir_to_lut_idx.argtypes = [c_vp, c_vp, c_dp, C.c_int64, c_i32p]
-    L.amx_noddi_fit.argtypes = [c_vp, c_vp, c_dp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint,
-                                c_dp, c_dp, c_dp, c_dp]
-    L.amx_freewater_fit.argtypes = [c_vp, c_vp, c_dp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_int,
-                                    C.c_uint, c_dp, c_dp, c_dp, c_dp]
-    L.amx_sandi_fit.argtypes = [c_vp, c_vp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp]
-    L.amx_noddi_fit_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_double, C.c_double, C.c_uint,
-                                       c_vp, c_vp, c_vp, c_vp, c_vp]
-    L.amx_freewater_fit_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_double, C.c_double, C.c_int,
-                                           C.c_uint, c_vp, c_vp, c_vp, c_vp, c_vp]
-    L.amx_sandi_fit_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double, C.c_double, C.c_uint,
-                                       c_vp, c_vp, c_vp, c_vp]
+    for row in FITS:                # the 16 fit symbols: the host form takes y as float64 | float32 rows, the device form pointers + the stream
+        mid = [C.c_int64, C.c_double, C.c_double] + list(row.extras) + [C.c_uint]
+        for sfx, yp in (('', c_dp), ('_f32', c_fp)):
+            getattr(L, 'amx_%s_fit%s' % (row.stem, sfx)).argtypes = [c_vp, c_vp, yp] + [c_dp] * row.dirs + mid + [c_dp] * len(row.outputs)
+            getattr(L, 'amx_%s_fit_device%s' % (row.stem, sfx)).argtypes = [c_vp] * (3 + row.dirs) + mid + [c_vp] * (len(row.outputs) + 1)
     L.amx_sync_status.argtypes = [c_vp, c_vp]
     L.amx_set_debug_x.argtypes = [c_vp, c_vp]
     L.amx_set_fw_iso.argtypes = [c_vp, c_vp]
     L.amx_freewater_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]      # ctx, lut, y32, y64, x_iso, n, ycorr, stream
     L.amx_prep_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, C.c_int, c_vp, c_vp]  # ctx, plan, lut, y32, x_iso, mean_b0, b0_cols (host), n, volume, stream
     L.amx_debug_fetch.argtypes = [c_vp, c_vp, C.c_int, c_vp, C.c_size_t]
-    L.amx_noddi_fit_f32.argtypes = [c_vp, c_vp, c_fp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp, c_dp]
-    L.amx_freewater_fit_f32.argtypes = [c_vp, c_vp, c_fp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_int, C.c_uint,
-                                        c_dp, c_dp, c_dp, c_dp]
-    L.amx_sandi_fit_f32.argtypes = [c_vp, c_vp, c_fp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp]
     L.amx_set_progress.argtypes = [c_vp, PROGRESS_CB, c_vp]
     L.amx_lut_upload_czb.argtypes = [c_vp, c_fp, c_fp, c_fp, c_dp, c_i16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.POINTER(c_vp)]
-    L.amx_czb_fit.argtypes = [c_vp, c_vp, c_dp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp]
-    L.amx_czb_fit_f32.argtypes = [c_vp, c_vp, c_fp, c_dp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_dp, c_dp, c_dp]
-    L.amx_czb_fit_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_double, C.c_double, C.c_uint, c_vp, c_vp, c_vp, c_vp]
-    for name in ('noddi', 'freewater', 'sandi', 'czb'):
-        getattr(L, 'amx_%s_fit_device_f32' % name).argtypes = getattr(L, 'amx_%s_fit_device' % name).argtypes
-        getattr(L, 'amx_%s_fit_device_f32' % name).restype = C.c_int
     L.amx_set_profiling.argtypes = [c_vp, C.c_int]
     L.amx_last_kernel_ms.argtypes = [c_vp, C.c_int, C.POINTER(C.c_float)]
     L.amx_last_stats.argtypes = [c_vp, c_i64p]
@@ -159,7 +180,6 @@ def lib():
     L.amx_dti_directions.argtypes = [c_vp, c_vp, c_dp, C.c_int64, c_dp]
     L.amx_dti_directions_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]
     L.amx_dti_directions_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]
-    L.amx_dti_directions_device_f32.restype = C.c_int
     L.amx_prep_create.argtypes = [c_vp, c_i64p, c_i64p, C.c_int, c_i32p, C.c_int64, c_i32p, c_i32p, C.c_int,
                                   c_i32p, C.c_int, C.c_int, C.POINTER(c_vp)]
     L.amx_prep_destroy.argtypes = [c_vp]
@@ -167,10 +187,8 @@ def lib():
     L.amx_prep_gather.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, c_dp, c_fp]
     L.amx_prep_gather_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp, c_vp, c_vp]
     L.amx_prep_gather_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp, c_vp, c_vp]
-    L.amx_prep_gather_device_f32.restype = C.c_int
     for f_ in (L.amx_prep_gather_directions_device, L.amx_prep_gather_directions_device_f32):
         f_.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp, c_vp, c_vp, c_vp]      # ctx, plan, tensor helper, img, normalize, thr, y, mean_b0, dirs, stream
-        f_.restype = C.c_int
     L.amx_prep_mean_b0.argtypes = [c_vp, c_vp, c_fp, c_fp]
     L.amx_prep_mean_b0_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp]
     L.amx_prep_scatter.argtypes = [c_vp, c_vp, c_dp, C.c_int, c_fp]
@@ -194,10 +212,6 @@ def lib():
     L.amx_prep_ingest.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, c_fp, C.POINTER(C.c_int64)]
     L.amx_lut_resample.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     L.amx_lut_rotate_resample.argtypes = [c_vp, c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
-    for name in SYMBOLS:
-        fn = getattr(L, name)
-        if fn.restype is C.c_int and name not in ('amx_version', 'amx_build_id'):
-            fn.restype = C.c_int
     _lib = L
     return L
 
@@ -323,8 +337,8 @@ class Context:
 class Lut:
     """amx_lut: device-resident dictionary."""
 
-    def __init__(self, ctx, handle, model, nS, n_atoms, n_maps=None):
-        self.ctx, self._h, self.model, self.nS, self.n_atoms, self.n_maps = ctx, handle, model, nS, n_atoms, n_maps
+    def __init__(self, ctx, handle, model, nS, n_atoms, n_maps=None, n_iso=None):
+        self.ctx, self._h, self.model, self.nS, self.n_atoms, self.n_maps, self.n_iso = ctx, handle, model, nS, n_atoms, n_maps, n_iso
 
     def close(self):
         if getattr(self, '_h', None) and getattr(self.ctx, '_h', None):
@@ -370,9 +384,7 @@ def upload_freewater(ctx, kernels, htable):
     h = c_vp()
     ctx.check(lib().amx_lut_upload_freewater(ctx._h, _p(D, c_fp), _p(CSF, c_fp), _p(ht, c_i16p), D.shape[0],
                                              CSF.shape[0], D.shape[1], D.shape[2], C.byref(h)))
-    lut = Lut(ctx, h, 'FreeWater', D.shape[2], D.shape[0] + CSF.shape[0])
-    lut.n_iso = CSF.shape[0]
-    return lut
+    return Lut(ctx, h, 'FreeWater', D.shape[2], D.shape[0] + CSF.shape[0], n_iso=CSF.shape[0])
 
 
 def upload_sandi(ctx, kernels, Rs, d_in, d_isos):
@@ -416,10 +428,6 @@ def _check_y(y, nS):
     return y
 
 
-def _yp(y):
-    return (True, _p(y, c_fp)) if y.dtype == np.float32 else (False, _p(y, c_dp))
-
-
 def _check_dirs(dirs, n):
     dirs = np.ascontiguousarray(dirs, dtype=np.float64)      # a copy is never modified (lut.pyx:335-338 quirk)
     if dirs.shape != (n, 3):
@@ -444,59 +452,52 @@ def _outs(out, n, specs):
     return res
 
 
-def noddi_fit(ctx, lut, y, dirs, lambda1, lambda2, n_maps, rmse=False, nrmse=False, mod=False, out=None):
+def _switches(row, want):
+    """(flags, [output k is on]) of a call"""
+    flags, on = 0, []
+    for o in row.outputs:
+        on.append(o.key is None or bool(want.get(o.key)))
+        if on[-1]:
+            flags |= o.flag
+    return flags, on
+
+
+def _fit_host(row, ctx, lut, y, dirs, lambda1, lambda2, extras, want, out):
+    """the host-buffer fit of `row`: extras as the row describes them, want: wrapper keyword -> bool, out: see _outs"""
     y = _check_y(y, lut.nS)
     n = y.shape[0]
-    dirs = _check_dirs(dirs, n)
-    if lut.n_maps is not None and n_maps != lut.n_maps:      # (the library writes what the DICTIONARY says: a short buffer would be overrun)
-        raise ValueError(f'the dictionary writes {lut.n_maps} maps per voxel, the model expects {n_maps} (isExvivo changed?)')
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_MODULATED if mod else 0)
-    est, r, nr, md = _outs(out, n, [((n_maps,), True), ((), rmse), ((), nrmse), ((2,), mod)])
-    f32, yp = _yp(y)
-    fn = lib().amx_noddi_fit_f32 if f32 else lib().amx_noddi_fit
-    ctx.check(fn(ctx._h, lut._h, yp, _p(dirs, c_dp), n, float(lambda1), float(lambda2),
-                 flags, _p(est, c_dp), _p(r, c_dp), _p(nr, c_dp), _p(md, c_dp)))
-    return est, r, nr, md
+    if row.dirs:
+        dirs = _check_dirs(dirs, n)
+    if row.check is not None:
+        row.check(lut, extras)
+    flags, on = _switches(row, want)
+    res = _outs(out, n, [(o.shape(lut, extras), k) for o, k in zip(row.outputs, on)])
+    f32 = y.dtype == np.float32
+    fn = getattr(lib(), 'amx_%s_fit%s' % (row.stem, '_f32' if f32 else ''))
+    args = [ctx._h, lut._h, _p(y, c_fp if f32 else c_dp)] + ([_p(dirs, c_dp)] if row.dirs else [])
+    args += (n, float(lambda1), float(lambda2)) + tuple(extras[:len(row.extras)]) + (flags,)
+    ctx.check(fn(*args, *[_p(a, c_dp) for a in res]))
+    return tuple(res)
+
+
+def noddi_fit(ctx, lut, y, dirs, lambda1, lambda2, n_maps, rmse=False, nrmse=False, mod=False, out=None):
+    return _fit_host(FIT['noddi'], ctx, lut, y, dirs, lambda1, lambda2, (n_maps,), dict(rmse=rmse, nrmse=nrmse, mod=mod), out)
 
 
 def freewater_fit(ctx, lut, y, dirs, lambda1, lambda2, is_mouse, rmse=False, nrmse=False, corrected=False, out=None):
-    y = _check_y(y, lut.nS)
-    n = y.shape[0]
-    dirs = _check_dirs(dirs, n)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_CORRECTED if corrected else 0)
-    est, r, nr, yc = _outs(out, n, [((4 if is_mouse else 2,), True), ((), rmse), ((), nrmse), ((lut.nS,), corrected)])
-    f32, yp = _yp(y)
-    fn = lib().amx_freewater_fit_f32 if f32 else lib().amx_freewater_fit
-    ctx.check(fn(ctx._h, lut._h, yp, _p(dirs, c_dp), n, float(lambda1), float(lambda2), int(bool(is_mouse)), flags,
-                 _p(est, c_dp), _p(r, c_dp), _p(nr, c_dp), _p(yc, c_dp)))
-    return est, r, nr, yc
+    return _fit_host(FIT['freewater'], ctx, lut, y, dirs, lambda1, lambda2, (int(bool(is_mouse)),),
+                     dict(rmse=rmse, nrmse=nrmse, corrected=corrected), out)
 
 
 def sandi_fit(ctx, lut, y, lambda1, lambda2, rmse=False, nrmse=False, out=None):
-    y = _check_y(y, lut.nS)
-    n = y.shape[0]
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0)
-    est, r, nr = _outs(out, n, [((6,), True), ((), rmse), ((), nrmse)])
-    f32, yp = _yp(y)
-    fn = lib().amx_sandi_fit_f32 if f32 else lib().amx_sandi_fit
-    ctx.check(fn(ctx._h, lut._h, yp, n, float(lambda1), float(lambda2), flags, _p(est, c_dp), _p(r, c_dp), _p(nr, c_dp)))
-    return est, r, nr
+    return _fit_host(FIT['sandi'], ctx, lut, y, None, lambda1, lambda2, (), dict(rmse=rmse, nrmse=nrmse), out)
 
 
 def czb_fit(ctx, lut, y, dirs, lambda1, lambda2, rmse=False, nrmse=False, out=None):
-    y = _check_y(y, lut.nS)
-    n = y.shape[0]
-    dirs = _check_dirs(dirs, n)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0)
-    est, r, nr = _outs(out, n, [((3,), True), ((), rmse), ((), nrmse)])
-    f32, yp = _yp(y)
-    fn = lib().amx_czb_fit_f32 if f32 else lib().amx_czb_fit
-    ctx.check(fn(ctx._h, lut._h, yp, _p(dirs, c_dp), n, float(lambda1), float(lambda2), flags, _p(est, c_dp), _p(r, c_dp),
-                 _p(nr, c_dp)))
-    return est, r, nr
+    return _fit_host(FIT['czb'], ctx, lut, y, dirs, lambda1, lambda2, (), dict(rmse=rmse, nrmse=nrmse), out)
 
 
-# ---- the same three fits on DEVICE-resident inputs (torch tensors used as plain device buffers); outputs are torch
+# ---- the same four fits on DEVICE-resident inputs (torch tensors used as plain device buffers); outputs are torch
 #      tensors on the same device, enqueued on `stream`; the caller synchronises with ctx.sync(stream)
 def debug_fetch(ctx, lut, which, shape, dtype):
     """workspace / dictionary tables of the support seeds (include/amico_amd.h: amx_debug_fetch) as a numpy array"""
@@ -507,12 +508,6 @@ def debug_fetch(ctx, lut, which, shape, dtype):
 
 def _dptr(t):
     return c_vp(t.data_ptr()) if t is not None else None
-
-
-def _dev_fn(model, y_t):
-    """amx_<model>_fit_device for float64 tensors, amx_<model>_fit_device_f32 for float32 ones"""
-    import torch
-    return getattr(lib(), 'amx_%s_fit_device%s' % (model, '_f32' if y_t.dtype == torch.float32 else ''))
 
 
 def _check_dev(lut, y_t, dirs_t=None):
@@ -527,58 +522,75 @@ def _check_dev(lut, y_t, dirs_t=None):
         raise ValueError('DIRs must be a contiguous float64 device tensor [n_vox, 3] on the device of y')
 
 
-def _debug_x(ctx, shape, like, want):
-    """registers a zeroed coefficient buffer for AMX_F_DEBUG_X (include/amico_amd.h) and returns (tensor, flag)"""
+def _own_tensor(name, t, shape, like):
+    """a result tensor the caller hands in: checked as strictly as _outs checks host arrays"""
     import torch
-    if not want:
-        return None, 0
-    x = torch.zeros(shape, dtype=torch.float64, device=like.device)
-    ctx.check(lib().amx_set_debug_x(ctx._h, _dptr(x)))
-    return x, F_DEBUG_X
+    if t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != like.device:
+        raise ValueError('%s must be a contiguous float64 device tensor of shape %s on the device of y' % (name, (shape,)))
+    return t
+
+
+_NOTHING = contextlib.nullcontext()
+
+
+@contextlib.contextmanager
+def _fw_iso(ctx, xi):
+    """the buffer AMX_F_FW_ISO writes to is registered for the length of the fit call"""
+    ctx.check(lib().amx_set_fw_iso(ctx._h, _dptr(xi)))
+    try:
+        yield
+    finally:
+        lib().amx_set_fw_iso(ctx._h, None)       # (the kernels enqueued meanwhile carry the pointer; the tensor is the caller's from here)
+
+
+def _fit_device(row, ctx, lut, y_t, dirs_t, lambda1, lambda2, extras, want, stream, return_x, iso, into=None):
+    """the device-resident fit of `row` (extras, want: as for _fit_host).  return_x: the zeroed AMX_F_DEBUG_X coefficients come back behind
+    the outputs; iso (Free-Water): True, or the tensor to write them into -- the isotropic coefficients f64 [n_vox, n_iso] come back
+    last; into: the `estimates` tensor, when the caller owns one already"""
+    import torch
+    _check_dev(lut, y_t, dirs_t if row.dirs else None)
+    if row.check is not None:
+        row.check(lut, extras)
+    n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
+    (flags, on), xd, xi = _switches(row, want), None, None
+    if return_x:
+        xd = torch.zeros((n,) + row.x_shape(lut), **f64)
+        ctx.check(lib().amx_set_debug_x(ctx._h, _dptr(xd)))
+        flags |= F_DEBUG_X
+    if iso is not False:
+        xi = torch.empty((n, lut.n_iso), **f64) if iso is True else _own_tensor('iso', iso, (n, lut.n_iso), y_t)
+        flags |= F_FW_ISO
+    res = [torch.empty((n,) + o.shape(lut, extras), **f64) if k else None for o, k in zip(row.outputs, on)]
+    if into is not None:
+        res[0] = _own_tensor('into', into, tuple(res[0].shape), y_t)
+    fn = getattr(lib(), 'amx_%s_fit_device%s' % (row.stem, '_f32' if y_t.dtype == torch.float32 else ''))
+    args = [ctx._h, lut._h, _dptr(y_t)] + ([_dptr(dirs_t)] if row.dirs else [])
+    args += (n, float(lambda1), float(lambda2)) + tuple(extras[:len(row.extras)]) + (flags,)
+    with _fw_iso(ctx, xi) if xi is not None else _NOTHING:
+        ctx.check(fn(*args, *[_dptr(t) for t in res], c_vp(stream or 0)))
+    return tuple(res) + ((xd,) if return_x else ()) + ((xi,) if xi is not None else ())
 
 
 def noddi_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, n_maps, rmse=False, nrmse=False, mod=False, stream=None,
                      return_x=False):
-    import torch
-    _check_dev(lut, y_t, dirs_t)
-    if lut.n_maps is not None and n_maps != lut.n_maps:
-        raise ValueError(f'the dictionary writes {lut.n_maps} maps per voxel, the model expects {n_maps} (isExvivo changed?)')
-    n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
-    xd, fx = _debug_x(ctx, (n, 3, lut.n_atoms), y_t, return_x)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_MODULATED if mod else 0) | fx
-    est = torch.empty((n, n_maps), **f64)
-    r = torch.empty(n, **f64) if rmse else None
-    nr = torch.empty(n, **f64) if nrmse else None
-    md = torch.empty((n, 2), **f64) if mod else None
-    ctx.check(_dev_fn('noddi', y_t)(ctx._h, lut._h, _dptr(y_t), _dptr(dirs_t), n, float(lambda1), float(lambda2), flags,
-                                         _dptr(est), _dptr(r), _dptr(nr), _dptr(md), c_vp(stream or 0)))
-    return (est, r, nr, md, xd) if return_x else (est, r, nr, md)
+    return _fit_device(FIT['noddi'], ctx, lut, y_t, dirs_t, lambda1, lambda2, (n_maps,), dict(rmse=rmse, nrmse=nrmse, mod=mod), stream,
+                       return_x, False)
 
 
 def freewater_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, is_mouse, rmse=False, nrmse=False, corrected=False,
                          stream=None, return_x=False, iso=False):
     """iso=True: the isotropic coefficients of every voxel, f64 [n_vox, n_iso], come back as one more element (AMX_F_FW_ISO: what
     freewater_corrected_device / Prep.corrected_device make the corrected DWI from; the flag changes no path, unlike corrected=True)"""
-    import torch
-    _check_dev(lut, y_t, dirs_t)
-    n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
-    xd, fx = _debug_x(ctx, (n, lut.n_atoms), y_t, return_x)
-    xi = torch.empty((n, lut.n_iso), **f64) if iso else None
-    if iso:
-        ctx.check(lib().amx_set_fw_iso(ctx._h, _dptr(xi)))
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | (F_CORRECTED if corrected else 0) | fx | (F_FW_ISO if iso else 0)
-    est = torch.empty((n, 4 if is_mouse else 2), **f64)
-    r = torch.empty(n, **f64) if rmse else None
-    nr = torch.empty(n, **f64) if nrmse else None
-    yc = torch.empty((n, lut.nS), **f64) if corrected else None
-    try:
-        ctx.check(_dev_fn('freewater', y_t)(ctx._h, lut._h, _dptr(y_t), _dptr(dirs_t), n, float(lambda1), float(lambda2),
-                                                 int(bool(is_mouse)), flags, _dptr(est), _dptr(r), _dptr(nr), _dptr(yc),
-                                                 c_vp(stream or 0)))
-    finally:
-        if iso:
-            lib().amx_set_fw_iso(ctx._h, None)       # (the kernels enqueued above carry the pointer; the tensor is the caller's from here)
-    return (est, r, nr, yc) + ((xd,) if return_x else ()) + ((xi,) if iso else ())
+    return _fit_device(FIT['freewater'], ctx, lut, y_t, dirs_t, lambda1, lambda2, (int(bool(is_mouse)),),
+                       dict(rmse=rmse, nrmse=nrmse, corrected=corrected), stream, return_x, bool(iso))
+
+
+def czb_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, rmse=False, nrmse=False, stream=None, return_x=False):
+    return _fit_device(FIT['czb'], ctx, lut, y_t, dirs_t, lambda1, lambda2, (), dict(rmse=rmse, nrmse=nrmse), stream, return_x, False)
+
+
+def sandi_fit_device(ctx, lut, y_t, lambda1, lambda2, rmse=False, nrmse=False, stream=None, return_x=False):
+    return _fit_device(FIT['sandi'], ctx, lut, y_t, None, lambda1, lambda2, (), dict(rmse=rmse, nrmse=nrmse), stream, return_x, False)
 
 
 def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None):
@@ -594,34 +606,6 @@ def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None):
     ctx.check(lib().amx_freewater_corrected_device(ctx._h, lut._h, _dptr(y_t) if f32 else None, None if f32 else _dptr(y_t), _dptr(xiso_t),
                                                    n, _dptr(yc), c_vp(stream or 0)))
     return yc
-
-
-def czb_fit_device(ctx, lut, y_t, dirs_t, lambda1, lambda2, rmse=False, nrmse=False, stream=None, return_x=False):
-    import torch
-    _check_dev(lut, y_t, dirs_t)
-    n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
-    xd, fx = _debug_x(ctx, (n, lut.n_atoms), y_t, return_x)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | fx
-    est = torch.empty((n, 3), **f64)
-    r = torch.empty(n, **f64) if rmse else None
-    nr = torch.empty(n, **f64) if nrmse else None
-    ctx.check(_dev_fn('czb', y_t)(ctx._h, lut._h, _dptr(y_t), _dptr(dirs_t), n, float(lambda1), float(lambda2), flags,
-                                       _dptr(est), _dptr(r), _dptr(nr), c_vp(stream or 0)))
-    return (est, r, nr, xd) if return_x else (est, r, nr)
-
-
-def sandi_fit_device(ctx, lut, y_t, lambda1, lambda2, rmse=False, nrmse=False, stream=None, return_x=False):
-    import torch
-    _check_dev(lut, y_t)
-    n, f64 = y_t.shape[0], dict(dtype=torch.float64, device=y_t.device)
-    xd, fx = _debug_x(ctx, (n, lut.n_atoms), y_t, return_x)
-    flags = (F_RMSE if rmse else 0) | (F_NRMSE if nrmse else 0) | fx
-    est = torch.empty((n, 6), **f64)
-    r = torch.empty(n, **f64) if rmse else None
-    nr = torch.empty(n, **f64) if nrmse else None
-    ctx.check(_dev_fn('sandi', y_t)(ctx._h, lut._h, _dptr(y_t), n, float(lambda1), float(lambda2), flags, _dptr(est),
-                                         _dptr(r), _dptr(nr), c_vp(stream or 0)))
-    return (est, r, nr, xd) if return_x else (est, r, nr)
 
 
 class Dict:
@@ -824,6 +808,25 @@ class Prep:
             raise ValueError('the image is debiased in place and must be writeable')
         self.ctx.check(lib().amx_prep_debias(self.ctx._h, self._h, _p(buf, c_fp), float(snr)))
         return img
+
+    def gather_device(self, d_img, d_y, d_mean_b0, normalize, b0_threshold=0.0, stream=None):
+        """device pointers (ints): image -> float32 rows y [n_vox, n_out] and mean_b0 [n_vox] (amx_prep_gather_device_f32); enqueued on `stream`"""
+        self.ctx.check(lib().amx_prep_gather_device_f32(self.ctx._h, self._h, c_vp(d_img), int(bool(normalize)), float(b0_threshold),
+                                                        c_vp(d_y), c_vp(d_mean_b0), c_vp(stream or 0)))
+
+    def gather_directions_device(self, dti, d_img, d_y, d_mean_b0, d_dirs, normalize, b0_threshold=0.0, stream=None):
+        """gather_device and the principal directions f64 [n_vox, 3] of `dti` (a Dti) in one pass over the image
+        (amx_prep_gather_directions_device_f32)"""
+        self.ctx.check(lib().amx_prep_gather_directions_device_f32(self.ctx._h, self._h, dti._h, c_vp(d_img), int(bool(normalize)),
+                                                                   float(b0_threshold), c_vp(d_y), c_vp(d_mean_b0), c_vp(d_dirs), c_vp(stream or 0)))
+
+    def scatter_device(self, d_values, k, d_volume, stream=None):
+        """device pointers (ints): f64 [n_vox, k] -> float32 volume [X, Y, Z, k], zero outside the mask (amx_prep_scatter_device)"""
+        self.ctx.check(lib().amx_prep_scatter_device(self.ctx._h, self._h, c_vp(d_values), int(k), c_vp(d_volume), c_vp(stream or 0)))
+
+    def mean_b0_device(self, d_img, d_volume, stream=None):
+        """device pointers (ints): the b0 mean of every voxel, float32 [X, Y, Z] (amx_prep_mean_b0_device)"""
+        self.ctx.check(lib().amx_prep_mean_b0_device(self.ctx._h, self._h, c_vp(d_img), c_vp(d_volume), c_vp(stream or 0)))
 
     def debias_device(self, d_img, snr, stream=None):
         """device pointer (int) of the image's element buffer, in place, enqueued on `stream`"""

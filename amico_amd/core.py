@@ -255,7 +255,7 @@ class Evaluation:
         sel = self.niiMASK_img == 1                                   # core.py:451 (== 1, not nonzero)
         import torch                                                  # device buffers only
         dev = torch.device('cuda', torch.cuda.current_device())
-        L, ctx, plan = _capi.lib(), self._prep.ctx, self._prep._plan
+        ctx, plan = self._prep.ctx, self._prep._plan
         t = time.time()
         # ---- raw image -> HBM once; everything up to the map volumes stays there (one stream, default)
         raw = self._raw
@@ -286,11 +286,10 @@ class Evaluation:
         thr = 0.0
         if self._prep.do_normalize and self._prep.b0_min_signal != 0.0:              # core.py:217
             d_vol = torch.empty(shape3, dtype=torch.float32, device=dev)
-            ctx.check(L.amx_prep_mean_b0_device(ctx._h, plan._h, d_img.data_ptr(), d_vol.data_ptr(), None))
+            plan.mean_b0_device(d_img.data_ptr(), d_vol.data_ptr())
             mean_b0s = d_vol.cpu().numpy()
             thr = float(self._prep.b0_min_signal * mean_b0s[mean_b0s > 0].mean())
-        ctx.check(L.amx_prep_gather_device_f32(ctx._h, plan._h, d_img.data_ptr(), int(self._prep.do_normalize), thr,
-                                           d_y.data_ptr(), d_mb0.data_ptr(), None))  # core.py:209-268 + 451-452
+        plan.gather_device(d_img.data_ptr(), d_y.data_ptr(), d_mb0.data_ptr(), self._prep.do_normalize, thr)      # core.py:209-268 + 451-452
         # core.py:270-276 on the rows the fit reads (float32 overflow in the normalisation is what can make one), before the tensor fit
         _capi.sanitize_device(ctx, d_y.data_ptr(), n * self._prep.n_out, bad_value)
         self.set_config('bad_samples_preprocessed', ctx.sanitize_last())
@@ -340,7 +339,7 @@ class Evaluation:
                 return self._prep.scatter(host_values)
             k = 1 if t_.dim() == 1 else t_.shape[1]
             vol = torch.empty(shape3 + (k,), dtype=torch.float32, device=dev)
-            ctx.check(L.amx_prep_scatter_device(ctx._h, plan._h, t_.data_ptr(), k, vol.data_ptr(), None))
+            plan.scatter_device(t_.data_ptr(), k, vol.data_ptr())
             ctx.sync()
             v = vol.cpu().numpy()
             return v[..., 0] if t_.dim() == 1 else v

@@ -23,9 +23,14 @@ def set_devices(ids=None):
     variable AMX_DEVICES=all | 0,1,... sets the same without touching the caller's script)."""
     global _DEVICES
     if isinstance(ids, str):
-        ids = None if not ids.strip() else ('all' if ids.strip().lower() == 'all' else [int(t) for t in ids.replace(',', ' ').split()])
+        ids = _parse_ids(ids) if ids.strip() else None
     _DEVICES = ids if ids is None or ids == 'all' else [int(i) for i in ids]
     reset_context()
+
+
+def _parse_ids(text):
+    """'all' | '0,1' | '0 1' -> 'all' | [0, 1]"""
+    return 'all' if text.strip().lower() == 'all' else [int(t) for t in text.replace(',', ' ').split()]
 
 
 def _device_ids():
@@ -35,7 +40,7 @@ def _device_ids():
         e = os.environ.get('AMX_DEVICES', '').strip()
         if not e:
             return None
-        ids = 'all' if e.lower() == 'all' else [int(t) for t in e.replace(',', ' ').split()]
+        ids = _parse_ids(e)
     if ids == 'all':
         ids = list(range(_capi.device_count()))
     return ids or None
@@ -296,6 +301,38 @@ class BaseModel(ABC):
             'compute_rmse': evaluation.get_config('doComputeRMSE'),
             'compute_nrmse': evaluation.get_config('doComputeNRMSE'),
         }
+        get_context()         # (made before the model looks at KERNELS: a missing GPU is what the caller hears of first)
+
+    def _want(self, **more):
+        """the output switches of this fit as the keywords of the _capi wrappers; more: keyword -> key of self.configs"""
+        return {k: bool(self.configs[c]) for k, c in dict(rmse='compute_rmse', nrmse='compute_nrmse', **more).items()}
+
+    def _run(self, evaluation, row, upload, extras, want, dev_want=None, dev_tail=None):
+        """the fit every model shares, behind its own checks.  row: the model's _capi.FIT row; upload(ctx) -> Lut; extras: the model's
+        arguments behind lambda2; want: keyword -> bool of the optional outputs (dev_want: the same for device-resident signals, when
+        it differs); dev_tail(ctx, lut, dev, out, results) -> results: the model's own last step of the device-resident branch"""
+        ctx = get_context()
+        lut = self._lut(evaluation, lambda: upload(ctx))
+        lambdas = (self.solver_params['lambda1'], self.solver_params['lambda2'])
+        names = [o.name for o in row.outputs]
+        dev = getattr(evaluation, '_dev', None)
+        if dev is not None:
+            dirs = (self._dev_dirs(evaluation, dev),) if row.dirs else ()
+            out = getattr(_capi, row.stem + '_fit_device')(ctx, lut, dev['y'], *dirs, *lambdas, *extras, **(dev_want or want))
+            results = self._finish_device(ctx, dev, dict(zip(names, out)))
+            return results if dev_tail is None else dev_tail(ctx, lut, dev, out, results)
+        fit, y, d = getattr(_capi, row.stem + '_fit'), evaluation.y, evaluation.DIRs
+        on = [o.key is None or want[o.key] for o in row.outputs]
+        if len(get_contexts()) > 1:
+            n = y.shape[0]
+            outs = self._fit_on_devices(
+                evaluation, n, upload,
+                lambda c, l, lo, hi, o: fit(c, l, y[lo:hi], *((d[lo:hi],) if row.dirs else ()), *lambdas, *extras, out=o, **want),
+                tuple(np.zeros((n,) + o.shape(lut, extras)) if k else None for o, k in zip(row.outputs, on)))
+        else:
+            outs = fit(ctx, lut, y, *((d,) if row.dirs else ()), *lambdas, *extras, **want)
+            self._warn_if_capped(ctx)
+        return {name: a for name, a, k in zip(names, outs, on) if k}
 
     # ---- device-resident inputs: Evaluation.fit leaves `y` (and `DIRs`) in HBM (evaluation._dev) when it produced
     #      them on the GPU; the fit then reads them in place and keeps its outputs there for the scatter
@@ -468,33 +505,10 @@ class CylinderZeppelinBall(BaseModel):
     @_verified_fit
     def fit(self, evaluation):
         super().fit(evaluation)
-        ctx = get_context()
         K = evaluation.KERNELS
         if K['wmr'].shape[0] != len(self.Rs) or K['wmh'].shape[0] != len(self.d_perps) or K['iso'].shape[0] != len(self.d_isos):
             raise ValueError('KERNELS do not match Rs / d_perps / d_isos of the model')
-        lut = self._lut(evaluation, lambda: _capi.upload_czb(ctx, K, self.Rs, evaluation.htable))
-        kw = dict(rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']))
-        dev = getattr(evaluation, '_dev', None)
-        if dev is not None:
-            est, rmse, nrmse = _capi.czb_fit_device(ctx, lut, dev['y'], self._dev_dirs(evaluation, dev),
-                                                    self.solver_params['lambda1'], self.solver_params['lambda2'], **kw)
-            return self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse})
-        if len(get_contexts()) > 1:
-            n, y, d = evaluation.y.shape[0], evaluation.y, evaluation.DIRs
-            est, rmse, nrmse = self._fit_on_devices(
-                evaluation, n, lambda c: _capi.upload_czb(c, K, self.Rs, evaluation.htable),
-                lambda c, l, lo, hi, o: _capi.czb_fit(c, l, y[lo:hi], d[lo:hi], self.solver_params['lambda1'], self.solver_params['lambda2'], out=o, **kw),
-                (np.zeros((n, 3)), np.zeros(n) if kw['rmse'] else None, np.zeros(n) if kw['nrmse'] else None))
-        else:
-            est, rmse, nrmse = _capi.czb_fit(ctx, lut, evaluation.y, evaluation.DIRs, self.solver_params['lambda1'],
-                                             self.solver_params['lambda2'], **kw)
-            self._warn_if_capped(ctx)
-        results = {'estimates': est}
-        if self.configs['compute_rmse']:
-            results['rmse'] = rmse
-        if self.configs['compute_nrmse']:
-            results['nrmse'] = nrmse
-        return results
+        return self._run(evaluation, _capi.FIT['czb'], lambda c: _capi.upload_czb(c, K, self.Rs, evaluation.htable), (), self._want())
 
 
 class NODDI(BaseModel):
@@ -563,38 +577,12 @@ class NODDI(BaseModel):
     def fit(self, evaluation):
         super().fit(evaluation)
         self.configs['compute_modulated_maps'] = evaluation.get_config('doSaveModulatedMaps')
-        ctx = get_context()
         n_wm = len(self.IC_ODs) * len(self.IC_VFs)
         if evaluation.KERNELS['wm'].shape[0] != n_wm:
             raise ValueError('KERNELS do not match IC_VFs / IC_ODs of the model')
-        lut = self._lut(evaluation, lambda: _capi.upload_noddi(ctx, evaluation.KERNELS, evaluation.htable,
-                                                               self.scheme.dwi_idx, self.isExvivo))
-        dev = getattr(evaluation, '_dev', None)
-        if dev is not None:
-            est, rmse, nrmse, mod = _capi.noddi_fit_device(
-                ctx, lut, dev['y'], self._dev_dirs(evaluation, dev), self.solver_params['lambda1'], self.solver_params['lambda2'],
-                len(self.maps_name), rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']),
-                mod=bool(self.configs['compute_modulated_maps']))
-            return self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse, 'estimates_mod': mod})
-        kw = dict(rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']), mod=bool(self.configs['compute_modulated_maps']))
-        if len(get_contexts()) > 1:
-            n, y, d, nm = evaluation.y.shape[0], evaluation.y, evaluation.DIRs, len(self.maps_name)
-            est, rmse, nrmse, mod = self._fit_on_devices(
-                evaluation, n, lambda c: _capi.upload_noddi(c, evaluation.KERNELS, evaluation.htable, self.scheme.dwi_idx, self.isExvivo),
-                lambda c, l, lo, hi, o: _capi.noddi_fit(c, l, y[lo:hi], d[lo:hi], self.solver_params['lambda1'], self.solver_params['lambda2'], nm, out=o, **kw),
-                (np.zeros((n, nm)), np.zeros(n) if kw['rmse'] else None, np.zeros(n) if kw['nrmse'] else None, np.zeros((n, 2)) if kw['mod'] else None))
-        else:
-            est, rmse, nrmse, mod = _capi.noddi_fit(ctx, lut, evaluation.y, evaluation.DIRs, self.solver_params['lambda1'],
-                                                    self.solver_params['lambda2'], len(self.maps_name), **kw)
-            self._warn_if_capped(ctx)
-        results = {'estimates': est}
-        if self.configs['compute_rmse']:
-            results['rmse'] = rmse
-        if self.configs['compute_nrmse']:
-            results['nrmse'] = nrmse
-        if self.configs['compute_modulated_maps']:
-            results['estimates_mod'] = mod
-        return results
+        return self._run(evaluation, _capi.FIT['noddi'],
+                         lambda c: _capi.upload_noddi(c, evaluation.KERNELS, evaluation.htable, self.scheme.dwi_idx, self.isExvivo),
+                         (len(self.maps_name),), self._want(mod='compute_modulated_maps'))
 
 
 class FreeWater(BaseModel):
@@ -656,53 +644,29 @@ class FreeWater(BaseModel):
     def fit(self, evaluation):
         super().fit(evaluation)
         self.configs['save_corrected_DWI'] = evaluation.get_config('doSaveCorrectedDWI')
-        ctx = get_context()
-        lut = self._lut(evaluation, lambda: _capi.upload_freewater(ctx, evaluation.KERNELS, evaluation.htable))
-        dev = getattr(evaluation, '_dev', None)
-        if dev is not None:
-            # doSaveCorrectedDWI asks the fit for the isotropic coefficients only (AMX_F_FW_ISO: the fit stays on its fast kernel and reads
-            # the float32 signals in place); Evaluation.fit makes the corrected volume from them on the GPU, and the rows
-            # results['y_corrected'] (models.pyx:1264-1274) are made by the same kernel if somebody reads them
-            want_yc = bool(self.configs['save_corrected_DWI'])
-            out = _capi.freewater_fit_device(
-                ctx, lut, dev['y'], self._dev_dirs(evaluation, dev), self.solver_params['lambda1'], self.solver_params['lambda2'],
-                self.type == 'Mouse', rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']), iso=want_yc)
-            est, rmse, nrmse = out[:3]
-            results = _LazyResults(self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse}))
-            if want_yc:
-                d_y, x_iso = dev['y'], out[-1]
-                dev['out']['x_iso'], dev['lut'] = x_iso, lut
+        want = self._want(corrected='save_corrected_DWI')
+        # device-resident signals: doSaveCorrectedDWI asks the fit for the isotropic coefficients only (AMX_F_FW_ISO: the fit stays on its
+        # fast kernel and reads the float32 signals in place); Evaluation.fit makes the corrected volume from them on the GPU, and the rows
+        # results['y_corrected'] (models.pyx:1264-1274) are made by the same kernel if somebody reads them
+        return self._run(evaluation, _capi.FIT['freewater'], lambda c: _capi.upload_freewater(c, evaluation.KERNELS, evaluation.htable),
+                         (self.type == 'Mouse',), want, dict(rmse=want['rmse'], nrmse=want['nrmse'], iso=want['corrected']), self._lazy_corrected)
 
-                def rows():
-                    # (the thunk keeps y, x_iso and the dictionary alive as long as the dict lives unread; what it cannot keep is the context)
-                    if getattr(ctx, '_h', None) is None or getattr(lut, '_h', None) is None:
-                        raise RuntimeError("results['y_corrected'] of this fit was not read before its GPU context / dictionary was closed "
-                                           "(reset_context()): read it first, or fit again")
-                    yc = _capi.freewater_corrected_device(ctx, lut, d_y, x_iso)
-                    ctx.sync()
-                    return yc.cpu().numpy()
-                results.set_lazy('y_corrected', rows)
-            return results
-        kw = dict(rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']), corrected=bool(self.configs['save_corrected_DWI']))
-        mouse = self.type == 'Mouse'
-        if len(get_contexts()) > 1:
-            n, y, d = evaluation.y.shape[0], evaluation.y, evaluation.DIRs
-            est, rmse, nrmse, yc = self._fit_on_devices(
-                evaluation, n, lambda c: _capi.upload_freewater(c, evaluation.KERNELS, evaluation.htable),
-                lambda c, l, lo, hi, o: _capi.freewater_fit(c, l, y[lo:hi], d[lo:hi], self.solver_params['lambda1'], self.solver_params['lambda2'], mouse, out=o, **kw),
-                (np.zeros((n, 4 if mouse else 2)), np.zeros(n) if kw['rmse'] else None, np.zeros(n) if kw['nrmse'] else None,
-                 np.zeros((n, y.shape[1])) if kw['corrected'] else None))
-        else:
-            est, rmse, nrmse, yc = _capi.freewater_fit(ctx, lut, evaluation.y, evaluation.DIRs, self.solver_params['lambda1'],
-                                                       self.solver_params['lambda2'], mouse, **kw)
-            self._warn_if_capped(ctx)
-        results = {'estimates': est}
-        if self.configs['compute_rmse']:
-            results['rmse'] = rmse
-        if self.configs['compute_nrmse']:
-            results['nrmse'] = nrmse
-        if self.configs['save_corrected_DWI']:
-            results['y_corrected'] = yc
+    @staticmethod
+    def _lazy_corrected(ctx, lut, dev, out, results):
+        results = _LazyResults(results)
+        if len(out) > 4:                       # (the fit was asked for x_iso: it comes last)
+            d_y, x_iso = dev['y'], out[-1]
+            dev['out']['x_iso'], dev['lut'] = x_iso, lut
+
+            def rows():
+                # (the thunk keeps y, x_iso and the dictionary alive as long as the dict lives unread; what it cannot keep is the context)
+                if getattr(ctx, '_h', None) is None or getattr(lut, '_h', None) is None:
+                    raise RuntimeError("results['y_corrected'] of this fit was not read before its GPU context / dictionary was closed "
+                                       "(reset_context()): read it first, or fit again")
+                yc = _capi.freewater_corrected_device(ctx, lut, d_y, x_iso)
+                ctx.sync()
+                return yc.cpu().numpy()
+            results.set_lazy('y_corrected', rows)
         return results
 
 
@@ -768,27 +732,5 @@ class SANDI(BaseModel):
     @_verified_fit
     def fit(self, evaluation):
         super().fit(evaluation)
-        ctx = get_context()
-        lut = self._lut(evaluation, lambda: _capi.upload_sandi(ctx, evaluation.KERNELS, self.Rs, self.d_in, self.d_isos))
-        dev = getattr(evaluation, '_dev', None)
-        if dev is not None:
-            est, rmse, nrmse = _capi.sandi_fit_device(ctx, lut, dev['y'], self.solver_params['lambda1'],
-                                                      self.solver_params['lambda2'], rmse=bool(self.configs['compute_rmse']),
-                                                      nrmse=bool(self.configs['compute_nrmse']))
-            return self._finish_device(ctx, dev, {'estimates': est, 'rmse': rmse, 'nrmse': nrmse})
-        kw = dict(rmse=bool(self.configs['compute_rmse']), nrmse=bool(self.configs['compute_nrmse']))
-        if len(get_contexts()) > 1:
-            n, y = evaluation.y.shape[0], evaluation.y
-            est, rmse, nrmse = self._fit_on_devices(
-                evaluation, n, lambda c: _capi.upload_sandi(c, evaluation.KERNELS, self.Rs, self.d_in, self.d_isos),
-                lambda c, l, lo, hi, o: _capi.sandi_fit(c, l, y[lo:hi], self.solver_params['lambda1'], self.solver_params['lambda2'], out=o, **kw),
-                (np.zeros((n, 6)), np.zeros(n) if kw['rmse'] else None, np.zeros(n) if kw['nrmse'] else None))
-        else:
-            est, rmse, nrmse = _capi.sandi_fit(ctx, lut, evaluation.y, self.solver_params['lambda1'], self.solver_params['lambda2'], **kw)
-            self._warn_if_capped(ctx)
-        results = {'estimates': est}
-        if self.configs['compute_rmse']:
-            results['rmse'] = rmse
-        if self.configs['compute_nrmse']:
-            results['nrmse'] = nrmse
-        return results
+        return self._run(evaluation, _capi.FIT['sandi'], lambda c: _capi.upload_sandi(c, evaluation.KERNELS, self.Rs, self.d_in, self.d_isos),
+                         (), self._want())

@@ -69,8 +69,7 @@ class _VolumePipeline:
 
     def _enqueue_signals(self, d_img, stream):
         """image -> y, mean_b0, dirs (everything ahead of the model fit)"""
-        L, c, p = _capi.lib(), self.ctx, self.prep._plan
-        s = _capi.c_vp(stream or 0)
+        c, p = self.ctx, self.prep._plan
         r = self.replace_bad_voxels
         if self.raw_dtype is not None:
             # core.py:136 and the scan of the image in one kernel; everything below reads the float32 image it leaves in self.img
@@ -81,12 +80,11 @@ class _VolumePipeline:
         if self.prep.debias_snr is not None:
             p.debias_device(d_img.data_ptr(), self.prep.debias_snr, stream)
         if self.fused:
-            # one pass over the image: the tensor fit rides on the gather's LDS tile (amx_prep_gather_directions_device_f32)
-            c.check(L.amx_prep_gather_directions_device_f32(c._h, p._h, self.tensor._dti._h, d_img.data_ptr(), int(self.prep.do_normalize), 0.0,
-                                                            self.y.data_ptr(), self.mean_b0.data_ptr(), self.dirs.data_ptr(), s))
+            # one pass over the image: the tensor fit rides on the gather's LDS tile
+            p.gather_directions_device(self.tensor._dti, d_img.data_ptr(), self.y.data_ptr(), self.mean_b0.data_ptr(), self.dirs.data_ptr(),
+                                       self.prep.do_normalize, 0.0, stream)
         else:
-            c.check(L.amx_prep_gather_device_f32(c._h, p._h, d_img.data_ptr(), int(self.prep.do_normalize), 0.0,
-                                                 self.y.data_ptr(), self.mean_b0.data_ptr(), s))
+            p.gather_device(d_img.data_ptr(), self.y.data_ptr(), self.mean_b0.data_ptr(), self.prep.do_normalize, 0.0, stream)
             if r is not None:
                 _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
             self.tensor.fit_device(self.y.data_ptr(), self.n_vox, self.dirs.data_ptr(), stream, f32=True)
@@ -94,10 +92,9 @@ class _VolumePipeline:
             _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
 
     def _enqueue_scatter(self, stream):
-        L, c, p = _capi.lib(), self.ctx, self.prep._plan
-        s = _capi.c_vp(stream or 0)
-        c.check(L.amx_prep_scatter_device(c._h, p._h, self.est.data_ptr(), self.est.shape[1], self.maps.data_ptr(), s))
-        c.check(L.amx_prep_scatter_device(c._h, p._h, self.dirs.data_ptr(), 3, self.dirs_vol.data_ptr(), s))
+        p = self.prep._plan
+        p.scatter_device(self.est.data_ptr(), self.est.shape[1], self.maps.data_ptr(), stream)
+        p.scatter_device(self.dirs.data_ptr(), 3, self.dirs_vol.data_ptr(), stream)
 
     def run(self, d_img, stream=None):
         self.enqueue(d_img, stream)
@@ -132,11 +129,9 @@ class NoddiVolumePipeline(_VolumePipeline):
         holding the elements of that dtype instead (any torch dtype: only its memory is used), which is left as it is; with debias_snr
         set the caller's d_img is OVERWRITTEN first: debiased where mask != 0, zero elsewhere; with replace_bad_voxels set its
         NaN / Inf samples are overwritten before that"""
-        L, c = _capi.lib(), self.ctx
-        s = _capi.c_vp(stream or 0)
         self._enqueue_signals(d_img, stream)
-        c.check(L.amx_noddi_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox,
-                                       self.lambda1, self.lambda2, 0, self.est.data_ptr(), None, None, None, s))
+        _capi._fit_device(_capi.FIT['noddi'], self.ctx, self.lut, self.y, self.dirs, self.lambda1, self.lambda2, (3,), {}, stream, False, False,
+                          into=self.est)
         self._enqueue_scatter(stream)
 
 
@@ -164,20 +159,10 @@ class FreeWaterVolumePipeline(_VolumePipeline):
 
     def enqueue(self, d_img, stream=None):
         """d_img: as for NoddiVolumePipeline.enqueue"""
-        L, c, p = _capi.lib(), self.ctx, self.prep._plan
-        s = _capi.c_vp(stream or 0)
         self._enqueue_signals(d_img, stream)
-        flags = 0
-        if self.want_corrected:
-            c.check(L.amx_set_fw_iso(c._h, self.x_iso.data_ptr()))
-            flags = _capi.F_FW_ISO
-        try:
-            c.check(L.amx_freewater_fit_device_f32(c._h, self.lut._h, self.y.data_ptr(), self.dirs.data_ptr(), self.n_vox, self.lambda1,
-                                                   self.lambda2, int(self.is_mouse), flags, self.est.data_ptr(), None, None, None, s))
-        finally:
-            if self.want_corrected:
-                L.amx_set_fw_iso(c._h, None)
+        _capi._fit_device(_capi.FIT['freewater'], self.ctx, self.lut, self.y, self.dirs, self.lambda1, self.lambda2, (int(self.is_mouse),), {},
+                          stream, False, self.x_iso if self.want_corrected else False, into=self.est)
         self._enqueue_scatter(stream)
         if self.want_corrected:
             rescale = self.prep.do_normalize and self.scheme.b0_count > 0
-            p.corrected_device(self.lut, self.y, self.x_iso, self.corrected, self.mean_b0 if rescale else None, self.b0_cols, stream)
+            self.prep._plan.corrected_device(self.lut, self.y, self.x_iso, self.corrected, self.mean_b0 if rescale else None, self.b0_cols, stream)
