@@ -25,7 +25,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_dir_to_lut_idx', 'amx_noddi_fit', 'amx_freewater_fit', 'amx_sandi_fit',
            'amx_noddi_fit_device', 'amx_freewater_fit_device', 'amx_sandi_fit_device', 'amx_sync_status',
            'amx_noddi_fit_device_f32', 'amx_freewater_fit_device_f32', 'amx_sandi_fit_device_f32', 'amx_czb_fit_device_f32',
-           'amx_set_debug_x', 'amx_set_fw_iso', 'amx_freewater_corrected_device', 'amx_prep_corrected_device', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
+           'amx_set_debug_x', 'amx_set_fw_iso', 'amx_freewater_corrected_device', 'amx_prep_corrected_device', 'amx_predict_device', 'amx_prep_predicted_device', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
            'amx_set_profiling', 'amx_last_kernel_ms', 'amx_last_stats', 'amx_last_seed_stats', 'amx_last_host_narrowed', 'amx_last_path', 'amx_host_pool_info', 'amx_selftest',
            'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
@@ -151,6 +151,8 @@ def lib():
     L.amx_set_fw_iso.argtypes = [c_vp, c_vp]
     L.amx_freewater_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]      # ctx, lut, y32, y64, x_iso, n, ycorr, stream
     L.amx_prep_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, C.c_int, c_vp, c_vp]  # ctx, plan, lut, y32, x_iso, mean_b0, b0_cols (host), n, volume, stream
+    L.amx_predict_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp]      # ctx, lut, x, x_stride, x_offset, dirs, n, y_est, stream
+    L.amx_prep_predicted_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, c_vp]   # ctx, plan, lut, x, x_stride, x_offset, dirs, mean_b0, volume, stream
     L.amx_debug_fetch.argtypes = [c_vp, c_vp, C.c_int, c_vp, C.c_size_t]
     L.amx_set_progress.argtypes = [c_vp, PROGRESS_CB, c_vp]
     L.amx_lut_upload_czb.argtypes = [c_vp, c_fp, c_fp, c_fp, c_dp, c_i16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -608,6 +610,30 @@ def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None):
     return yc
 
 
+def _check_x(lut, x_t, dirs_t, n=None):
+    """(x_stride, x_offset) of a coefficient tensor: f64 [n, n_atoms], or NODDI's AMX_F_DEBUG_X layout [n, 3, n_atoms] (row 2 is taken)"""
+    import torch
+    na = lut.n_atoms
+    if x_t.dtype != torch.float64 or not x_t.is_contiguous() or tuple(x_t.shape[1:]) not in ((na,), (3, na)) or (n is not None and x_t.shape[0] != n):
+        raise ValueError(f'x must be a contiguous float64 device tensor [n_vox, {na}] (or [n_vox, 3, {na}], the NODDI layout of return_x)')
+    if dirs_t is not None and (dirs_t.dtype != torch.float64 or tuple(dirs_t.shape) != (x_t.shape[0], 3) or not dirs_t.is_contiguous()
+                               or dirs_t.device != x_t.device):
+        raise ValueError('DIRs must be a contiguous float64 device tensor [n_vox, 3] on the device of x')
+    return (3 * na, 2 * na) if x_t.dim() == 3 else (na, 0)
+
+
+def predict_device(ctx, lut, x_t, dirs_t=None, stream=None):
+    """the signal the fitted model predicts, y_est = A x, f64 [n, nS] (amx_predict_device): x_t the coefficients a fit with return_x=True
+    left -- f64 [n, n_atoms], or NODDI's [n, 3, n_atoms] whose debiased row is taken --, dirs_t the directions of that fit (None for
+    SANDI); fp64, one rounding per product and sum, atoms ascending.  Device tensors, enqueued on `stream`"""
+    import torch
+    stride, offset = _check_x(lut, x_t, dirs_t)
+    n = x_t.shape[0]
+    ye = torch.empty((n, lut.nS), dtype=torch.float64, device=x_t.device)
+    ctx.check(lib().amx_predict_device(ctx._h, lut._h, _dptr(x_t), stride, offset, _dptr(dirs_t), n, _dptr(ye), c_vp(stream or 0)))
+    return ye
+
+
 class Dict:
     """amx_dict: the dictionaries of the batched solver entry points (cyspams.interfaces.nnls / lasso, models.pyx:18, batched).
     A: [n_dicts, m, n] (or [m, n]) in numpy's own layout -- the column-major m x n slices the C ABI wants are made here."""
@@ -891,6 +917,24 @@ class Prep:
         b0 = np.ascontiguousarray(b0_cols, dtype=np.int32).ravel()
         self.ctx.check(lib().amx_prep_corrected_device(self.ctx._h, self._h, lut._h, _dptr(y_t), _dptr(xiso_t), _dptr(mean_b0_t),
                                                        _p(b0, c_i32p) if len(b0) else None, len(b0), _dptr(volume_t), c_vp(stream or 0)))
+        return volume_t
+
+    def predicted_device(self, lut, x_t, volume_t, dirs_t=None, mean_b0_t=None, stream=None):
+        """RESULTS['DWI_predicted'] in HBM: the coefficients x f64 [n_vox, n_atoms] (or NODDI's [n_vox, 3, n_atoms]) and the directions
+        f64 [n_vox, 3] (None for SANDI), rows in the plan's masked order -> volume f32 [X, Y, Z, n_out] = float32(mean_b0 * A x), zeros
+        outside the mask, every element written once; mean_b0_t f32 [n_vox]: rescale by it (None: no rescaling).  Device tensors,
+        enqueued on `stream` (amx_prep_predicted_device)"""
+        import torch
+        n = self.n_vox
+        stride, offset = _check_x(lut, x_t, dirs_t, n)
+        if mean_b0_t is not None and (mean_b0_t.dtype != torch.float32 or tuple(mean_b0_t.shape) != (n,) or not mean_b0_t.is_contiguous()
+                                      or mean_b0_t.device != x_t.device):
+            raise ValueError(f'mean_b0 must be a contiguous float32 device tensor [{n}] on the device of x')
+        if volume_t.dtype != torch.float32 or tuple(volume_t.shape) != self.shape[:3] + (self.n_out,) or not volume_t.is_contiguous() \
+                or volume_t.device != x_t.device:
+            raise ValueError('volume must be a contiguous float32 device tensor [X, Y, Z, n_out] on the device of x')
+        self.ctx.check(lib().amx_prep_predicted_device(self.ctx._h, self._h, lut._h, _dptr(x_t), stride, offset, _dptr(dirs_t), _dptr(mean_b0_t),
+                                                       _dptr(volume_t), c_vp(stream or 0)))
         return volume_t
 
     def scatter(self, values):

@@ -249,6 +249,8 @@ class Evaluation:
         if self.KERNELS['model'] != self.model.id:
             raise RuntimeError('Response functions were not created with the same model')
         _dti.check_fit_method(self.get_config('DTI_fit_method'))     # core.py:419-420: before anything is uploaded
+        if self.get_config('doSavePredictedSignal') and len(_models.get_contexts()) > 1:
+            raise NotImplementedError('doSavePredictedSignal is not built for several devices (set_devices)')
         nt = self.get_config('nthreads')
         self.nthreads = nt if nt > 0 else cpu_count()
         self.model.scheme = self.scheme
@@ -377,6 +379,19 @@ class Evaluation:
                 if keep_b0:
                     y_corrected[:, b0_idx] = self.y[:, b0_idx] * np.reshape(self.mean_b0s, (-1, 1))
                 self.RESULTS['DWI_corrected'] = self._prep.scatter(y_corrected)
+        if self.get_config('doSavePredictedSignal'):
+            # the fit left its coefficients in HBM: dictionary, x, DIRs (and mean_b0) -> the float32 volume in one kernel, one copy home;
+            # neither y nor the rows results['y_est'] come to the host (amx_prep_predicted_device)
+            rescale = bool(self.get_config('doNormalizeSignal')) and self.scheme.b0_count > 0
+            if 'predict' not in self._dev:
+                raise NotImplementedError("doSavePredictedSignal: this model's fit() left no coefficients in HBM (it does not go through "
+                                          "BaseModel._run)")
+            vol = torch.empty(shape3 + (self._prep.n_out,), dtype=torch.float32, device=dev)
+            p_lut, p_x, p_dirs = self._dev['predict']
+            plan.predicted_device(p_lut, p_x, vol, p_dirs, self._dev['mb0'] if rescale else None)
+            ctx.sync()
+            self.RESULTS['DWI_predicted'] = vol.cpu().numpy()
         self._dev.pop('out', None)
         self._dev.pop('lut', None)
+        self._dev.pop('predict', None)
         return results

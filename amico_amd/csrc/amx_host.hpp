@@ -68,6 +68,7 @@ struct amx_ctx : WorkSet {
     void (*progress)(int64_t, int64_t, void *) = nullptr;   // amx_set_progress
     void *progress_user = nullptr;
     DevBuf wy;                     // float64 copy of float32 device signals for the lane kernels that read float64 only (amx_*_fit_device_f32)
+    DevBuf pred_idx;               // LUT index of every row of the last amx_predict_device / amx_prep_predicted_device call (amx_predict.hip)
     DevBuf hy32;                   // float32 signals of the *_fit_f32 entry points (and of float64 host signals that are float32 values: amx_stage.hpp)
     amx_stage::Pool *stage = nullptr;  // host threads + pinned slots of the lossless float64 -> float32 transport (made at the first large float64 host call)
     std::thread stage_thread;      // makes the pool beside the dictionary upload (prefetch_stage_pool); joined by the first host-buffer fit that needs it
@@ -488,6 +489,7 @@ int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, in
                       double *zero_rows = nullptr, int zero_cols = 0, double *zero_rows2 = nullptr, int zero_cols2 = 0);
 int enqueue_index_bucketing(amx_ctx *ctx, const int32_t *d_idx, int n_dicts, int64_t n, Plan &pl, hipStream_t s);   // the batched solvers' plan
 int enqueue_linear_plan(amx_ctx *ctx, int64_t n, Plan &pl, hipStream_t s);                                          // SANDI's: the voxels in order
+int enqueue_dir_to_lut(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, int *d_idx, hipStream_t s);              // the LUT indices alone (amx_predict.hip)
 void fold_counters(amx_ctx *ctx, hipStream_t s);
 void widen_on_device(const float *d_y32, double *dst, size_t nel, hipStream_t s);
 void clear_events(amx_ctx *ctx);

@@ -192,7 +192,19 @@ void progress_tick(amx_ctx *ctx, hipStream_t s, int64_t done, int64_t total)
     if (hipLaunchHostFunc(s, progress_host_fn, t) != hipSuccess) { (void)hipGetLastError(); delete t; }
 }
 
-// (here, beside the other launch of k_dir_to_lut)
+// the LUT index of every voxel alone, into a buffer of the caller's (amx_predict.hip): no histogram, no plan; a direction out of bounds
+// gives -1 and is reported through the status words like the fit reports it
+int enqueue_dir_to_lut(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, int *d_idx, hipStream_t s)
+{
+    if (!lut->htable) return amx_bad(ctx, "dictionary has no hash table");
+    const int span = prep_span(n);
+    hipLaunchKernelGGL(k_dir_to_lut, dim3((unsigned)((n + span - 1) / span)), dim3(1024), 0, s, d_dirs, (int)n, lut->htable, lut->ndirs, d_idx,
+                       (int *)nullptr, ctx->status_d, 0, 0, span, (double *)nullptr, 0, (double *)nullptr, 0);
+    HIPCHK(ctx, hipGetLastError());
+    return AMX_OK;
+}
+
+// (here, beside the other launches of k_dir_to_lut)
 extern "C" int amx_dir_to_lut_idx(amx_ctx *ctx, const amx_lut *lut, const double *dirs, int64_t n, int32_t *out_idx)
 {
     if (!ctx) return AMX_E_BADARG;

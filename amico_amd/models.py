@@ -143,27 +143,25 @@ def _verified_fit(fit):
 
 
 class _LazyResults(dict):
-    """The dict a fit returns, with ONE value that is made when it is first read (FreeWater's device-resident fit holds `y_corrected`
-    this way: Evaluation.fit() builds the corrected volume on the GPU and never reads the rows).  `key in results`, `keys()`,
-    iteration and `len()` see the key from the start and make nothing; every way of reading the value -- `results[key]`, `get`, `pop`,
-    `values()`, `items()`, `copy()`, `dict(results)`, `{**results}`, `==` -- runs the thunk first, once, and keeps what it returns."""
+    """The dict a fit returns, with values that are made when they are first read (FreeWater's device-resident fit holds `y_corrected`
+    this way, every model's `y_est`: Evaluation.fit() builds the volumes on the GPU and never reads the rows).  `key in results`, `keys()`,
+    iteration and `len()` see the key from the start and make nothing; reading one value -- `results[key]`, `get`, `pop` -- runs its thunk
+    first, once, and keeps what it returns; `values()`, `items()`, `copy()`, `dict(results)`, `{**results}`, `==` do so for all of them."""
 
     def __init__(self, *args, **kwargs):
         super().__init__(*args, **kwargs)
-        self._lazy = None                    # (key, thunk) until the value is made or replaced
+        self._lazy = {}                      # key -> thunk until the value is made or replaced
 
     def set_lazy(self, key, thunk):
         dict.__setitem__(self, key, None)
-        self._lazy = (key, thunk)
+        self._lazy[key] = thunk
 
     def _force(self, key=None):
-        if self._lazy is not None and key in (None, self._lazy[0]):
-            (k, thunk), self._lazy = self._lazy, None
-            dict.__setitem__(self, k, thunk())
+        for k in ([key] if key in self._lazy else list(self._lazy) if key is None else []):
+            dict.__setitem__(self, k, self._lazy.pop(k)())
 
     def _drop(self, key):
-        if self._lazy is not None and self._lazy[0] == key:
-            self._lazy = None
+        self._lazy.pop(key, None)
 
     def __getitem__(self, key):
         self._force(key)
@@ -312,15 +310,26 @@ class BaseModel(ABC):
         arguments behind lambda2; want: keyword -> bool of the optional outputs (dev_want: the same for device-resident signals, when
         it differs); dev_tail(ctx, lut, dev, out, results) -> results: the model's own last step of the device-resident branch"""
         ctx = get_context()
+        dev = getattr(evaluation, '_dev', None)
+        # doSavePredictedSignal (not a key of the reference): the signal the fitted model predicts, results['y_est'] / RESULTS['DWI_predicted']
+        predict = bool(evaluation.get_config('doSavePredictedSignal'))
+        if predict and (dev is None or len(get_contexts()) > 1):
+            raise NotImplementedError('doSavePredictedSignal needs the signals Evaluation.fit() left on one GPU: it is not built for an '
+                                      'assigned evaluation.y or for several devices (set_devices)')
         lut = self._lut(evaluation, lambda: upload(ctx))
         lambdas = (self.solver_params['lambda1'], self.solver_params['lambda2'])
         names = [o.name for o in row.outputs]
-        dev = getattr(evaluation, '_dev', None)
         if dev is not None:
             dirs = (self._dev_dirs(evaluation, dev),) if row.dirs else ()
-            out = getattr(_capi, row.stem + '_fit_device')(ctx, lut, dev['y'], *dirs, *lambdas, *extras, **(dev_want or want))
+            more = dict(return_x=True) if predict else {}       # (AMX_F_DEBUG_X selects no path: the same kernels, and they write x)
+            out = getattr(_capi, row.stem + '_fit_device')(ctx, lut, dev['y'], *dirs, *lambdas, *extras, **(dev_want or want), **more)
+            x = None
+            if predict:                                          # (the coefficients come back right behind the row's outputs)
+                x, out = out[len(names)], out[:len(names)] + out[len(names) + 1:]
             results = self._finish_device(ctx, dev, dict(zip(names, out)))
-            return results if dev_tail is None else dev_tail(ctx, lut, dev, out, results)
+            if dev_tail is not None:
+                results = dev_tail(ctx, lut, dev, out, results)
+            return results if x is None else self._lazy_predicted(ctx, lut, dev, x, dirs[0] if dirs else None, results)
         fit, y, d = getattr(_capi, row.stem + '_fit'), evaluation.y, evaluation.DIRs
         on = [o.key is None or want[o.key] for o in row.outputs]
         if len(get_contexts()) > 1:
@@ -333,6 +342,24 @@ class BaseModel(ABC):
             outs = fit(ctx, lut, y, *((d,) if row.dirs else ()), *lambdas, *extras, **want)
             self._warn_if_capped(ctx)
         return {name: a for name, a, k in zip(names, outs, on) if k}
+
+    @staticmethod
+    def _lazy_predicted(ctx, lut, dev, x, dirs, results):
+        """results['y_est'] f64 [n_vox, nS] = A x (what _compute_rmse takes the residual of, models.pyx:47-71), made by
+        amx_predict_device when it is first read; the coefficients and the dictionary stay in `dev` for Evaluation.fit's volume"""
+        if not isinstance(results, _LazyResults):
+            results = _LazyResults(results)
+        dev['predict'] = (lut, x, dirs)
+
+        def rows():
+            if getattr(ctx, '_h', None) is None or getattr(lut, '_h', None) is None:
+                raise RuntimeError("results['y_est'] of this fit was not read before its GPU context / dictionary was closed "
+                                   "(reset_context()): read it first, or fit again")
+            ye = _capi.predict_device(ctx, lut, x, dirs)
+            ctx.sync()
+            return ye.cpu().numpy()
+        results.set_lazy('y_est', rows)
+        return results
 
     # ---- device-resident inputs: Evaluation.fit leaves `y` (and `DIRs`) in HBM (evaluation._dev) when it produced
     #      them on the GPU; the fit then reads them in place and keeps its outputs there for the scatter

@@ -220,6 +220,32 @@ int amx_freewater_corrected_device(amx_ctx *ctx, const amx_lut *lut, const float
                                    int64_t n_vox, double *d_ycorr, void *hip_stream);
 /* (volume form: amx_prep_corrected_device, beside amx_prep_scatter_device below) */
 
+/* ---- the signal the fitted model predicts, y_est = A x: what _compute_rmse / _compute_nrmse take the residual of and then drop
+ * (models.pyx:47-71, called at :640, :971, :1259, :1615).  No counterpart in the reference's results; here it is made from what a fit
+ * leaves in HBM -- the dictionary `lut` and the coefficient vectors AMX_F_DEBUG_X wrote (amx_set_debug_x) -- by one streaming kernel:
+ *     y_est[i][s] = sum_j A_i[s][j] * x_i[j]
+ *   NODDI      A_i = un-normalised [wm(lut_idx) | (dot) | iso], x_i = the debiased coefficients (row 2 of the AMX_F_DEBUG_X layout)
+ *   FreeWater  A_i = [D(lut_idx) | CSF],                         x_i = the lasso solution
+ *   SANDI      A_i = KERNELS['signal'],                          x_i = the coefficients rescaled by `norms` (the quirk of
+ *              models.pyx:1570-1571 that the error maps reproduce: the prediction is the thing RMSE is the residual of)
+ *   CZB        A_i = [wmr | wmh | iso] of the orientation,       x_i = the lasso solution
+ * Row i's coefficients are d_x[i * x_stride + x_offset + j], j < n_atoms, counted in doubles: 3 * n_atoms and 2 * n_atoms for NODDI on
+ * the debug buffer, n_atoms and 0 for the other models (and for a plain [n][n_atoms] buffer).  d_dirs f64[n_vox][3]: the directions
+ * the fit was given (lut.pyx:316-356 picks the orientation); NULL for SANDI, which has one dictionary.
+ * Arithmetic, per sample: fp64, atoms in ascending order, every product and every sum rounded on its own (no fused multiply-add):
+ *     acc = 0; for j: acc = acc + (double)A[s][j] * x[j]
+ * bit for bit; atoms whose coefficient is exactly 0 are skipped (adding +-0 changes nothing), a NaN coefficient is not zero: it makes the
+ * whole row NaN, as that voxel's maps are.  A voxel whose direction is out of bounds gets a row of zeros, as its maps do (and the next
+ * amx_sync_status reports it, as after the fit).  Coefficient vectors of any density are computed in full: the kernel keeps up to 16
+ * non-zeros per voxel on chip and walks the dense vector for a voxel that has more.
+ * Device pointers, enqueued on hip_stream, no synchronisation; calls on one ctx are to be enqueued on one stream at a time (they
+ * share the ctx's LUT-index buffer, like the fits share its workspace).  AMX_E_BADARG with a message: a NULL pointer, d_dirs with a
+ * dictionary of a model without directions or no d_dirs with any other, x_stride < x_offset + n_atoms.
+ * rows form:   -> d_yest f64[n_vox][nS], one coalesced row per voxel. */
+int amx_predict_device(amx_ctx *ctx, const amx_lut *lut, const double *d_x, int64_t x_stride, int64_t x_offset, const double *d_dirs,
+                       int64_t n_vox, double *d_yest, void *hip_stream);
+/* (volume form: amx_prep_predicted_device, beside amx_prep_corrected_device below) */
+
 /* ---- diagnosis / tests of the support seeds (csrc/amx_seed.hpp; no counterpart in the reference): copies a workspace
  * buffer of the LAST NODDI fit of this ctx -- which = 0: voxel permutation int32[n] (bucket order), 1: projected signals
  * f64[n][12] (bucket order), 2: support seeds uint64[n] (bucket order; up to 8 atom ids, one per byte, >= 0xf0 = empty;
@@ -366,6 +392,13 @@ int amx_prep_scatter_device(amx_ctx *ctx, const amx_prep *p, const double *d_val
  *              once and no memset precedes it. */
 int amx_prep_corrected_device(amx_ctx *ctx, const amx_prep *p, const amx_lut *lut, const float *d_y32, const double *d_xiso,
                               const float *d_mean_b0, const int32_t *b0_cols, int n_b0_cols, float *d_volume, void *hip_stream);
+
+/* The predicted signal, volume form (rows form, arithmetic: amx_predict_device) -> d_volume f32[X][Y][Z][n_out] (C order; n_out = the
+ *              plan's prepared volumes = the dictionary's nS; d_x / d_dirs rows in the plan's masked order).  A masked voxel of rank r
+ *              gets out[s] = (float)(m * y_est[r][s]) with m = (double)d_mean_b0[r], or 1 when d_mean_b0 is NULL; every other voxel
+ *              gets zeros from this same kernel: each element of the volume is written exactly once and no memset precedes it. */
+int amx_prep_predicted_device(amx_ctx *ctx, const amx_prep *p, const amx_lut *lut, const double *d_x, int64_t x_stride, int64_t x_offset,
+                              const double *d_dirs, const float *d_mean_b0, float *d_volume, void *hip_stream);
 
 /* (f0) Rician debias of the raw signal, core.py:201-206 (doDebiasSignal, DWI-SNR) -> preproc.py:23-36 `debiasRician`:
  *     per voxel with mask != 0:  sigma = DWI[ix,iy,iz,b0_idx].mean() / SNR;  E = argmin_E sum_i (S_i - mu(E_i))^2  from E = S,
