@@ -1,4 +1,5 @@
-// amx_fw.hip -- FreeWater solver kernel (models.pyx:1231-1276)
+// amx_fw.hip -- FreeWater (models.pyx:1231-1276): which solver a fit takes.  Here the wavefront-per-voxel kernel (amx_kernels.hpp);
+// the lane-per-voxel kernels of the small dictionaries, the fast path, are in amx_fw_lane.hip
 #include "amx_launch.hpp"
 using namespace amx;
 

@@ -1,235 +1,8 @@
-// amx_small.hip -- FreeWater / SANDI fit for small dictionaries (n_atoms <= 16): ONE VOXEL PER LANE.
-//
-// models.pyx:1231-1276 (FreeWater) and :1567-1619 (SANDI) solve, per voxel,
-//     min_x 1/2||y - A x||^2 + lambda1*sum(x) + lambda2/2*||x||^2 ,  x >= 0      (cyspams lasso)
-// with 11..15 atoms and lambda2 > 0.  A wavefront per voxel (amx_solver.hpp) leaves most lanes idle
-// on such problems, so this unit maps one voxel to one LANE:
-//   * the workgroup's voxels share one orientation (bucketing) => A (nS x n) and the regularised
-//     Gram matrix H = A'A + lambda2*I (n x n, built by the workgroup itself in its prologue) sit in
-//     LDS and are read with wave-uniform (broadcast) addresses;
-//   * each lane forms c = A'y from its own signal row and runs a Lawson-Hanson active set on
-//     (H, c) entirely in registers: the passive set is a bit mask, the passive system is solved by a
-//     MASKED Cholesky factorisation (rows/columns outside the set replaced by identity), all loops
-//     are fully unrolled over the compile-time dictionary size => no cross-lane traffic, and lane
-//     divergence is plain SIMT predication.
-// H is well conditioned thanks to the ridge (cond <= ~1e6 for AMICO's defaults), so Gram space is
-// safe here (it is NOT for NODDI's unregularised NNLS stages).
-#include "amx_launch.hpp"
-using namespace amx;
+// amx_fw_lane.hip -- FreeWater, one voxel per lane (amx_lane_qp.hpp): k_freewater_lane, and the fast path for maps only --
+// per-orientation tables, projection, solver with refill (k_freewater_refill), or all in one kernel (k_freewater_fused)
+#include "amx_lane_qp.hpp"
 
 namespace {
-
-template <int N>
-__device__ __forceinline__ constexpr int tri(int i, int j) { return i * (i + 1) / 2 + j; }
-
-// x / d for well-scaled operands (no denormal / overflow handling: v_rcp_f64, two Newton steps, one residual correction;
-// ~9 instructions against ~35 of the IEEE sequence, within 1 ulp)
-__device__ __forceinline__ double fast_div(double x, double d)
-{
-    double r = __builtin_amdgcn_rcp(d);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    r = __builtin_fma(__builtin_fma(-d, r, 1.0), r, r);
-    const double q = x * r;
-    return __builtin_fma(__builtin_fma(-d, q, x), r, q);
-}
-
-// H / the dictionary are loop invariant: without these barriers the compiler keeps their entries in vector registers
-// across the fully unrolled passes (hundreds of VGPRs) and spills everything else
-#define AMX_RELOAD() asm volatile("" ::: "memory")
-
-// Cholesky of H restricted to P and the two triangular solves: z = H_PP^-1 cc_P (0 elsewhere).
-// The restriction costs ONE select per column: ivm_j = 1 / L_jj for j in P, 0 otherwise.  A zero ivm_j zeroes column j of
-// the factor (so no row of P ever sees atom j) and z_j in both substitutions.  Row j itself is then computed from whatever
-// the arithmetic gives (finite: sums of products of bounded entries; a negative pivot only feeds the discarded rsqrt) --
-// nothing reads it, because every use of row j is multiplied by ivm_j or by z_j = 0.
-template <int N>
-__device__ __forceinline__ void lane_solve(const double *__restrict__ Hs, const double (&cc)[N], unsigned P, double (&z)[N])
-{
-    double L[N * (N + 1) / 2], ivm[N];
-    AMX_RELOAD();
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double s = Hs[j * N + j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= L[tri<N>(j, k)] * L[tri<N>(j, k)];
-        const double iv = ((P >> j) & 1u) ? rsqrt(s) : 0.0;
-        ivm[j] = iv;
-#pragma unroll
-        for (int i = j + 1; i < N; i++) {
-            double tt = Hs[i * N + j];
-#pragma unroll
-            for (int k = 0; k < j; k++) tt -= L[tri<N>(i, k)] * L[tri<N>(j, k)];
-            L[tri<N>(i, j)] = tt * iv;
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        double s = cc[j];
-#pragma unroll
-        for (int k = 0; k < j; k++) s -= L[tri<N>(j, k)] * z[k];
-        z[j] = s * ivm[j];
-    }
-#pragma unroll
-    for (int j = N - 1; j >= 0; j--) {
-        double s = z[j];
-#pragma unroll
-        for (int i = j + 1; i < N; i++) s -= L[tri<N>(i, j)] * z[i];
-        z[j] = s * ivm[j];
-    }
-}
-
-// per-lane NNQP: min 1/2 x'Hx - cc'x, x >= 0 (cc = c - lambda1); Hs in LDS, row-major N x N.
-// warm: start from all n_atoms atoms and drop the non-positive ones in blocks before the Lawson-Hanson loop takes over
-// (unique optimum with the ridge; see lane_nnqp_rows).  returns 0, or 2 if an iteration cap tripped.
-template <int N>
-__device__ __forceinline__ int lane_nnqp(const double *__restrict__ Hs, const double (&cc)[N], double (&x)[N],
-                                         int n_atoms = N, bool warm = false)
-{
-    const double tol = 1e-12, inf = __builtin_huge_val();
-    double z[N];
-    unsigned P = 0u;
-    int status = 0;
-#pragma unroll
-    for (int j = 0; j < N; j++) x[j] = 0.0;
-    if (warm) {
-        P = (1u << n_atoms) - 1u;
-        for (int round = 0; round < N && P != 0u; ++round) {
-            lane_solve<N>(Hs, cc, P, z);
-            unsigned negm = 0u;
-#pragma unroll
-            for (int j = 0; j < N; j++)
-                if (((P >> j) & 1u) && !(z[j] > 0.0)) negm |= 1u << j;
-            if (negm == 0u) {
-#pragma unroll
-                for (int j = 0; j < N; j++) x[j] = ((P >> j) & 1u) ? z[j] : 0.0;
-                break;
-            }
-            P &= ~negm;
-        }
-    }
-    for (int it = 0; status == 0; ++it) {
-        if (it > 3 * N + 8) { status = 2; break; }
-        // dual vector g = cc - H x, most violating atom outside the passive set
-        AMX_RELOAD();
-        double best = -inf;
-        int t = -1;
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            double g = cc[j];
-#pragma unroll
-            for (int k = 0; k < N; k++) g -= Hs[j * N + k] * x[k];
-            if (!((P >> j) & 1u) && g > best) { best = g; t = j; }
-        }
-        if (!(best > tol)) break;               // KKT point
-        P |= 1u << t;
-        for (int in = 0;; ++in) {
-            if (in > N + 2) { status = 2; break; }
-            lane_solve<N>(Hs, cc, P, z);
-            bool feasible = true;
-#pragma unroll
-            for (int j = 0; j < N; j++)
-                if (((P >> j) & 1u) && !(z[j] > 0.0)) feasible = false;
-            if (feasible) {
-#pragma unroll
-                for (int j = 0; j < N; j++) x[j] = ((P >> j) & 1u) ? z[j] : 0.0;
-                break;
-            }
-            double alpha = inf;
-            int jm = -1;
-#pragma unroll
-            for (int j = 0; j < N; j++) {
-                if (((P >> j) & 1u) && !(z[j] > 0.0)) {
-                    const double den = x[j] - z[j];
-                    const double r = (den > 0.0) ? x[j] / den : 0.0;
-                    if (r < alpha) { alpha = r; jm = j; }
-                }
-            }
-#pragma unroll
-            for (int j = 0; j < N; j++) {
-                if ((P >> j) & 1u) {
-                    x[j] += alpha * (z[j] - x[j]);
-                    if (j == jm || !(x[j] > 0.0)) { x[j] = 0.0; P &= ~(1u << j); }
-                }
-            }
-            if (P == 0u) break;
-        }
-    }
-    return status;
-}
-
-// workgroup prologue: tile -> LDS, H = A'A + lambda2*I (identity on the padding atoms)
-template <int N, typename AT>
-__device__ __forceinline__ void small_prologue(const AT *__restrict__ tile, int words, AT *As, double *Hs, int nS,
-                                               int ldA, int n_atoms, double lam2)
-{
-    for (int k = threadIdx.x; k < words; k += blockDim.x) As[k] = tile[k];
-    __syncthreads();
-    for (int e = threadIdx.x; e < N * N; e += blockDim.x) {
-        const int j = e / N, k = e % N;
-        double acc = (j == k) ? ((j < n_atoms) ? lam2 : 1.0) : 0.0;
-        if (j < n_atoms && k < n_atoms)
-            for (int i = 0; i < nS; i++) acc += (double)As[i * ldA + j] * (double)As[i * ldA + k];
-        Hs[e] = acc;
-    }
-    __syncthreads();
-}
-
-// c = A'y for this lane's voxel (+ sum y^2); A read with wave-uniform LDS addresses
-template <int N, typename AT>
-__device__ __forceinline__ bool lane_aty(const AT *As, const double *__restrict__ yv, int nS, int ldA, int n_atoms,
-                                         double (&c)[N], double &ysq)
-{
-    bool finite = true;
-    ysq = 0.0;
-#pragma unroll
-    for (int j = 0; j < N; j++) c[j] = 0.0;
-    // the lane's signal row is strided in memory (one cache line per lane and load): keep sixteen loads in flight
-    int i = 0;
-    for (; i + 16 <= nS; i += 16) {
-        double yb[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) yb[u] = yv[i + u];
-#pragma unroll
-        for (int u = 0; u < 16; u++) {
-            const double yi = yb[u];
-            finite = finite && (fabs(yi) <= 1.79769313486231570e308);
-            ysq += yi * yi;
-#pragma unroll
-            for (int j = 0; j < N; j++)
-                if (j < n_atoms) c[j] += (double)As[(i + u) * ldA + j] * yi;
-        }
-    }
-    for (; i < nS; i++) {
-        const double yi = yv[i];
-        finite = finite && (fabs(yi) <= 1.79769313486231570e308);
-        ysq += yi * yi;
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < n_atoms) c[j] += (double)As[i * ldA + j] * yi;
-    }
-    return finite;
-}
-
-template <int N, typename AT>
-__device__ __forceinline__ double lane_rss(const AT *As, const double *__restrict__ yv, int nS, int ldA, int n_atoms,
-                                           const double (&x)[N])
-{
-    double rss = 0.0;
-    for (int i = 0; i < nS; i++) {
-        double e = yv[i];
-#pragma unroll
-        for (int j = 0; j < N; j++)
-            if (j < n_atoms) e -= (double)As[i * ldA + j] * x[j];
-        rss += e * e;
-    }
-    return rss;
-}
-
-#define AMX_SMALL_LDS(AT)                                                                        \
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_s[];                      \
-    const int words = a.c.nS * a.c.ldA;                                                          \
-    AT *As = reinterpret_cast<AT *>(smem_s);                                                     \
-    double *Hs = reinterpret_cast<double *>(smem_s + (((size_t)words * sizeof(AT) + 15) & ~(size_t)15));
 
 template <int N>
 __global__ void __launch_bounds__(256) k_freewater_lane(const FwArgs a)
@@ -294,342 +67,6 @@ __global__ void __launch_bounds__(256) k_freewater_lane(const FwArgs a)
                 const double yc = yv[i] - fw;
                 a.ycorr[(size_t)vox * nS + i] = yc < 0.0 ? 0.0 : yc;
             }
-        }
-    }
-}
-
-template <int N>
-__global__ void __launch_bounds__(256) k_sandi_lane(const SandiArgs a)
-{
-    AMX_SMALL_LDS(double)
-    const int cid = xcd_chunk((int)blockIdx.x, *a.c.n_chunks);
-    if (cid < 0) return;
-    const Chunk ck = a.c.chunks[cid];
-    const int nS = a.c.nS, ldA = a.c.ldA, n_atoms = a.c.n_atoms, n_rs = a.n_rs, n_in = a.n_in;
-    small_prologue<N, double>(reinterpret_cast<const double *>(a.c.tiles), words, As, Hs, nS, ldA, n_atoms, a.c.lam2);
-    for (int v = threadIdx.x; v < ck.count; v += blockDim.x) {
-        const int vox = a.c.perm[ck.start + v];
-        const double *yv = a.c.y + (size_t)vox * nS;
-        double c[N], x[N], ysq;
-        const bool ok = lane_aty<N, double>(As, yv, nS, ldA, n_atoms, c, ysq);
-        double *e = a.est + (size_t)vox * 6;
-        if (!ok) {
-            const double nan = __builtin_nan("");
-            for (int m = 0; m < 6; m++) e[m] = nan;
-            if (a.rmse) a.rmse[vox] = nan;
-            if (a.nrmse) a.nrmse[vox] = nan;
-            continue;
-        }
-#pragma unroll
-        for (int j = 0; j < N; j++) c[j] -= a.c.lam1;
-        if (lane_nnqp<N>(Hs, c, x, n_atoms, amx_warm_start(a.c.lam2, a.c.flags)) != 0) atomicAdd(&a.c.status[ST_ITCAP], 1);
-        // models.pyx:1570-1612
-        double x_sum = 0.0, xsph = 0.0, xstk = 0.0, xiso = 0.0, Rsoma = 0.0, Din = 0.0, De = 0.0;
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            if (j < n_atoms) {
-                x[j] *= a.norms[j];
-                x_sum += x[j];
-                if (j < n_rs) { xsph += x[j]; Rsoma += a.Rs[j] * x[j]; }
-                else if (j < n_rs + n_in) { xstk += x[j]; Din += a.d_in[j - n_rs] * x[j]; }
-                else { xiso += x[j]; De += a.d_isos[j - n_rs - n_in] * x[j]; }
-            }
-        }
-        if (a.c.xdbg) {                                   // the rescaled x (models.pyx:1570-1571)
-#pragma unroll
-            for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
-        }
-        x_sum += 1e-16;
-        e[0] = fast_div(xsph, x_sum); e[1] = fast_div(xstk, x_sum); e[2] = fast_div(xiso, x_sum);
-        e[3] = 1e6 * fast_div(Rsoma, xsph + 1e-16);
-        e[4] = 1e3 * fast_div(Din, xstk + 1e-16);
-        e[5] = 1e3 * fast_div(De, xiso + 1e-16);
-        if (a.rmse || a.nrmse) {
-            // quirk kept (models.pyx:1571 then 1615): errors use the RESCALED x with the NORMALISED A
-            const double rss = lane_rss<N, double>(As, yv, nS, ldA, n_atoms, x);
-            if (a.rmse) a.rmse[vox] = sqrt(rss / (double)nS);
-            if (a.nrmse) a.nrmse[vox] = (ysq > 1e-16) ? sqrt(rss / ysq) : 0.0;
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
-// Row-space solver of the SANDI problem (M = 6 values per voxel after the directional average, N = 15 atoms, ONE dictionary
-// for all voxels):  min 1/2 ||y - A x||^2 + lambda1 sum(x) + lambda2/2 ||x||^2, x >= 0, lambda2 > 0.
-// On a passive set P the solution is x_P = (c_P - A_P' w) / lambda2 with w = B^-1 A_P c_P, B = lambda2 I + A_P A_P' (Woodbury:
-// a 6 x 6 Cholesky instead of a |P| x |P| one).  For j outside P the same expression is the dual value: A_P x_P = w exactly,
-// so g_j = c_j - a_j'w -- the KKT test and the choice of the entering atom cost nothing extra.
-// Tables of the dictionary (k_sandi_tables, once per (dictionary, lambda1, lambda2)), read with wave-uniform addresses (scalar loads):
-//   T [N][kRowsTs]  packed lower triangles of a_j a_j'          (B is summed from them: no +- drift, half the arithmetic)
-//   G [N][M], g0 [N]  z0 = G y + g0 = the unconstrained optimum on the FULL set (G = A' (lambda2 I + A A')^-1)
-// Warm start: SANDI's optimum is dense (12 of 15 atoms), so the method starts from P0 = {z0 > 0} -- the full-set solve and
-// the first block removal are one tabulated map -- and continues by block principal pivoting (below).  With lambda2 > 0
-// the optimum is unique, so the path does not matter; the result satisfies the KKT conditions to 1e-12.
-constexpr int kRowsTs = 22;                // stride of T: 21 entries of the 6 x 6 triangle, padded for 16-byte reads
-
-template <int M, int N, typename TP>
-__device__ __forceinline__ int lane_nnqp_rows(TP A, int ldA, TP T, TP G, TP g0, const double (&y)[M],
-                                              double lam1, double lam2, double (&x)[N], int n_atoms, bool warm)
-{
-    static_assert(M * (M + 1) / 2 <= kRowsTs, "triangle of a_j a_j' fits its table row");
-    constexpr int kTri = M * (M + 1) / 2;
-    const double tol = 1e-12, il2 = 1.0 / lam2;
-    // c = A'y - lambda1 is never stored (15 doubles = 30 registers the Cholesky would have to live with): c_j is recomputed for
-    // the atoms that change sides (below), the dual values are g_j = a_j'(y - w) - lambda1.
-    unsigned P = 0u;
-    AMX_RELOAD();
-#pragma unroll
-    for (int j = 0; j < N; j++) {
-        x[j] = 0.0;
-        double sz = g0[j];
-#pragma unroll
-        for (int i = 0; i < M; i++) sz += G[j * M + i] * y[i];
-        if (warm && j < n_atoms && sz > 0.0) P |= 1u << j;
-    }
-    constexpr int kBackup = 3;               // block exchanges allowed without progress (Kim & Park)
-    int ninf = N + 1, backup = 0;
-    // A_P A_P' and the right-hand side A_P c_P are CARRIED from trip to trip: only the atoms that changed sides are added or
-    // subtracted (rank-one terms from the table, a_j c_j with c_j = a_j'y - lambda1 recomputed on the spot).  The branch per atom
-    // is wave-uniform (ballot over the lanes still iterating): in the late trips of a lock-step wavefront few lanes are left and
-    // they exchange one or two atoms each.  (+- accumulation: a handful of updates per voxel, errors of 1e-16 relative.)
-    double Bp[kTri], rp[M];
-#pragma unroll
-    for (int t = 0; t < kTri; t++) Bp[t] = 0.0;
-#pragma unroll
-    for (int i = 0; i < M; i++) rp[i] = 0.0;
-    unsigned flips = P;
-    for (int it = 0;; ++it) {
-        if (it > 4 * N + 16) return 2;
-        double B[kTri], L[kTri], li[M], w[M];
-        AMX_RELOAD();
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            const bool fj = (flips >> j) & 1u;
-            if (__ballot(fj) != 0ull) {
-                const double dj = fj ? (((P >> j) & 1u) ? 1.0 : -1.0) : 0.0;
-                double cj = -lam1;
-#pragma unroll
-                for (int i = 0; i < M; i++) cj += A[i * ldA + j] * y[i];
-                cj *= dj;
-#pragma unroll
-                for (int t = 0; t < kTri; t++) Bp[t] += dj * T[j * kRowsTs + t];
-#pragma unroll
-                for (int i = 0; i < M; i++) rp[i] += cj * A[i * ldA + j];
-            }
-        }
-#pragma unroll
-        for (int t = 0; t < kTri; t++) B[t] = Bp[t];
-#pragma unroll
-        for (int i = 0; i < M; i++) { w[i] = rp[i]; B[tri<M>(i, i)] += lam2; }
-#pragma unroll
-        for (int j = 0; j < M; j++) {
-            double d = B[tri<M>(j, j)];
-#pragma unroll
-            for (int k = 0; k < j; k++) d -= L[tri<M>(j, k)] * L[tri<M>(j, k)];
-            const double iv = rsqrt(d);
-            li[j] = iv;
-#pragma unroll
-            for (int i = j + 1; i < M; i++) {
-                double tt = B[tri<M>(i, j)];
-#pragma unroll
-                for (int k = 0; k < j; k++) tt -= L[tri<M>(i, k)] * L[tri<M>(j, k)];
-                L[tri<M>(i, j)] = tt * iv;
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < M; j++) {
-            double sacc = w[j];
-#pragma unroll
-            for (int k = 0; k < j; k++) sacc -= L[tri<M>(j, k)] * w[k];
-            w[j] = sacc * li[j];
-        }
-#pragma unroll
-        for (int j = M - 1; j >= 0; j--) {
-            double sacc = w[j];
-#pragma unroll
-            for (int i = j + 1; i < M; i++) sacc -= L[tri<M>(i, j)] * w[i];
-            w[j] = sacc * li[j];
-        }
-        AMX_RELOAD();
-        // block principal pivoting: passive atoms with a non-positive coefficient leave, inactive atoms with a positive dual
-        // value enter, all at once while the number of infeasibilities keeps falling (then kBackup more times); otherwise only
-        // the infeasible atom with the largest index is exchanged (Murty's rule).  (Launched with the warm start only: smaller
-        // lambda2 / flag bit 31 (cold start) go to k_sandi_lane's Lawson-Hanson loop, amx_launch_sandi_small.)
-        unsigned v1 = 0u, v2 = 0u;
-#pragma unroll
-        for (int i = 0; i < M; i++) w[i] = y[i] - w[i];
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            double g = -lam1;
-#pragma unroll
-            for (int i = 0; i < M; i++) g += A[i * ldA + j] * w[i];
-            const bool pj = (P >> j) & 1u;
-            x[j] = pj ? g * il2 : 0.0;
-            if (pj && !(g > 0.0)) v1 |= 1u << j;
-            if (!pj && j < n_atoms && g > tol) v2 |= 1u << j;
-        }
-        const unsigned bad = v1 | v2;
-        if (bad == 0u) return 0;                                   // KKT point: x holds the solution
-        const int nbad = __builtin_popcount(bad);
-        bool block = false;
-        if (nbad < ninf) { ninf = nbad; backup = warm ? kBackup : 0; block = warm; }
-        else if (backup > 0) { backup--; block = true; }
-        flips = block ? bad : (1u << (31 - __builtin_clz(bad)));
-        P ^= flips;
-    }
-}
-
-// T, G, g0 of one dictionary and one (lambda1, lambda2): one workgroup, thread 0 inverts the 6 x 6 (Gauss-Jordan on the SPD
-// matrix, no pivoting needed).  out: T [N][kRowsTs] | G [N][M] | g0 [16] | A [M][16] (zero-padded rows)
-template <int M, int N>
-__global__ void __launch_bounds__(64) k_sandi_tables(const double *__restrict__ Ag, int ldA, int n_atoms, double lam1, double lam2,
-                                                     double *__restrict__ out)
-{
-    __shared__ double A[M * 16], W[M * M], Bm[M * 2 * M];
-    for (int e = threadIdx.x; e < M * 16; e += blockDim.x) A[e] = ((e % 16) < n_atoms) ? Ag[(e / 16) * ldA + (e % 16)] : 0.0;
-    __syncthreads();
-    double *T = out, *G = out + N * kRowsTs, *g0 = G + N * M;
-    for (int e = threadIdx.x; e < M * 16; e += blockDim.x) g0[16 + e] = A[e];                // the dictionary, rows padded to 16
-    for (int e = threadIdx.x; e < N * kRowsTs; e += blockDim.x) {
-        const int j = e / kRowsTs, t = e % kRowsTs;
-        int i = 0;
-        while ((i + 1) * (i + 2) / 2 <= t) i++;                 // t = i (i + 1) / 2 + k
-        const int k = t - i * (i + 1) / 2;
-        T[e] = (t < M * (M + 1) / 2) ? A[i * 16 + j] * A[k * 16 + j] : 0.0;
-    }
-    if (threadIdx.x == 0) {
-        for (int i = 0; i < M; i++)
-            for (int k = 0; k < M; k++) {
-                double acc = (i == k) ? lam2 : 0.0;
-                for (int j = 0; j < N; j++) acc += A[i * 16 + j] * A[k * 16 + j];
-                Bm[i * 2 * M + k] = acc; Bm[i * 2 * M + M + k] = (i == k) ? 1.0 : 0.0;
-            }
-        for (int c0 = 0; c0 < M; c0++) {
-            const double pv = 1.0 / Bm[c0 * 2 * M + c0];
-            for (int k = 0; k < 2 * M; k++) Bm[c0 * 2 * M + k] *= pv;
-            for (int i = 0; i < M; i++)
-                if (i != c0) {
-                    const double f = Bm[i * 2 * M + c0];
-                    for (int k = 0; k < 2 * M; k++) Bm[i * 2 * M + k] -= f * Bm[c0 * 2 * M + k];
-                }
-        }
-        for (int i = 0; i < M; i++) for (int k = 0; k < M; k++) W[i * M + k] = Bm[i * 2 * M + M + k];
-    }
-    __syncthreads();
-    // z0 = (c - A' W A c) / lambda2 with c = A'y - lambda1 1 and A A' = W^-1 - lambda2 I:
-    //    = A' W y - (lambda1 / lambda2) (1 - A' W A 1)
-    for (int e = threadIdx.x; e < N * M; e += blockDim.x) {
-        const int j = e / M, i = e % M;
-        double acc = 0.0;
-        for (int k = 0; k < M; k++) acc += A[k * 16 + j] * W[k * M + i];
-        G[e] = acc;
-    }
-    for (int j = threadIdx.x; j < 16; j += blockDim.x) {
-        double acc = 0.0;
-        if (j < n_atoms) {
-            double awa = 0.0;
-            for (int i = 0; i < M; i++) {
-                double wi = 0.0;
-                for (int k = 0; k < M; k++) { double a1 = 0.0; for (int jj = 0; jj < n_atoms; jj++) a1 += A[k * 16 + jj]; wi += W[i * M + k] * a1; }
-                awa += A[i * 16 + j] * wi;
-            }
-            acc = -(lam1 / lam2) * (1.0 - awa);
-        }
-        g0[j] = acc;
-    }
-}
-constexpr int kSandiTableWords = 15 * kRowsTs + 15 * 6 + 16 + 8 * 16;
-
-constexpr int kRowsOcc = 3;
-
-// SANDI, nS == M (<= 8) values per voxel: row-space solver; the dictionary and its tables come through the scalar cache
-// (wave-uniform addresses), y from the voxel's row.
-template <int M, int N>
-__global__ void __launch_bounds__(256, kRowsOcc) k_sandi_rows(const SandiArgs a)
-{
-    Chunk ck;
-    const bool linear = a.n_lin > 0;           // SANDI has one dictionary: nothing to bucket, the voxels are taken in order
-    if (linear) {
-        ck.start = (int)blockIdx.x * 256; ck.count = a.n_lin - ck.start < 256 ? a.n_lin - ck.start : 256;
-        if (ck.count <= 0) return;
-    } else {
-        const int cid = xcd_chunk((int)blockIdx.x, *a.c.n_chunks);
-        if (cid < 0) return;
-        ck = a.c.chunks[cid];
-    }
-    const int n_atoms = a.c.n_atoms, n_rs = a.n_rs, n_in = a.n_in;
-    // the dictionary and its tables (4.6 KB, the same for every voxel) are read through the SCALAR cache: every address is
-    // wave-uniform, so the loads are s_load_dwordx8/x16 into SGPRs and the fused multiply-adds take them as their scalar
-    // operand -- no LDS instruction in the solver (from LDS the ~210 16-byte broadcast reads per trip cost as much of the
-    // CU's time as the ~650 fp64 instructions they feed).
-    using CD = const __attribute__((address_space(4))) double;
-    constexpr int ldA = 16;
-    CD *T = (CD *)a.tables, *G = T + N * kRowsTs, *g0 = G + N * M, *A = g0 + 16;
-    const bool warm = amx_warm_start(a.c.lam2, a.c.flags);
-    // the atoms' norms and model parameters (Rs | d_in | d_isos by atom class) once per workgroup: read in the maps section below
-    // from their four arrays, every value was a load of its own under a wave-uniform guard, waited for before the next one left --
-    // ~45 memory round trips one after the other per wavefront, as long as the solver itself
-    __shared__ double s_par[2][16];
-    if (threadIdx.x < 16) {
-        const int j = threadIdx.x;
-        s_par[0][j] = j < n_atoms ? a.norms[j] : 0.0;
-        s_par[1][j] = j < n_rs ? a.Rs[j] : (j < n_rs + n_in ? a.d_in[j - n_rs] : (j < n_atoms ? a.d_isos[j - n_rs - n_in] : 0.0));
-    }
-    __syncthreads();
-    for (int v = threadIdx.x; v < ck.count; v += blockDim.x) {
-        const int vox = linear ? ck.start + v : a.c.perm[ck.start + v];
-        const double *yv = a.c.y + (size_t)vox * M;
-        double y[M], x[N], ysq = 0.0;
-        bool ok = true;
-#pragma unroll
-        for (int i = 0; i < M; i++) {
-            y[i] = yv[i];
-            ok = ok && (fabs(y[i]) <= 1.79769313486231570e308);
-            ysq += y[i] * y[i];
-        }
-        double *e = a.est + (size_t)vox * 6;
-        if (!ok) {
-            const double nan = __builtin_nan("");
-            for (int m = 0; m < 6; m++) e[m] = nan;
-            if (a.rmse) a.rmse[vox] = nan;
-            if (a.nrmse) a.nrmse[vox] = nan;
-            continue;
-        }
-        if (lane_nnqp_rows<M, N>(A, ldA, T, G, g0, y, a.c.lam1, a.c.lam2, x, n_atoms, warm) != 0) atomicAdd(&a.c.status[ST_ITCAP], 1);
-        // models.pyx:1570-1612
-        double x_sum = 0.0, xsph = 0.0, xstk = 0.0, xiso = 0.0, Rsoma = 0.0, Din = 0.0, De = 0.0;
-#pragma unroll
-        for (int j = 0; j < N; j++) {
-            const double nj = s_par[0][j < 16 ? j : 0], pj = s_par[1][j < 16 ? j : 0];
-            if (j < n_atoms) {
-                x[j] *= nj;
-                x_sum += x[j];
-                if (j < n_rs) { xsph += x[j]; Rsoma += pj * x[j]; }
-                else if (j < n_rs + n_in) { xstk += x[j]; Din += pj * x[j]; }
-                else { xiso += x[j]; De += pj * x[j]; }
-            }
-        }
-        if (a.c.xdbg) {                                   // the rescaled x (models.pyx:1570-1571)
-#pragma unroll
-            for (int j = 0; j < N; j++) if (j < n_atoms) a.c.xdbg[(size_t)vox * n_atoms + j] = x[j];
-        }
-        x_sum += 1e-16;
-        e[0] = fast_div(xsph, x_sum); e[1] = fast_div(xstk, x_sum); e[2] = fast_div(xiso, x_sum);
-        e[3] = 1e6 * fast_div(Rsoma, xsph + 1e-16);
-        e[4] = 1e3 * fast_div(Din, xstk + 1e-16);
-        e[5] = 1e3 * fast_div(De, xiso + 1e-16);
-        if (a.rmse || a.nrmse) {
-            // quirk kept (models.pyx:1571 then 1615): errors use the RESCALED x with the NORMALISED A
-            double rss = 0.0;
-#pragma unroll
-            for (int i = 0; i < M; i++) {
-                double ei = y[i];
-#pragma unroll
-                for (int j = 0; j < N; j++) ei -= A[i * ldA + j] * x[j];
-                rss += ei * ei;
-            }
-            if (a.rmse) a.rmse[vox] = sqrt(rss / (double)M);
-            if (a.nrmse) a.nrmse[vox] = (ysq > 1e-16) ? sqrt(rss / ysq) : 0.0;
         }
     }
 }
@@ -1609,22 +1046,6 @@ static size_t project_lds_bytes(int nS, int N, int nw)
     return ((size_t)(nS + N) * NP + (size_t)nw * (kTileRows * kTileLd + 32)) * sizeof(double);
 }
 
-template <typename Args, typename K>
-int launch_lane(amx_ctx *ctx, Args &a, const Plan &pl, hipStream_t s, K kern, size_t elem, int N)
-{
-    const size_t lds = (((size_t)a.c.nS * a.c.ldA * elem + 15) & ~(size_t)15) + (size_t)N * N * sizeof(double);
-    if (lds > 160 * 1024) { ctx->err = "dictionary tile does not fit the 160 KB LDS of a CU"; return AMX_E_BADARG; }
-    int rc;
-    if ((rc = set_lds(ctx, kern, lds))) return rc;
-    rec(ctx, 2, s);
-    hipLaunchKernelGGL(kern, dim3(((pl.max_chunks + 7) / 8) * 8), dim3(256), lds, s, a);
-    amx_note(ctx, "lane-per-voxel solver (k_freewater_lane / k_sandi_lane)");
-    AMX_TRACE(ctx, s, "lane-per-voxel solver");
-    rec(ctx, 3, s);
-    HIPCHK(ctx, hipGetLastError());
-    return AMX_OK;
-}
-
 }  // namespace
 
 typedef void (*FwKernel)(const FwArgs);
@@ -1690,9 +1111,8 @@ static int fw_prepare_n(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t
         const int NP = (N + 1) & ~1;
         const size_t lds = ((size_t)lut->nS * NP + N * N) * sizeof(double);
         int rc;
-        if ((rc = set_lds(ctx, k_fw_orient_prep<N>, lds))) return rc;
-        hipLaunchKernelGGL(k_fw_orient_prep<N>, dim3(lut->ndirs), dim3(64), lds, s, reinterpret_cast<const float *>(lut->tiles),
-                           lut->tile_stride, lut->ldA, lut->nS, lut->n_atoms, a.c.lam2, lut->fw_prep);
+        if ((rc = launch_lds(ctx, k_fw_orient_prep<N>, dim3(lut->ndirs), dim3(64), lds, s, reinterpret_cast<const float *>(lut->tiles),
+                             lut->tile_stride, lut->ldA, lut->nS, lut->n_atoms, a.c.lam2, lut->fw_prep))) return rc;
         AMX_TRACE(ctx, s, "FreeWater per-orientation tables");
         HIPCHK(ctx, hipEventRecord(lut->fw_ready, s));
         lut->fw_lam2 = a.c.lam2; lut->fw_N = N;
@@ -1720,48 +1140,6 @@ int amx_launch_fw_small(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s)
     if (n <= 11) return launch_lane(ctx, a, pl, s, k_freewater_lane<11>, sizeof(float), 11);
     if (n == 12) return launch_lane(ctx, a, pl, s, k_freewater_lane<12>, sizeof(float), 12);
     return launch_lane(ctx, a, pl, s, k_freewater_lane<16>, sizeof(float), 16);
-}
-
-// tables of the row-space solver, cached in the dictionary handle for one (lambda1, lambda2)
-int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, SandiArgs &a, hipStream_t s)
-{
-    a.tables = nullptr;
-    if (!(lut->nS == 6 && lut->n_atoms == 15 && amx_warm_start(a.c.lam2, a.c.flags))) return AMX_OK;   // other shapes / cold start: atom-space kernels
-    if (lut->sandi_lam1 != a.c.lam1 || lut->sandi_lam2 != a.c.lam2 || !lut->sandi_prep) {
-        if (lut->sandi_prep) HIPCHK(ctx, hipDeviceSynchronize());                              // (a fit with the old tables may still run)
-        if (!lut->sandi_prep) HIPCHK(ctx, hipMalloc((void **)&lut->sandi_prep, kSandiTableWords * sizeof(double)));
-        if (!lut->sandi_ready) HIPCHK(ctx, hipEventCreateWithFlags(&lut->sandi_ready, hipEventDisableTiming));
-        hipLaunchKernelGGL((k_sandi_tables<6, 15>), dim3(1), dim3(64), 0, s, reinterpret_cast<const double *>(lut->tiles), lut->ldA,
-                           lut->n_atoms, a.c.lam1, a.c.lam2, lut->sandi_prep);
-        AMX_TRACE(ctx, s, "SANDI dictionary tables");
-        HIPCHK(ctx, hipEventRecord(lut->sandi_ready, s));
-        lut->sandi_lam1 = a.c.lam1; lut->sandi_lam2 = a.c.lam2;
-    }
-    HIPCHK(ctx, hipStreamWaitEvent(s, lut->sandi_ready, 0));
-    a.tables = lut->sandi_prep;
-    return AMX_OK;
-}
-
-int amx_launch_sandi_small(amx_ctx *ctx, SandiArgs &a, const Plan &pl, hipStream_t s)
-{
-    const int n = a.c.n_atoms;                // SANDI default: 5 + 5 + 5 = 15 atoms
-    // the default protocol after the directional average (b0 + 5 shells = 6 values, 15 atoms): row-space solver
-    // (a refill variant of this kernel -- lanes drawing the next voxel from a global counter -- was measured SLOWER,
-    //  2.65 vs 2.29 ms per 1 M voxels: SANDI's optimum is dense, 12 of 15 atoms, so the lanes of a wavefront need
-    //  nearly the same number of steps and there is no idle time to win back)
-    if (a.c.nS == 6 && n == 15 && amx_warm_start(a.c.lam2, a.c.flags) && !ctx->opt_sandi_atom_space) {
-        if (!a.tables) { ctx->err = "amx_launch_sandi_small: dictionary tables missing (amx_sandi_prepare)"; return AMX_E_BADARG; }
-        rec(ctx, 2, s);
-        hipLaunchKernelGGL((k_sandi_rows<6, 15>), dim3(a.n_lin > 0 ? (a.n_lin + 255) / 256 : ((pl.max_chunks + 7) / 8) * 8), dim3(256), 0, s, a);
-        amx_note(ctx, "k_sandi_rows<6,15>");
-        AMX_TRACE(ctx, s, "row-space SANDI solver");
-        rec(ctx, 3, s);
-        HIPCHK(ctx, hipGetLastError());
-        return AMX_OK;
-    }
-    if (n <= 12) return launch_lane(ctx, a, pl, s, k_sandi_lane<12>, sizeof(double), 12);
-    if (n <= 15) return launch_lane(ctx, a, pl, s, k_sandi_lane<15>, sizeof(double), 15);
-    return launch_lane(ctx, a, pl, s, k_sandi_lane<16>, sizeof(double), 16);
 }
 
 #ifdef AMX_FW_PHASES

@@ -406,7 +406,7 @@ int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s)
 int amx_launch_batched(amx_ctx *ctx, amx::BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge);
 int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
 int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
-// lane-per-voxel variants for dictionaries of <= 16 atoms (amx_small.hip)
+// lane-per-voxel variants for dictionaries of <= 16 atoms (amx_fw_lane.hip, amx_sandi_lane.hip)
 int amx_launch_fw_small(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);
 int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, amx::FwArgs &a, hipStream_t s);
 int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, amx::SandiArgs &a, hipStream_t s);   // before amx_launch_fw when the refill path runs
@@ -415,7 +415,7 @@ int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipS
 // with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
 // the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.
 __host__ __device__ static inline bool amx_warm_start(double lam2, unsigned flags) { return lam2 >= 1e-5 && !(flags & 0x80000000u); }
-// FreeWater with lanes that never idle (k_freewater_refill, amx_small.hip): maps only (the error maps / AMX_F_CORRECTED
+// FreeWater with lanes that never idle (k_freewater_refill, amx_fw_lane.hip): maps only (the error maps / AMX_F_CORRECTED
 // need the signal again and stay with k_freewater_lane; AMX_F_FW_ISO needs only x and selects nothing), <= 12 atoms; chunks of up to 4096 voxels per workgroup
 // voxels of one orientation per workgroup of the refill kernel: large enough to keep the lanes fed (the buffer needs a
 // pool to draw from), small enough for ~3 rounds of workgroups over the chip (measured on 2 M voxels: 512 -> 1.83 ms,

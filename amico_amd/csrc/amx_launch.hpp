@@ -11,6 +11,16 @@ static int set_lds(amx_ctx *ctx, K kern, size_t bytes)
     return AMX_OK;
 }
 
+// a kernel with dynamic LDS: raise its limit, then launch it
+template <typename K, typename... A>
+static int launch_lds(amx_ctx *ctx, K kern, dim3 grid, dim3 block, size_t lds, hipStream_t s, const A &...args)
+{
+    int rc;
+    if ((rc = set_lds(ctx, kern, lds))) return rc;
+    hipLaunchKernelGGL(kern, grid, block, lds, s, args...);
+    return AMX_OK;
+}
+
 // main pass over the orientation chunks + re-run of the voxels whose passive set overflowed
 constexpr size_t kLdsPerCU = 160 * 1024;
 

@@ -1,4 +1,5 @@
-// amx_sandi.hip -- SANDI solver kernel (models.pyx:1567-1619)
+// amx_sandi.hip -- SANDI (models.pyx:1567-1619): which solver a fit takes.  Here the wavefront-per-voxel kernel (amx_kernels.hpp);
+// the lane-per-voxel kernels of the small dictionaries, the fast path, are in amx_sandi_lane.hip
 #include "amx_launch.hpp"
 using namespace amx;
 

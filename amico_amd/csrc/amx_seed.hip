@@ -86,11 +86,9 @@ int amx_launch_noddi_seed2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
     int rc;
     sa.gcount = pl.feed_set(FEED_SEED2); sa.n_gcount = pl.max_schunks;
     if (pl.seed2_occ2) {
-        if ((rc = set_lds(ctx, k_lasso_seed<true>, lds))) return rc;
-        hipLaunchKernelGGL(k_lasso_seed<true>, dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed2_waves), lds, s, sa);
+        if ((rc = launch_lds(ctx, k_lasso_seed<true>, dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed2_waves), lds, s, sa))) return rc;
     } else {
-        if ((rc = set_lds(ctx, k_lasso_seed<false>, lds))) return rc;
-        hipLaunchKernelGGL(k_lasso_seed<false>, dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed2_waves), lds, s, sa);
+        if ((rc = launch_lds(ctx, k_lasso_seed<false>, dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed2_waves), lds, s, sa))) return rc;
     }
     amx_note(ctx, pl.seed2_occ2 ? "k_lasso_seed<occ2>" : "k_lasso_seed");
     AMX_TRACE(ctx, s, "LASSO seed solver");
@@ -155,10 +153,7 @@ int amx_launch_noddi_gemm(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a, 
     int rc;
     const dim3 grid(((pl.max_schunks + 7) / 8) * 8);
 #define AMX_GEMM_GO(L, K, ...)                                                                     \
-    do {                                                                                           \
-        if ((rc = set_lds(ctx, (k_noddi_gemm<L, K, ##__VA_ARGS__>), lds))) return rc;              \
-        hipLaunchKernelGGL((k_noddi_gemm<L, K, ##__VA_ARGS__>), grid, dim3(512), lds, s, ga);      \
-    } while (0)
+    do { if ((rc = launch_lds(ctx, (k_noddi_gemm<L, K, ##__VA_ARGS__>), grid, dim3(512), lds, s, ga))) return rc; } while (0)
     const int mtf = (lasso ? lut->n_wm : lut->n_atoms) / 16;
     const int n_pass = gemm_passes(lut->nS), win = gemm_window(lut->nS);
     for (int p = 0; p < n_pass; p++) {
@@ -250,8 +245,7 @@ int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a
 #endif
     const size_t lds = ((size_t)lut->n_wm * kSeedLd + 2 + 2 * ((lut->n_wm + 1) & ~1) + (size_t)9 * (kSeedKD / 4) * 64 + (size_t)4 * 64 * 16) * sizeof(double);
     int rc;
-    if ((rc = set_lds(ctx, (k_lasso_gcert<kGcert2Max, false>), lds))) return rc;
-    hipLaunchKernelGGL((k_lasso_gcert<kGcert2Max, false>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g);
+    if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Max, false>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g))) return rc;
     amx_note(ctx, "k_lasso_gcert<11>");
     AMX_TRACE(ctx, s, "Gram-space certificates of the LASSO seeds");
     HIPCHK(ctx, hipGetLastError());
@@ -263,8 +257,7 @@ int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a
 #ifdef AMX_STATS
         g.stats = a.c.status + ST_SEED + 48;
 #endif
-        if ((rc = set_lds(ctx, (k_lasso_gcert<kGcert2Wide, true>), lds))) return rc;
-        hipLaunchKernelGGL((k_lasso_gcert<kGcert2Wide, true>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g);
+        if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide, true>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g))) return rc;
         amx_note(ctx, "k_lasso_gcert<18,wide>");
         AMX_TRACE(ctx, s, "Gram-space certificates of the LASSO seeds, supports of 12 .. 18 atoms");
         HIPCHK(ctx, hipGetLastError());
@@ -277,8 +270,7 @@ int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a
 #ifdef AMX_STATS
             g.stats = nullptr;
 #endif
-            if ((rc = set_lds(ctx, (k_lasso_gcert<kGcert2Wide3, true, kGcert2Wide>), lds))) return rc;
-            hipLaunchKernelGGL((k_lasso_gcert<kGcert2Wide3, true, kGcert2Wide>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g);
+            if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide3, true, kGcert2Wide>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g))) return rc;
             amx_note(ctx, "k_lasso_gcert<24,wide,18>");
             AMX_TRACE(ctx, s, "Gram-space certificates of the LASSO seeds, supports beyond the second pass");
             HIPCHK(ctx, hipGetLastError());
@@ -320,17 +312,13 @@ int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
     // wrong more often -- the shapes whose tile is read from L2 (AMX_GCERT_REPAIR=0 / 1 forces)
     const bool repair = ctx->opt_gcert_repair >= 0 ? ctx->opt_gcert_repair != 0 : amx_noddi_tile_global(lut->nS, lut->ldA, lut->n_atoms);
     if (stage == 1 && repair) {
-        if ((rc = set_lds(ctx, (k_nnls_gcert<1, false, true>), lds))) return rc;
-        hipLaunchKernelGGL((k_nnls_gcert<1, false, true>), grid, dim3(64 * pl.seed_waves), lds, s, g);
+        if ((rc = launch_lds(ctx, (k_nnls_gcert<1, false, true>), grid, dim3(64 * pl.seed_waves), lds, s, g))) return rc;
     } else if (stage == 1) {
-        if ((rc = set_lds(ctx, k_nnls_gcert<1>, lds))) return rc;
-        hipLaunchKernelGGL(k_nnls_gcert<1>, grid, dim3(64 * pl.seed_waves), lds, s, g);
+        if ((rc = launch_lds(ctx, k_nnls_gcert<1>, grid, dim3(64 * pl.seed_waves), lds, s, g))) return rc;
     } else if (repair) {
-        if ((rc = set_lds(ctx, (k_nnls_gcert<3, false, true>), lds))) return rc;
-        hipLaunchKernelGGL((k_nnls_gcert<3, false, true>), grid, dim3(64 * pl.seed_waves), lds, s, g);
+        if ((rc = launch_lds(ctx, (k_nnls_gcert<3, false, true>), grid, dim3(64 * pl.seed_waves), lds, s, g))) return rc;
     } else {
-        if ((rc = set_lds(ctx, k_nnls_gcert<3>, lds))) return rc;
-        hipLaunchKernelGGL(k_nnls_gcert<3>, grid, dim3(64 * pl.seed_waves), lds, s, g);
+        if ((rc = launch_lds(ctx, k_nnls_gcert<3>, grid, dim3(64 * pl.seed_waves), lds, s, g))) return rc;
     }
     amx_note(ctx, stage == 1 ? (repair ? "k_nnls_gcert<1,repair>" : "k_nnls_gcert<1>") : (repair ? "k_nnls_gcert<3,repair>" : "k_nnls_gcert<3>"));
     AMX_TRACE(ctx, s, "Gram-space certificates");
@@ -360,11 +348,9 @@ int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a,
         g.tile_in_lds = lds + tile <= kLdsPerCU ? 1 : 0;
         const size_t lds2 = lds + (g.tile_in_lds ? tile : 0);
         if (stage == 1) {
-            if ((rc = set_lds(ctx, (k_nnls_gcert<1, true>), lds2))) return rc;
-            hipLaunchKernelGGL((k_nnls_gcert<1, true>), grid, dim3(64 * pl.seed_waves), lds2, s, g);
+            if ((rc = launch_lds(ctx, (k_nnls_gcert<1, true>), grid, dim3(64 * pl.seed_waves), lds2, s, g))) return rc;
         } else {
-            if ((rc = set_lds(ctx, (k_nnls_gcert<3, true>), lds2))) return rc;
-            hipLaunchKernelGGL((k_nnls_gcert<3, true>), grid, dim3(64 * pl.seed_waves), lds2, s, g);
+            if ((rc = launch_lds(ctx, (k_nnls_gcert<3, true>), grid, dim3(64 * pl.seed_waves), lds2, s, g))) return rc;
         }
         amx_note(ctx, stage == 1 ? "k_nnls_gcert<1,rescue>" : "k_nnls_gcert<3,rescue>");
         AMX_TRACE(ctx, s, "Gram-space certificates, rescue pass");
@@ -400,14 +386,11 @@ int amx_launch_noddi_seed(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a, 
     int rc;
     sa.gcount = pl.feed_set(stage == 1 ? FEED_SEED1 : FEED_SEED3); sa.n_gcount = pl.max_schunks;
     if (stage == 1 && pl.seed_occ2) {
-        if ((rc = set_lds(ctx, (k_nnls_seed<1, 8, true>), lds))) return rc;
-        hipLaunchKernelGGL((k_nnls_seed<1, 8, true>), grid, dim3(64 * pl.seed1_waves), lds, s, sa);
+        if ((rc = launch_lds(ctx, (k_nnls_seed<1, 8, true>), grid, dim3(64 * pl.seed1_waves), lds, s, sa))) return rc;
     } else if (stage == 1) {
-        if ((rc = set_lds(ctx, (k_nnls_seed<1, 8>), lds))) return rc;
-        hipLaunchKernelGGL((k_nnls_seed<1, 8>), grid, dim3(64 * pl.seed1_waves), lds, s, sa);
+        if ((rc = launch_lds(ctx, (k_nnls_seed<1, 8>), grid, dim3(64 * pl.seed1_waves), lds, s, sa))) return rc;
     } else {
-        if ((rc = set_lds(ctx, (k_nnls_seed<3, 6>), lds))) return rc;
-        hipLaunchKernelGGL((k_nnls_seed<3, 6>), grid, dim3(64 * pl.seed_waves), lds, s, sa);
+        if ((rc = launch_lds(ctx, (k_nnls_seed<3, 6>), grid, dim3(64 * pl.seed_waves), lds, s, sa))) return rc;
     }
     amx_note(ctx, stage == 1 ? (pl.seed_occ2 ? "k_nnls_seed<1,8,occ2>" : "k_nnls_seed<1,8>") : "k_nnls_seed<3,6>");
     AMX_TRACE(ctx, s, "seed solver");

@@ -210,6 +210,15 @@ def test_build_id_matches_the_sources():
     assert _capi.build_is_current(), 'libamico_amd.so is older than its sources: run make -C amico_amd/csrc'
 
 
+def test_every_hashed_unit_is_compiled():
+    """the .hip files under csrc are exactly the Makefile's UNITS plus amx_buildid: a source that is hashed into the build id
+    but not compiled (or a unit listed without its source) cannot go unnoticed"""
+    csrc = os.path.join(ROOT, 'amico_amd', 'csrc')
+    units = re.search(r'^UNITS\s*=\s*(.*)$', open(os.path.join(csrc, 'Makefile')).read(), re.M).group(1).split()
+    assert len(units) == len(set(units))
+    assert sorted(units + ['amx_buildid']) == sorted(f[:-4] for f in os.listdir(csrc) if f.endswith('.hip'))
+
+
 def test_dictionary_cache_is_checked_behind_the_fit(monkeypatch):
     """BaseModel._lut / _verified_fit: the digest of KERNELS runs beside the fit; a fit that ran on a stale upload (KERNELS edited in
     place since) is discarded and run again on the rebuilt dictionary -- the reference re-reads KERNELS on every fit (models.pyx:840-847)"""
