@@ -286,12 +286,13 @@ template <int N> __device__ __forceinline__ constexpr int stri(int i, int j) { r
 // W [atoms x voxels] = S' [atoms x KD] * R [KD x voxels], v_mfma_f64_16x16x4_f64 (exact fp64 products and sums).
 //   * A operand (S'): prepared once per chunk in LDS in operand order, Aop[(mt * KS + ks) * 64 + lane] = S[atom 16 mt +
 //     (lane & 15)][4 ks + (lane >> 4)] (zero beyond n_atoms);
-//   * B operand (R): every lane publishes the residual of ITS voxel in the wavefront's LDS block Rb [64][4 KS + 1] and
-//     reads back the element the operand layout asks of it -- r[4 ks + (lane >> 4)] of voxel 16 nt + (lane & 15);
+//   * B operand (R): every lane that needs a scan publishes the residual of ITS voxel in the wavefront's LDS block Rb [64][4 KS + 1],
+//     in the row of its slot (ScanSlots below: "voxel" v in what follows is the voxel of slot v), and every lane reads back the
+//     element the operand layout asks of it -- r[4 ks + (lane >> 4)] of voxel 16 nt + (lane & 15);
 //   * D: register r of lane l holds the dual value of atom 16 mt + 4 r + (l >> 4) for voxel 16 nt + (l & 15).  The arg-max
 //     rides in the value itself: the low 8 mantissa bits are replaced by the candidate's code (mt * 4 + r, later the row
 //     l >> 4), so one v_max_f64 per value keeps both; the four rows that share a voxel are combined by the two row
-//     swaps, and the lane that owns voxel v finds its result in row v >> 4.  (2^-44 relative: far below what the choice
+//     swaps, and lane v finds the result of voxel v in row v >> 4.  (2^-44 relative: far below what the choice
 //     of the entering atom, or the 1e-10 stopping test, can see.)
 __device__ __forceinline__ double seed_max(double a, double b)     // plain v_max_f64 (no canonicalisation of the operands)
 {
@@ -308,44 +309,68 @@ __device__ __forceinline__ double seed_min(double a, double b)
 }
 
 typedef double seed_v4d __attribute__((ext_vector_type(4)));
-template <int KS, int MT, bool PIPE = true>
-__device__ __forceinline__ void seed_scan_mfma(const double *Aop, double *Rb, const double (&r)[4 * KS], int lane, double &best, int &bj)
+
+// Only the lanes that NEED a scan this trip publish a column: lane l takes slot rank(l) -- the number of needing lanes below it --
+// so the cnt columns in use fill the voxel groups 0 .. G - 1, G = ceil(cnt / 16), and the products and the tag / max work of the
+// other groups are not issued at all (the tail of a chunk, when the feed has run dry: a handful of lanes at work, one group instead
+// of four).  Column v of W depends on column v of R alone, so a voxel's dual values are the same bits whichever column carries it;
+// the columns from cnt on hold whatever the block held before, and nobody reads their results.
+struct ScanSlots {
+    int cnt, groups, slot;
+    __device__ __forceinline__ ScanSlots(bool need)
+    {
+        const unsigned long long m = __ballot(need);
+        cnt = __builtin_popcountll(m);
+        groups = (cnt + 15) >> 4;                                   // wave-uniform
+        slot = (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
+    }
+    // after the scan lane s holds the result of slot s: the owner of the slot fetches it (two ds_bpermute_b32, no LDS traffic)
+    __device__ __forceinline__ double fetch(double v) const
+    {
+        const int lo = __builtin_amdgcn_ds_bpermute(slot << 2, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(slot << 2, __double2hiint(v));
+        return __hiloint2double(hi, lo);
+    }
+};
+
+// the scan over the first GN voxel groups; returns to lane l the tagged maximum of column l (lanes of the groups >= GN: -inf)
+template <int KS, int MT, bool PIPE, int GN>
+__device__ __forceinline__ double seed_scan_groups(const double *Aop, const double *Rb, int lane)
 {
     constexpr int KDP = 4 * KS + 1;
     const int q = lane >> 4, c16 = lane & 15;
+    double b[GN][KS];
 #pragma unroll
-    for (int d = 0; d < 4 * KS; d++) Rb[lane * KDP + d] = r[d];
-    double b[4][KS];
-#pragma unroll
-    for (int nt = 0; nt < 4; nt++) {
+    for (int nt = 0; nt < GN; nt++) {
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) b[nt][ks] = Rb[(16 * nt + c16) * KDP + 4 * ks + q];
     }
     const double ninf = -__builtin_huge_val();
-    double bv[4] = {ninf, ninf, ninf, ninf};
-    // software pipeline: the 12 products of tile mt + 1 are issued BEFORE the tag / max work on tile mt's results, so the matrix
+    double bv[GN];
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) bv[nt] = ninf;
+    // software pipeline: the products of tile mt + 1 are issued BEFORE the tag / max work on tile mt's results, so the matrix
     // pipe runs while the vector pipe reduces (one wavefront per SIMD: nothing else would overlap the two)
-    auto products = [&](int mt, seed_v4d (&acc)[4]) {
+    auto products = [&](int mt, seed_v4d (&acc)[GN]) {
         double av[KS];
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) av[ks] = Aop[(mt * KS + ks) * 64 + lane];
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) acc[nt] = (seed_v4d){0.0, 0.0, 0.0, 0.0};
+        for (int nt = 0; nt < GN; nt++) acc[nt] = (seed_v4d){0.0, 0.0, 0.0, 0.0};
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) {
 #pragma unroll
-            for (int nt = 0; nt < 4; nt++) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], b[nt][ks], acc[nt], 0, 0, 0);
+            for (int nt = 0; nt < GN; nt++) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], b[nt][ks], acc[nt], 0, 0, 0);
         }
     };
-    seed_v4d cur[4], nxt[PIPE ? 4 : 1];
+    seed_v4d cur[GN], nxt[PIPE ? GN : 1];
     if (PIPE) products(0, cur);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-        if (PIPE) { if (mt + 1 < MT) products(mt + 1, reinterpret_cast<seed_v4d (&)[4]>(nxt)); }
+        if (PIPE) { if (mt + 1 < MT) products(mt + 1, reinterpret_cast<seed_v4d (&)[GN]>(nxt)); }
         else products(mt, cur);                       // (two wavefronts per SIMD: the other wavefront fills the matrix pipe's shadow)
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-        for (int nt = 0; nt < 4; nt++) {
+        for (int nt = 0; nt < GN; nt++) {
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
                 const double v = cur[nt][rr];
@@ -356,16 +381,37 @@ __device__ __forceinline__ void seed_scan_mfma(const double *Aop, double *Rb, co
         __builtin_amdgcn_sched_barrier(0);
         if (PIPE) {
 #pragma unroll
-            for (int nt = 0; nt < 4; nt++) cur[nt] = nxt[PIPE ? nt : 0];
+            for (int nt = 0; nt < GN; nt++) cur[nt] = nxt[PIPE ? nt : 0];
         }
     }
     double mine = ninf;
 #pragma unroll
-    for (int nt = 0; nt < 4; nt++) {
+    for (int nt = 0; nt < GN; nt++) {
         const double t = __hiloint2double(__double2hiint(bv[nt]), (int)((unsigned)__double2loint(bv[nt]) | (unsigned)(q << 6)));
         const double m = rows_allmax(t);
         mine = (q == nt) ? m : mine;
     }
+    return mine;
+}
+
+// need: this lane's voxel wants a scan this trip (the caller has made sure that some lane does); best / bj of the other lanes are not results
+template <int KS, int MT, bool PIPE = true>
+__device__ __forceinline__ void seed_scan_mfma(const double *Aop, double *Rb, const double (&r)[4 * KS], int lane, bool need, double &best, int &bj)
+{
+    constexpr int KDP = 4 * KS + 1;
+    const ScanSlots sl(need);
+    if (need) {
+#pragma unroll
+        for (int d = 0; d < 4 * KS; d++) Rb[sl.slot * KDP + d] = r[d];
+    }
+    double mine;
+    switch (sl.groups) {
+    case 1: mine = seed_scan_groups<KS, MT, PIPE, 1>(Aop, Rb, lane); break;
+    case 2: mine = seed_scan_groups<KS, MT, PIPE, 2>(Aop, Rb, lane); break;
+    case 3: mine = seed_scan_groups<KS, MT, PIPE, 3>(Aop, Rb, lane); break;
+    default: mine = seed_scan_groups<KS, MT, PIPE, 4>(Aop, Rb, lane); break;
+    }
+    mine = sl.fetch(mine);
     const unsigned code = (unsigned)__double2loint(mine) & 0xffu;
     best = mine;
     bj = 16 * (int)((code >> 2) & 15u) + 4 * (int)(code & 3u) + (int)(code >> 6);
@@ -877,7 +923,7 @@ __global__ void __launch_bounds__(256, (MS > 6 ? (OCC2 ? 2 : kSeed1Occ) : kSeed3
             int bj = -1;
             if (STAGE == 1) {
                 if (n_atoms <= 16 * MT) {
-                    seed_scan_mfma<KS, MT, (!OCC2 && kSeed1Occ == 1)>(Aop, Rb, r, lane, best, bj);
+                    seed_scan_mfma<KS, MT, (!OCC2 && kSeed1Occ == 1)>(Aop, Rb, r, lane, scan, best, bj);
                 } else {
                     for (int j = 0; j < n_atoms; j++) {
                         const double *sp = Sg + (size_t)j * KD;              // wave-uniform address: scalar loads
@@ -2426,6 +2472,101 @@ __global__ void __launch_bounds__(1024) k_noddi_project2(const Seed2Args a)
     }
 }
 
+// The LASSO seed solver's scan over the first GN voxel groups (operands as in seed_scan_groups; Pb: the passive-set words of the
+// columns).  To lane l, for column l: the tagged maximum over the atoms outside the passive set, its runner-up, and the tagged
+// maximum of the NEGATED values of the passive atoms (lanes of the groups >= GN: -inf).
+template <int KS, int MT, bool PIPE, int GN>
+__device__ __forceinline__ void lasso_scan_groups(const double *Aop, const double *Rb, const unsigned long long *Pb, int lane, double &mine, double &second, double &mine2)
+{
+    constexpr int KDP = 4 * KS + 1;
+    const int q = lane >> 4, c16 = lane & 15;
+    double b[GN][KS];
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) {
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) b[nt][ks] = Rb[(16 * nt + c16) * KDP + 4 * ks + q];
+    }
+    const double ninf = -__builtin_huge_val();
+    // the SAME product holds t_j + lambda1 of the passive atoms: their minimum (kept as the maximum of the negated values, same
+    // tag trick) names the atom that leaves -- no second pass over the passive set with per-lane gathers
+    double bv[GN], wv[GN], b2[GN];                         // b2: runner-up of bv (two atoms may enter in one trip)
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) { bv[nt] = ninf; wv[nt] = ninf; b2[nt] = ninf; }
+    // (one wavefront per SIMD: unrolled and software-pipelined like seed_scan_groups -- the products of tile mt + 1 are issued
+    //  before the mask / tag / max work on tile mt)
+    auto products = [&](int mt, seed_v4d (&acc)[GN]) {
+        double av[KS];
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) av[ks] = Aop[(mt * KS + ks) * 64 + lane];
+#pragma unroll
+        for (int nt = 0; nt < GN; nt++) acc[nt] = (seed_v4d){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+#pragma unroll
+            for (int nt = 0; nt < GN; nt++) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], b[nt][ks], acc[nt], 0, 0, 0);
+        }
+    };
+    seed_v4d cur[GN], nxt[PIPE ? GN : 1];
+    if (PIPE) products(0, cur);
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++) {
+        if (PIPE) { if (mt + 1 < MT) products(mt + 1, reinterpret_cast<seed_v4d (&)[GN]>(nxt)); }
+        else products(mt, cur);
+        // passive bits of the voxels 16 nt + c16 for this tile's atoms (row-shifted), read back per tile instead of
+        // living in 24 registers for the whole scan
+        unsigned long long pw[GN];
+#pragma unroll
+        for (int nt = 0; nt < GN; nt++) pw[nt] = Pb[(16 * nt + c16) * 3 + ((16 * mt) >> 6)] >> q;
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int nt = 0; nt < GN; nt++) {
+#pragma unroll
+            for (int rr = 0; rr < 4; rr++) {
+                const int bit = 16 * mt + 4 * rr;        // position of this atom in the row-shifted mask
+                const bool pas = (pw[nt] >> (bit & 63)) & 1ull;
+                const double v = cur[nt][rr];
+                const unsigned lo = ((unsigned)__double2loint(v) & 0xffffff00u) | (unsigned)(mt * 4 + rr);
+                const int hi = pas ? (int)0xffe00000 : __double2hiint(v);     // passive: -9e307 (finite whatever the low word is; 0xfff... would be a NaN)
+                const double val = __hiloint2double(hi, (int)lo);
+                b2[nt] = seed_max(b2[nt], seed_min(bv[nt], val));
+                bv[nt] = seed_max(bv[nt], val);
+                const int hn = pas ? (__double2hiint(v) ^ (int)0x80000000) : (int)0xffe00000;
+                wv[nt] = seed_max(wv[nt], __hiloint2double(hn, (int)lo));
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (PIPE) {
+#pragma unroll
+            for (int nt = 0; nt < GN; nt++) cur[nt] = nxt[PIPE ? nt : 0];
+        }
+    }
+    mine = ninf;
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) {
+        const double t = __hiloint2double(__double2hiint(bv[nt]), (int)((unsigned)__double2loint(bv[nt]) | (unsigned)(q << 6)));
+        const double m = rows_allmax(t);
+        mine = (q == nt) ? m : mine;
+    }
+    // runner-up of the voxel: the row that holds the winner contributes its own runner-up, the other rows their best
+    // (the tags make all values distinct, so equality identifies the winner's row)
+    second = ninf;
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) {
+        const double t1 = __hiloint2double(__double2hiint(bv[nt]), (int)((unsigned)__double2loint(bv[nt]) | (unsigned)(q << 6)));
+        const double t2 = __hiloint2double(__double2hiint(b2[nt]), (int)((unsigned)__double2loint(b2[nt]) | (unsigned)(q << 6)));
+        const double mall = rows_allmax(t1);
+        const double m = rows_allmax((t1 == mall) ? t2 : t1);
+        second = (q == nt) ? m : second;
+    }
+    mine2 = ninf;
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) {
+        const double t = __hiloint2double(__double2hiint(wv[nt]), (int)((unsigned)__double2loint(wv[nt]) | (unsigned)(q << 6)));
+        const double m = rows_allmax(t);
+        mine2 = (q == nt) ? m : mine2;
+    }
+}
+
 constexpr int kSeed2Occ = 1;
 template <bool OCC2 = false>
 __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const Seed2Args a)
@@ -2569,101 +2710,28 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
         double best = -inf, best2 = -inf;
         int bj = -1, bj2 = -1;
         {
+            // (only the active lanes publish a column, and only the voxel groups that hold one are scanned: see ScanSlots)
+            const ScanSlots sl(active);
+            if (active) {
 #pragma unroll
-            for (int d = 0; d < KD; d++) Rb[lane * KDP + d] = r[d];
+                for (int d = 0; d < KD; d++) Rb[sl.slot * KDP + d] = r[d];
 #pragma unroll
-            for (int w3 = 0; w3 < 3; w3++) Pb[lane * 3 + w3] = active ? P[w3] : ~0ull;
-            double b[4][KS];
-#pragma unroll
-            for (int nt = 0; nt < 4; nt++) {
-#pragma unroll
-                for (int ks = 0; ks < KS; ks++) b[nt][ks] = Rb[(16 * nt + c16) * KDP + 4 * ks + q];
+                for (int w3 = 0; w3 < 3; w3++) Pb[sl.slot * 3 + w3] = P[w3];
             }
-            const double ninf = -inf;
-            double bv[4] = {ninf, ninf, ninf, ninf};
-            // the SAME product holds t_j + lambda1 of the passive atoms: their minimum (kept as the maximum of the negated values, same
-            // tag trick) names the atom that leaves -- no second pass over the passive set with per-lane gathers
-            double wv[4] = {ninf, ninf, ninf, ninf};
-            double b2[4] = {ninf, ninf, ninf, ninf};           // runner-up of bv (two atoms may enter in one trip)
-            // (one wavefront per SIMD: unrolled and software-pipelined like seed_scan_mfma -- the products of tile mt + 1 are issued
-            //  before the mask / tag / max work on tile mt)
-            auto products = [&](int mt, seed_v4d (&acc)[4]) {
-                double av[KS];
-#pragma unroll
-                for (int ks = 0; ks < KS; ks++) av[ks] = Aop[(mt * KS + ks) * 64 + lane];
-#pragma unroll
-                for (int nt = 0; nt < 4; nt++) acc[nt] = (seed_v4d){0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int ks = 0; ks < KS; ks++) {
-#pragma unroll
-                    for (int nt = 0; nt < 4; nt++) acc[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[ks], b[nt][ks], acc[nt], 0, 0, 0);
-                }
-            };
-            seed_v4d cur[4], nxt[PREF2 ? 4 : 1];
-            if (PREF2) products(0, cur);
-#pragma unroll
-            for (int mt = 0; mt < MT; mt++) {
-                if (PREF2) { if (mt + 1 < MT) products(mt + 1, reinterpret_cast<seed_v4d (&)[4]>(nxt)); }
-                else products(mt, cur);
-                // passive bits of the voxels 16 nt + c16 for this tile's atoms (row-shifted), read back per tile instead of
-                // living in 24 registers for the whole scan
-                unsigned long long pw[4];
-#pragma unroll
-                for (int nt = 0; nt < 4; nt++) pw[nt] = Pb[(16 * nt + c16) * 3 + ((16 * mt) >> 6)] >> q;
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int nt = 0; nt < 4; nt++) {
-#pragma unroll
-                    for (int rr = 0; rr < 4; rr++) {
-                        const int bit = 16 * mt + 4 * rr;        // position of this atom in the row-shifted mask
-                        const bool pas = (pw[nt] >> (bit & 63)) & 1ull;
-                        const double v = cur[nt][rr];
-                        const unsigned lo = ((unsigned)__double2loint(v) & 0xffffff00u) | (unsigned)(mt * 4 + rr);
-                        const int hi = pas ? (int)0xffe00000 : __double2hiint(v);     // passive: -9e307 (finite whatever the low word is; 0xfff... would be a NaN)
-                        const double val = __hiloint2double(hi, (int)lo);
-                        b2[nt] = seed_max(b2[nt], seed_min(bv[nt], val));
-                        bv[nt] = seed_max(bv[nt], val);
-                        const int hn = pas ? (__double2hiint(v) ^ (int)0x80000000) : (int)0xffe00000;
-                        wv[nt] = seed_max(wv[nt], __hiloint2double(hn, (int)lo));
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                if (PREF2) {
-#pragma unroll
-                    for (int nt = 0; nt < 4; nt++) cur[nt] = nxt[PREF2 ? nt : 0];
-                }
+            double mine, second, mine2;
+            switch (sl.groups) {
+            case 1: lasso_scan_groups<KS, MT, PREF2, 1>(Aop, Rb, Pb, lane, mine, second, mine2); break;
+            case 2: lasso_scan_groups<KS, MT, PREF2, 2>(Aop, Rb, Pb, lane, mine, second, mine2); break;
+            case 3: lasso_scan_groups<KS, MT, PREF2, 3>(Aop, Rb, Pb, lane, mine, second, mine2); break;
+            default: lasso_scan_groups<KS, MT, PREF2, 4>(Aop, Rb, Pb, lane, mine, second, mine2); break;
             }
-            double mine = ninf;
-#pragma unroll
-            for (int nt = 0; nt < 4; nt++) {
-                const double t = __hiloint2double(__double2hiint(bv[nt]), (int)((unsigned)__double2loint(bv[nt]) | (unsigned)(q << 6)));
-                const double m = rows_allmax(t);
-                mine = (q == nt) ? m : mine;
-            }
+            mine = sl.fetch(mine); second = sl.fetch(second); mine2 = sl.fetch(mine2);
             const unsigned code = (unsigned)__double2loint(mine) & 0xffu;
             best = mine - lam1;
             bj = 16 * (int)((code >> 2) & 15u) + 4 * (int)(code & 3u) + (int)(code >> 6);
-            // runner-up of the voxel: the row that holds the winner contributes its own runner-up, the other rows their best
-            // (the tags make all values distinct, so equality identifies the winner's row)
-            double second = ninf;
-#pragma unroll
-            for (int nt = 0; nt < 4; nt++) {
-                const double t1 = __hiloint2double(__double2hiint(bv[nt]), (int)((unsigned)__double2loint(bv[nt]) | (unsigned)(q << 6)));
-                const double t2 = __hiloint2double(__double2hiint(b2[nt]), (int)((unsigned)__double2loint(b2[nt]) | (unsigned)(q << 6)));
-                const double mall = rows_allmax(t1);
-                const double m = rows_allmax((t1 == mall) ? t2 : t1);
-                second = (q == nt) ? m : second;
-            }
             const unsigned codes = (unsigned)__double2loint(second) & 0xffu;
             best2 = second - lam1;
             bj2 = 16 * (int)((codes >> 2) & 15u) + 4 * (int)(codes & 3u) + (int)(codes >> 6);
-            double mine2 = ninf;
-#pragma unroll
-            for (int nt = 0; nt < 4; nt++) {
-                const double t = __hiloint2double(__double2hiint(wv[nt]), (int)((unsigned)__double2loint(wv[nt]) | (unsigned)(q << 6)));
-                const double m = rows_allmax(t);
-                mine2 = (q == nt) ? m : mine2;
-            }
             const unsigned code2 = (unsigned)__double2loint(mine2) & 0xffu;
             // mine2 = -(smallest passive s_j'r): t_j = -mine2 - lambda1 <= 0 ?  (no passive atom: mine2 = -9e307)
             if (active && mine2 > -1e300 && -mine2 - lam1 <= 0.0)
