@@ -285,6 +285,13 @@ int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;      // (one dictionary: no bucketing)
     a.norms = lut->norms; a.Rs = lut->Rs; a.d_in = lut->d_in; a.d_isos = lut->d_isos;
     a.n_rs = lut->n_rs; a.n_in = lut->n_in; a.n_iso = lut->n_isos;
+    if (lut->nS > kSandiShortNS) {
+        // protocols without the directional average: c = A'y on the matrix cores, then the Gram-space solvers (amx_sandi_long.hip).  They need the
+        // ridge: an isotropic dictionary has rank <= shells + 1 < n_atoms, so without it the optimum is not unique and A'A alone is singular
+        if (c.lam2 < 1e-9) return fit_bad(ctx, m, ": protocols of more than 128 volumes need lambda2 >= 1e-9 (Gram-space solver)");
+        if ((rc = amx_sandi_long_prepare(ctx, lut, c.lam2, s))) return rc;
+        return fit_close(ctx, c, amx_launch_sandi_long(ctx, lut, a, c.n, s), false);      // (the voxels in order, no per-call counters)
+    }
     if ((rc = amx_sandi_prepare(ctx, lut, a, s))) return rc;
     // the row-space kernel (default protocol) takes the voxels in order and counts straight into the status words: one launch
     // per fit; the other SANDI kernels walk the (trivial) plan and use the per-call counters
@@ -313,13 +320,13 @@ int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
 }  // namespace
 
 // float32 signals in HBM (the image's dtype, core.py:136; lossless) are read in place by the NODDI kernels, by every wavefront-per-voxel
-// kernel and by FreeWater's matrix-core projection; the other lane kernels get a float64 copy made on the device first.
+// kernel, by FreeWater's matrix-core projection and by SANDI's (k_sandi_project); the other lane kernels get a float64 copy made on the device first.
 int amx_fit_dev(amx_ctx *ctx, const FitSpec &m, FitCall c)
 {
     int rc;
     const bool f32 = ctx && c.lut && c.lut->model == m.model && c.y32 && c.n > 0;      // (else: fit_check says what is wrong)
     if (f32 && ((m.model == 2 && !amx_fw_native_f32(ctx, c.lut->n_atoms, c.lut->nS, c.flags, c.lam2)) ||
-                (m.model == 3 && amx_use_lane_solver(ctx, c.lut->n_atoms, c.lam2)))) {
+                (m.model == 3 && c.lut->nS <= kSandiShortNS && amx_use_lane_solver(ctx, c.lut->n_atoms, c.lam2)))) {      // (longer protocols: k_sandi_project reads either)
         const size_t nel = (size_t)c.n * c.lut->nS;
         HIPCHK(ctx, hipSetDevice(ctx->device));
         if ((rc = amx_ensure(ctx, ctx->wy, nel * sizeof(double)))) return rc;

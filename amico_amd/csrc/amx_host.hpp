@@ -253,6 +253,10 @@ struct amx_lut {
     mutable double *sandi_prep = nullptr;
     mutable double sandi_lam1 = -1.0, sandi_lam2 = -1.0;
     mutable hipEvent_t sandi_ready = nullptr;
+    // SANDI on protocols of more than 128 volumes (amx_sandi_long.hip), for one lambda2: G = A'A, H = G + lambda2 I, A' in MFMA operand order
+    mutable double *sandi_long_prep = nullptr;
+    mutable double sandi_long_lam2 = -1.0;
+    mutable hipEvent_t sandi_long_ready = nullptr;
 };
 
 // dictionaries of the batched solver entry points (amx_nnls_batched / amx_lasso_batched)
@@ -411,6 +415,10 @@ int amx_launch_fw_small(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_
 int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, amx::FwArgs &a, hipStream_t s);
 int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, amx::SandiArgs &a, hipStream_t s);   // before amx_launch_fw when the refill path runs
 int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
+// SANDI, protocols of more than kSandiShortNS volumes (amx_sandi_long.hip): projection on the matrix cores, then a Gram-space solver
+constexpr int kSandiShortNS = 128;     // up to here a wavefront's lanes hold the signal rows (k_sandi<2>) / a lane walks its own row (k_sandi_lane)
+int amx_sandi_long_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
+int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s);
 // Lane-per-voxel solvers: start the active set from ALL atoms and drop the non-positive ones in blocks (unique optimum
 // with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
 // the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.

@@ -41,10 +41,11 @@ void amx_lut_destroy(amx_lut *lut)
     if (!lut) return;
     if (lut->ctx) hipSetDevice(lut->ctx->device);
     void *ps[] = {lut->u2iso, lut->screen2_kappa0, lut->screen_kappa0, lut->screen2_S, lut->screen2_kappa, lut->screen_S, lut->screen_kappa, lut->basis_U, lut->basis_S, lut->basis2_U, lut->basis2_S, lut->gram, lut->gram_dwi, lut->tiles, lut->htable, lut->rowdwi, lut->colscale, lut->icvf, lut->kappa,
-                  lut->norms, lut->Rs, lut->d_in, lut->d_isos, lut->fw_prep, lut->sandi_prep, lut->czb_prep};
+                  lut->norms, lut->Rs, lut->d_in, lut->d_isos, lut->fw_prep, lut->sandi_prep, lut->sandi_long_prep, lut->czb_prep};
     for (void *p : ps) if (p) hipFree(p);
     if (lut->fw_ready) (void)hipEventDestroy(lut->fw_ready);
     if (lut->sandi_ready) (void)hipEventDestroy(lut->sandi_ready);
+    if (lut->sandi_long_ready) (void)hipEventDestroy(lut->sandi_long_ready);
     if (lut->czb_ready) (void)hipEventDestroy(lut->czb_ready);
     delete lut;
 }
@@ -145,7 +146,7 @@ int amx_lut_upload_sandi(amx_ctx *ctx, const double *signal, const double *norms
     if (!signal || !norms || !Rs || !d_in || !d_isos || !out || nS <= 0 || n_rs < 0 || n_in < 0 || n_iso < 0)
         return amx_bad(ctx, "amx_lut_upload_sandi: bad argument");
     const int n_atoms = n_rs + n_in + n_iso;
-    if (n_atoms <= 0 || n_atoms > 64 || nS > 128) return amx_bad(ctx, "amx_lut_upload_sandi: unsupported size (n_atoms <= 64, nS <= 128)");
+    if (n_atoms <= 0 || n_atoms > 64 || nS > 512) return amx_bad(ctx, "amx_lut_upload_sandi: unsupported size (n_atoms <= 64, nS <= 512)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     amx_lut *lut = new_lut(ctx, 3, nS, n_atoms, 1);
     lut->n_rs = n_rs; lut->n_in = n_in; lut->n_isos = n_iso;

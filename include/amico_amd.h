@@ -82,7 +82,12 @@ int amx_lut_upload_noddi(amx_ctx *ctx, const float *wm, const float *iso, const 
 int amx_lut_upload_freewater(amx_ctx *ctx, const float *D, const float *CSF, const int16_t *htable,
                              int n_perp, int n_iso, int ndirs, int nS, amx_lut **out);
 /* SANDI.  KERNELS['signal'] f64 column-major [nS][n_atoms], ['norms'] f64[n_atoms]
- * (models.pyx:1456-1482); Rs, d_in, d_isos = model parameters used by the maps (:1540-1542) */
+ * (models.pyx:1456-1482); Rs, d_in, d_isos = model parameters used by the maps (:1540-1542).
+ * n_atoms <= 64, nS <= 512: the direction-averaged shells (6 values) as well as the acquisition itself (doDirectionalAverage off, the
+ * reference's default: 306 volumes).  Protocols of more than 128 volumes are fitted in Gram space (A'y of every voxel on the fp64 matrix
+ * cores, then H = A'A + lambda2 I per voxel: csrc/amx_sandi_long.hip) and need lambda2 >= 1e-9 -- an isotropic dictionary has rank
+ * <= shells + 1 < n_atoms, so without the ridge the optimum is not unique; amx_sandi_fit* answer AMX_E_BADARG there.
+ * amx_last_kernel_ms of such a fit: 1 = the solver kernel, 2 = the projection. */
 int amx_lut_upload_sandi(amx_ctx *ctx, const double *signal, const double *norms, const double *Rs,
                          const double *d_in, const double *d_isos, int nS, int n_rs, int n_in,
                          int n_iso, amx_lut **out);
