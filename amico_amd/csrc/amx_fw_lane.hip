@@ -415,8 +415,9 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
     double *buf0 = Hs + 2 * kSlot + 2;
     const int n_chunks = *a.c.n_chunks;
     const int n_units = n_chunks * a.sub_per_chunk;
-    const double tol = 1e-12, inf = __builtin_huge_val();
+    const double inf = __builtin_huge_val();
     // lane state
+    double tol = 1e-12;                      // of the dual test: 1e-12 min(1, max |c|) of the lane's voxel (lane_nnqp)
     const bool warm0 = amx_warm_start(a.c.lam2, a.c.flags);
     constexpr int kBackup = 3;               // block exchanges allowed without progress (Kim & Park)
     bool active = false;
@@ -504,11 +505,14 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
             const int e = take ? buf_pos + rank : 0;
             const int nv = Vb[e];
             const unsigned np0 = Pb[e];
+            double cmax = 0.0;
 #pragma unroll
             for (int j = 0; j < N; j++) {
                 const double cj = Cb[e * NP + j];
                 c[j] = take ? cj : c[j];
+                cmax = fmax(cmax, fabs(cj));
             }
+            if (take) tol = 1e-12 * fmin(cmax, 1.0);
             // warm: the full-set solve and the first block removal happened in k_fw_project (p0: the atoms that stayed)
             if (take) { active = true; vox = nv; P = warm0 ? np0 : 0u; its = warm0 ? 1 : 0; ninf = N + 1; backup = 0; Hl = Hs + buf_slot * kSlot; }
             const int taken = min(__builtin_popcountll(freem), buf_cnt);
@@ -870,7 +874,7 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
     // ==================================================================== consumers: the solver of k_freewater_refill
     const int cw = wave < pw ? wave : wave - 1;
     double *Hs = Hp + (size_t)cw * kFuseHs * kHW;
-    const double tol = 1e-12;
+    double tol = 1e-12;                      // of the dual test: 1e-12 min(1, max |c|) of the lane's voxel (lane_nnqp)
     const bool warm0 = amx_warm_start(a.c.lam2, a.c.flags);
     constexpr int kBackup = 3;
     bool active = false;
@@ -947,11 +951,14 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
             const int e = take ? buf_pos + rank : 0;
             const int nv = Vb[e];
             const unsigned np0 = Pb[e];
+            double cmax = 0.0;
 #pragma unroll
             for (int j = 0; j < N; j++) {
                 const double cj = Cb[e * NP + j];
                 c[j] = take ? cj : c[j];
+                cmax = fmax(cmax, fabs(cj));
             }
+            if (take) tol = 1e-12 * fmin(cmax, 1.0);
             if (take) { active = true; vox = nv; P = warm0 ? np0 : 0u; its = warm0 ? 1 : 0; ninf = N + 1; backup = 0; Hl = Hs + buf_h * kHW; }
             const int taken = min(__builtin_popcountll(freem), buf_cnt);
             buf_pos += taken; buf_cnt -= taken;

@@ -389,7 +389,7 @@ __device__ __forceinline__ void fw_voxel(const FwArgs &a, const float *As, doubl
         if (a.xiso && lane < a.n_iso) a.xiso[(size_t)vox * a.n_iso + lane] = __builtin_nan("");
     }
     if (ok) {
-    NNSolver<NR, NQ, MAXP, true, float> S;
+    NNSolver<NR, NQ, MAXP, true, float, true> S;      // (lambda2 = 0 is plain NNLS: a signal that IS an atom leaves at a zero residual)
     const int st = __builtin_amdgcn_readfirstlane(S.solve(As, ldA, nS, n_atoms, yr, rowok, scl, allowed, a.c.lam1, a.c.lam2, rs, rl, lane));
     if (st == kOverflow) {
         if (lane == 0) { const int k = atomicAdd(a.c.ovf_count, 1); a.c.ovf_list[k] = vox; }
@@ -481,7 +481,7 @@ __device__ __forceinline__ void sandi_voxel(const SandiArgs &a, const double *As
         if (lane == 0 && a.nrmse) a.nrmse[vox] = __builtin_nan("");
     }
     if (ok) {
-    NNSolver<NR, NQ, MAXP, true, double> S;
+    NNSolver<NR, NQ, MAXP, true, double, true> S;
     const int st = __builtin_amdgcn_readfirstlane(S.solve(As, ldA, nS, n_atoms, yr, rowok, scl, allowed, a.c.lam1, a.c.lam2, rs, rl, lane));
     if (st == kOverflow) {
         if (lane == 0) { const int k = atomicAdd(a.c.ovf_count, 1); a.c.ovf_list[k] = vox; }

@@ -89,12 +89,16 @@ template <int N>
 __device__ __forceinline__ int lane_nnqp(const double *__restrict__ Hs, const double (&cc)[N], double (&x)[N],
                                          int n_atoms = N, bool warm = false)
 {
-    const double tol = 1e-12, inf = __builtin_huge_val();
+    const double inf = __builtin_huge_val();
     double z[N];
     unsigned P = 0u;
     int status = 0;
+    // the dual test compares gradients (units of cc) with zero: its tolerance follows the voxel's own scale, so that a voxel of
+    // amplitude 2^-20 is solved as far as one of amplitude 1 (1e-12 as it has always been where max |cc| >= 1)
+    double cmax = 0.0;
 #pragma unroll
-    for (int j = 0; j < N; j++) x[j] = 0.0;
+    for (int j = 0; j < N; j++) { x[j] = 0.0; cmax = fmax(cmax, fabs(cc[j])); }
+    const double tol = 1e-12 * fmin(cmax, 1.0);
     if (warm) {
         P = (1u << n_atoms) - 1u;
         for (int round = 0; round < N && P != 0u; ++round) {

@@ -79,7 +79,12 @@ __device__ __forceinline__ int lane_nnqp_rows(TP A, int ldA, TP T, TP G, TP g0, 
 {
     static_assert(M * (M + 1) / 2 <= kRowsTs, "triangle of a_j a_j' fits its table row");
     constexpr int kTri = M * (M + 1) / 2;
-    const double tol = 1e-12, il2 = 1.0 / lam2;
+    const double il2 = 1.0 / lam2;
+    // the dual test follows the voxel's own scale (lane_nnqp): the atoms are normalised, so |c_j| <= ||y|| -- max |y| stands for it
+    double ymax = 0.0;
+#pragma unroll
+    for (int i = 0; i < M; i++) ymax = fmax(ymax, fabs(y[i]));
+    const double tol = 1e-12 * fmin(ymax, 1.0);
     // c = A'y - lambda1 is never stored (15 doubles = 30 registers the Cholesky would have to live with): c_j is recomputed for
     // the atoms that change sides (below), the dual values are g_j = a_j'(y - w) - lambda1.
     unsigned P = 0u;

@@ -243,7 +243,7 @@ __global__ void __launch_bounds__(64) k_sandi_gram_wave(const SandiLongArgs a)
         }
         // the dual tests compare gradients (units of c) with zero: the tolerance follows the voxel's own scale (k_czb_lane)
         const double cmax = amx::wave_max(fabs(craw));
-        const double tol = 1e-12 * (cmax > 1.0 ? cmax : 1.0);
+        const double tol = 1e-12 * cmax;
         __syncthreads();
         cv[lane] = craw - a.lam1; zat[lane] = 0.0; inP[lane] = at ? 1 : 0; bad[lane] = 0;
         if (lane < 4) shi[lane] = 0;

@@ -258,7 +258,9 @@ __device__ __forceinline__ void tile_column(const AT *As, int ldA, int nS, int t
 // NQ   atoms per lane  (n_atoms <= 64*NQ)
 // MAXP capacity of the passive set (slot space, <= 64)
 // RIDGE lambda2 > 0 (augmented rows kept); AT storage type of A in LDS
-template <int NR, int NQ, int MAXP, bool RIDGE, typename AT>
+// ZEROEXIT the zero-residual exit of the unregularised problem is compiled in (solve()).  The solvers without ridge rows always have it;
+//      FreeWater's and SANDI's, which keep the ridge rows for any lambda2 >= 0, ask for it and take it when lambda1 = lambda2 = 0
+template <int NR, int NQ, int MAXP, bool RIDGE, typename AT, bool ZEROEXIT = !RIDGE>
 struct NNSolver {
     static_assert(MAXP <= kWave, "passive set lives in the lanes of one wavefront");
     // thin QR of the passive columns
@@ -759,8 +761,9 @@ struct NNSolver {
         // either sign, and Lawson-Hanson's strict `w > 0` rule would keep admitting atoms with coefficients ~1e-17 until
         // the iteration cap (a voxel whose signal IS an atom: golden fixture voxel 0).  The point is a Kuhn-Tucker point to
         // working precision: stop there.
+        const bool zero_exit = ZEROEXIT && lam1 == 0.0 && (!RIDGE || lam2 == 0.0);
         double ysq = 0.0;
-        if (lam1 == 0.0 && !RIDGE) {
+        if (zero_exit) {
 #pragma unroll
             for (int rr = 0; rr < NR; rr++) ysq += yr[rr] * yr[rr];
             ysq = wave_sum(ysq);
@@ -784,7 +787,7 @@ struct NNSolver {
                         }
                     }
                 }
-                if (lam1 == 0.0 && !RIDGE && np > 0) {
+                if (zero_exit && np > 0) {
                     double rsq = 0.0;
 #pragma unroll
                     for (int rr = 0; rr < NR; rr++) rsq += r[rr] * r[rr];

@@ -174,15 +174,17 @@ def czb_certificate(K, lut, y, x, lam1, lam2, rows=None):
     return float(np.abs(g[P]).max(initial=0.0)), float(g[~P].max(initial=0.0)), float(x[sel].min())
 
 
-def czb_resolve(A, y, lam1, lam2, refine=3):
+def czb_resolve(A, y, lam1, lam2, refine=3, start=None):
     """the optimum of one voxel by block principal pivoting on H = A'A + lambda2 I, every solve refined against long-double
-    residuals: (x, g) float64 -- the support of x is that of the exact optimum unless an atom is degenerate to ~1e-18"""
+    residuals: (x, g) float64 -- the support of x is that of the exact optimum unless an atom is degenerate to ~1e-18.
+    start: the passive set to begin from (bool [n_atoms]; default: the atoms with c > 0).  Whatever the start, a result is returned
+    only when its own long-double Kuhn-Tucker conditions hold."""
     A = np.asarray(A, dtype=np.float64).astype(LD)
     n = A.shape[1]
     H = A.T @ A + LD(lam2) * np.eye(n, dtype=LD)
     c = A.T @ np.asarray(y, dtype=np.float64).astype(LD) - LD(lam1)
     H64 = H.astype(np.float64)
-    P = np.asarray(c > 0)
+    P = np.asarray(c > 0) if start is None else np.array(start, dtype=bool)
     ninf, backup = n + 1, 3
     for trip in range(20 * n + 50):
         x = np.zeros(n, dtype=LD)
