@@ -36,7 +36,8 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample',
-           'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device']
+           'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device',
+           'amx_dict_set_dense', 'amx_batched_last_dense']
 
 # one row per model fit: what the C entry points amx_<stem>_fit[_f32] / amx_<stem>_fit_device[_f32] differ in.  lib() makes their argtypes
 # from it, _fit_host / _fit_device their calls, models.BaseModel._run the results dict.
@@ -168,6 +169,8 @@ def lib():
     L.amx_dict_upload.argtypes = [c_vp, c_dp, C.c_int, C.c_int, C.c_int, C.POINTER(c_vp)]
     L.amx_dict_destroy.argtypes = [c_vp]
     L.amx_dict_destroy.restype = None
+    L.amx_dict_set_dense.argtypes = [c_vp, c_vp, C.c_int]
+    L.amx_batched_last_dense.argtypes = [c_vp, c_i64p]
     L.amx_nnls_batched.argtypes = [c_vp, c_vp, c_i32p, c_dp, C.c_int64, c_dp, c_dp]
     L.amx_lasso_batched.argtypes = [c_vp, c_vp, c_i32p, c_dp, C.c_int64, C.c_double, C.c_double, c_dp]
     L.amx_nnls_batched_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]
@@ -318,6 +321,13 @@ class Context:
         buf = C.create_string_buffer(2048)
         self.check(lib().amx_last_path(self._h, buf, 2048))
         return buf.value.decode()
+
+    def last_dense(self):
+        """what k_batched_big did in the last synchronised batched call (amx_batched_last_dense): the voxels of a dense dictionary whose
+        support outgrew the 48-atom pass, and the pivoting steps they took together"""
+        out = (C.c_int64 * 2)()
+        self.check(lib().amx_batched_last_dense(self._h, out))
+        return {'voxels': int(out[0]), 'steps': int(out[1])}
 
     def last_seed_stats(self):
         """how the NODDI voxels since the previous sync were settled (amx_last_seed_stats): certification rates of the three stages"""
@@ -636,9 +646,11 @@ def predict_device(ctx, lut, x_t, dirs_t=None, stream=None):
 
 class Dict:
     """amx_dict: the dictionaries of the batched solver entry points (cyspams.interfaces.nnls / lasso, models.pyx:18, batched).
-    A: [n_dicts, m, n] (or [m, n]) in numpy's own layout -- the column-major m x n slices the C ABI wants are made here."""
+    A: [n_dicts, m, n] (or [m, n]) in numpy's own layout -- the column-major m x n slices the C ABI wants are made here.
+    dense=True (or set_dense(True) later) also keeps the Gram matrices of the dictionaries in HBM (n^2 doubles each): on such a dictionary
+    no voxel is refused for the size of its support (amx_dict_set_dense); the default refuses supports of more than 48 atoms."""
 
-    def __init__(self, ctx, A):
+    def __init__(self, ctx, A, dense=False):
         A = np.asarray(A, dtype=np.float64)
         if A.ndim == 2:
             A = A[None]
@@ -649,6 +661,14 @@ class Dict:
         h = c_vp()
         ctx.check(lib().amx_dict_upload(ctx._h, _p(cm, c_dp), self.m, self.n, self.n_dicts, C.byref(h)))
         self._h = h
+        self.dense = False
+        if dense:
+            self.set_dense(True)
+
+    def set_dense(self, on=True, ctx=None):
+        """build (on) or free (off) the Gram tables; ctx: the context to call through (the dictionary's own)"""
+        (ctx or self.ctx).check(lib().amx_dict_set_dense((ctx or self.ctx)._h, self._h, int(bool(on))))
+        self.dense = bool(on)
 
     def __del__(self):
         try:

@@ -2,25 +2,26 @@
 #include "amx_launch.hpp"
 using namespace amx;
 
+// dense: the dictionary keeps its Gram tables (amx_dict_set_dense) -- what overflows the re-run pass goes to list 6 and k_batched_big takes it
 template <int NR, bool RIDGE>
-static int go(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s)
+static int go(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s, bool dense)
 {
     constexpr int NQ = 3, MP = 16, MB = 48;      // passive set of the main pass / of the one-wavefront re-run pass (48: its triangular factors still fit next to a 99 x 145 fp64 tile)
     constexpr int NW = 8;
     return launch_pair<NW>(ctx, a, pl, s, k_batched<NR, NQ, MP, NW, RIDGE, false>, k_batched<NR, NQ, MB, 1, RIDGE, true>,
                            [&](int nw) { return fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, nw, MP, false, RIDGE); },
-                           fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, false, RIDGE), 0, 2);
+                           fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, false, RIDGE), 0, 2, "wavefront-per-voxel solver", dense);
 }
 
 // dictionaries beyond the LDS variants (m > 256 samples, n > 192 atoms, or an fp64 tile larger than a CU's LDS): the same solver with
 // the tile read where it lies (k_batched<..., GT = true>: 8 rows / 4 atoms per lane: m <= 512, n <= 256)
 template <bool RIDGE>
-static int go_global(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s)
+static int go_global(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s, bool dense)
 {
     constexpr int NR = 8, NQ = 4, MP = 16, MB = 48, NW = 4;
     return launch_pair<NW>(ctx, a, pl, s, k_batched<NR, NQ, MP, NW, RIDGE, false, true>, k_batched<NR, NQ, MB, 1, RIDGE, true, true>,
                            [&](int nw) { return fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, nw, MP, false, RIDGE, true); },
-                           fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, false, RIDGE, true), 0, 2);
+                           fit_lds_bytes<double>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, false, RIDGE, true), 0, 2, "wavefront-per-voxel solver", dense);
 }
 
 bool amx_batched_tile_global(int m, int ldA, int n)
@@ -29,11 +30,11 @@ bool amx_batched_tile_global(int m, int ldA, int n)
     return fit_lds_bytes<double>(m, ldA, m <= 128 ? 2 : 4, 3, 1, 48, false, true) > kLdsPerCU;
 }
 
-int amx_launch_batched(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge)
+int amx_launch_batched(amx_ctx *ctx, BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge, bool dense)
 {
-    if (amx_batched_tile_global(a.c.nS, a.c.ldA, a.c.n_atoms)) return ridge ? go_global<true>(ctx, a, pl, s) : go_global<false>(ctx, a, pl, s);
-    if (ridge) return a.c.nS <= 128 ? go<2, true>(ctx, a, pl, s) : go<4, true>(ctx, a, pl, s);
-    return a.c.nS <= 128 ? go<2, false>(ctx, a, pl, s) : go<4, false>(ctx, a, pl, s);
+    if (amx_batched_tile_global(a.c.nS, a.c.ldA, a.c.n_atoms)) return ridge ? go_global<true>(ctx, a, pl, s, dense) : go_global<false>(ctx, a, pl, s, dense);
+    if (ridge) return a.c.nS <= 128 ? go<2, true>(ctx, a, pl, s, dense) : go<4, true>(ctx, a, pl, s, dense);
+    return a.c.nS <= 128 ? go<2, false>(ctx, a, pl, s, dense) : go<4, false>(ctx, a, pl, s, dense);
 }
 
 // ------------------------------------------------------------------ the C entry points
@@ -60,7 +61,8 @@ static int batched_dev(amx_ctx *ctx, const amx_dict *dict, const int32_t *d_idx,
     a.x = d_x; a.rnorm = d_rnorm;
     // (voxels with a bad dictionary index are skipped: defined zeros)
     HIPCHK(ctx, hipMemsetAsync(d_x, 0, (size_t)n_vox * dict->n * sizeof(double), s));
-    rc = amx_launch_batched(ctx, a, pl, s, ridge);
+    rc = amx_launch_batched(ctx, a, pl, s, ridge, dict->dense);
+    if (!rc && dict->dense) rc = amx_launch_batched_big(ctx, a, dict, pl, s);      // (one launch that finds a zero count when nothing overflowed)
     fold_counters(ctx, s);
     rec(ctx, 1, s);
     return rc;
@@ -95,7 +97,37 @@ void amx_dict_destroy(amx_dict *h)
     if (!h) return;
     if (h->ctx) hipSetDevice(h->ctx->device);
     if (h->tiles) hipFree(h->tiles);
+    if (h->gram) hipFree(h->gram);
     delete h;
+}
+
+int amx_dict_set_dense(amx_ctx *ctx, amx_dict *dict, int on)
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (!dict || dict->ctx != ctx) return amx_bad(ctx, "amx_dict_set_dense: not a dictionary of this ctx");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    if (!on) {
+        dict->dense = false;
+        if (dict->gram) HIPCHK(ctx, hipFree(dict->gram));              // (waits for the kernels that read it)
+        dict->gram = nullptr;
+        return AMX_OK;
+    }
+    if (dict->dense) return AMX_OK;
+    const int ldG = dict->ldA;
+    double *g = nullptr;
+    HIPCHK(ctx, hipMalloc((void **)&g, (size_t)dict->n_dicts * dict->n * ldG * sizeof(double)));      // (failure: the dictionary stays as it was)
+    dict->gram = g; dict->ldG = ldG;
+    const int rc = amx_build_dict_gram(ctx, dict);
+    if (rc) { (void)hipFree(g); dict->gram = nullptr; return rc; }
+    dict->dense = true;
+    return AMX_OK;
+}
+
+int amx_batched_last_dense(amx_ctx *ctx, int64_t out[2])
+{
+    if (!ctx || !out) return AMX_E_BADARG;
+    out[0] = ctx->dense_stats[0]; out[1] = ctx->dense_stats[1];
+    return AMX_OK;
 }
 
 int amx_nnls_batched_device(amx_ctx *ctx, const amx_dict *dict, const int32_t *d_dict_idx, const double *d_y, int64_t n_vox, double *d_x,

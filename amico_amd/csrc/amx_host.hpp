@@ -61,6 +61,7 @@ struct amx_ctx : WorkSet {
     bool ev_valid[kEv];
     int64_t stats[4] = {0, 0, 0, 0};
     int64_t seed_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // amx_last_seed_stats
+    int64_t dense_stats[2] = {0, 0};   // amx_batched_last_dense: voxels k_batched_big solved in the last synchronised call, its pivoting steps
     int64_t uncert_vox[3] = {0, 0, 0};   // ... of which a stage ran without its Gram-space certificate (shape gate, AMX_NO_GCERT)
     int64_t seeded_vox = 0;        // voxels enqueued on the seed -> certificate chain since the last amx_sync_status
     double *dbg_x = nullptr;       // AMX_F_DEBUG_X destination (caller-owned device buffer, amx_set_debug_x)
@@ -264,6 +265,11 @@ struct amx_dict {
     amx_ctx *ctx = nullptr;
     int m = 0, n = 0, ldA = 0, tile_stride = 0, n_dicts = 0;
     double *tiles = nullptr;       // device f64 [n_dicts][m][ldA] (row-major, odd leading dimension)
+    // amx_dict_set_dense: the Gram matrices G_d = A_d'A_d, device f64 [n_dicts][n][ldG]; voxels whose support outgrows the 48-atom re-run
+    // pass go to k_batched_big (amx_batched_big.hip) instead of AMX_E_OVERFLOW
+    bool dense = false;
+    double *gram = nullptr;
+    int ldG = 0;
 };
 
 // principal-direction estimator of one acquisition scheme (amx_signal.hip)
@@ -407,7 +413,9 @@ int amx_launch_noddi_s3(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStre
 int amx_launch_fw(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);
 int amx_launch_sandi(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
 int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_batched(amx_ctx *ctx, amx::BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge);
+int amx_launch_batched(amx_ctx *ctx, amx::BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge, bool dense = false);
+int amx_launch_batched_big(amx_ctx *ctx, const amx::BatchedArgs &a, const amx_dict *dict, const Plan &pl, hipStream_t s);   // amx_batched_big.hip: a dense dictionary's voxels beyond 48 atoms
+int amx_build_dict_gram(amx_ctx *ctx, const amx_dict *dict);                                                              // ... and its Gram tables
 int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
 int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
 // lane-per-voxel variants for dictionaries of <= 16 atoms (amx_fw_lane.hip, amx_sandi_lane.hip)

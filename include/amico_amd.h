@@ -278,10 +278,23 @@ int amx_debug_fetch(amx_ctx *ctx, const amx_lut *lut, int which, void *dst, size
  * Lawson-Hanson / its elastic-net form with a thin QR of the passive columns, one wavefront per voxel, strict Kuhn-Tucker stop
  * (csrc/amx_solver.hpp); a support of more than 48 atoms is beyond it (AMX_E_OVERFLOW -- AMICO's problems end at ~25).  A voxel with a non-finite signal gets NaN; an index outside [0, n_dicts) is reported like a bad
  * direction (AMX_E_DIR_OOB, the first offending voxel in the message) and its x stays zero.  The *_device forms take device
- * pointers and a hipStream_t and are asynchronous (amx_sync_status returns the status).                                      */
+ * pointers and a hipStream_t and are asynchronous (amx_sync_status returns the status).
+ * Supports of ANY size, opt-in per dictionary -- the reference's nnls / lasso have no cap below min(m, n):
+ *   amx_dict_set_dense       on != 0: build the Gram matrices G_d = A_d'A_d on the GPU from the uploaded tiles (f64[n_dicts][n][ldG]: n^2
+ *                            doubles per dictionary, and a build pass -- only the caller who needs dense supports pays for them) and mark the
+ *                            dictionary.  On a marked dictionary the four batched calls never answer AMX_E_OVERFLOW for the size of a support:
+ *                            the voxels the 48-atom pass cannot hold are solved by k_batched_big (csrc/amx_batched_big.hip: block principal
+ *                            pivoting in Gram space, a workgroup per voxel, the result checked against the true residual), every other voxel
+ *                            exactly as on an unmarked dictionary.  Idempotent; on == 0 frees the tables and clears the mark; a dictionary of
+ *                            another ctx is AMX_E_BADARG; a failed allocation is AMX_E_HIP and leaves the dictionary unmarked.
+ *                            amx_dict_destroy frees the tables.  An unmarked dictionary enqueues exactly what it did before.
+ *   amx_batched_last_dense   of the last synchronised batched call: out[0] = voxels k_batched_big solved, out[1] = its pivoting steps
+ *                            (factorisations) over all of them.                                                                          */
 typedef struct amx_dict amx_dict;
 int  amx_dict_upload(amx_ctx *ctx, const double *A, int m, int n, int n_dicts, amx_dict **out);
 void amx_dict_destroy(amx_dict *dict);
+int  amx_dict_set_dense(amx_ctx *ctx, amx_dict *dict, int on);
+int  amx_batched_last_dense(amx_ctx *ctx, int64_t out[2]);
 int amx_nnls_batched(amx_ctx *ctx, const amx_dict *dict, const int32_t *dict_idx, const double *y, int64_t n_vox,
                      double *x, double *rnorm);
 int amx_lasso_batched(amx_ctx *ctx, const amx_dict *dict, const int32_t *dict_idx, const double *y, int64_t n_vox,
