@@ -273,7 +273,8 @@ int freewater_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = fit_open(ctx, m, c, pl, refill ? amx_refill_chunk(c.n) : kChunk, xiso, lut->n_iso)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
     a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = c.is_mouse; a.n_maps = fit_maps(m, c); a.xiso = xiso;
     if (refill && (rc = amx_fw_prepare(ctx, lut, a, s))) return rc;
-    return fit_close(ctx, c, amx_launch_fw(ctx, a, pl, s));
+    // (more than 64 atoms: the dense route, amx_enet_big.hip -- the dictionary's shape alone decides)
+    return fit_close(ctx, c, amx_big_dictionary(lut) ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s) : amx_launch_fw(ctx, a, pl, s));
 }
 
 // ------------------------------------------------------------------ SANDI
@@ -285,10 +286,13 @@ int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;      // (one dictionary: no bucketing)
     a.norms = lut->norms; a.Rs = lut->Rs; a.d_in = lut->d_in; a.d_isos = lut->d_isos;
     a.n_rs = lut->n_rs; a.n_in = lut->n_in; a.n_iso = lut->n_isos;
+    // protocols without the directional average need the ridge: an isotropic dictionary has rank <= shells + 1 < n_atoms, so without it the optimum
+    // is not unique and A'A alone is singular
+    if (lut->nS > kSandiShortNS && c.lam2 < 1e-9) return fit_bad(ctx, m, ": protocols of more than 128 volumes need lambda2 >= 1e-9 (Gram-space solver)");
+    // more than 64 atoms: the dense route, whatever the protocol (amx_enet_big.hip; the voxels in order, no per-call counters)
+    if (amx_big_dictionary(lut)) return fit_close(ctx, c, amx_launch_enet_big(ctx, lut, a, c.n, s), false);
     if (lut->nS > kSandiShortNS) {
-        // protocols without the directional average: c = A'y on the matrix cores, then the Gram-space solvers (amx_sandi_long.hip).  They need the
-        // ridge: an isotropic dictionary has rank <= shells + 1 < n_atoms, so without it the optimum is not unique and A'A alone is singular
-        if (c.lam2 < 1e-9) return fit_bad(ctx, m, ": protocols of more than 128 volumes need lambda2 >= 1e-9 (Gram-space solver)");
+        // c = A'y on the matrix cores, then the Gram-space solvers (amx_sandi_long.hip)
         if ((rc = amx_sandi_long_prepare(ctx, lut, c.lam2, s))) return rc;
         return fit_close(ctx, c, amx_launch_sandi_long(ctx, lut, a, c.n, s), false);      // (the voxels in order, no per-call counters)
     }
@@ -313,7 +317,7 @@ int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;
     a.n_rs = lut->n_rs; a.n_perp = lut->n_perp; a.Rs = lut->Rs; a.gram = lut->gram; a.ldG = lut->ldG;
     if (fast) { if (!(rc = amx_czb_prepare(ctx, lut, c.lam2, s))) rc = amx_launch_czb_fast(ctx, lut, a, pl, s); }
-    else rc = amx_launch_czb(ctx, a, pl, s);
+    else rc = amx_big_dictionary(lut) ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s) : amx_launch_czb(ctx, a, pl, s);
     return fit_close(ctx, c, rc);
 }
 

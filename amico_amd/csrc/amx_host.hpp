@@ -225,7 +225,7 @@ struct amx_lut {
     int n_perp = 0, n_iso = 0;     // FreeWater
     int n_rs = 0, n_in = 0, n_isos = 0;   // SANDI
     void *tiles = nullptr;
-    double *gram = nullptr, *gram_dwi = nullptr;   // per-orientation Gram matrices (NODDI)
+    double *gram = nullptr, *gram_dwi = nullptr;   // per-orientation Gram matrices (NODDI; gram: CylinderZeppelinBall, and every dictionary of more than 64 atoms)
     double *basis_U = nullptr, *basis_S = nullptr; // per-orientation compressed basis and dictionary (amx_seed.hpp), NODDI
     double *screen2_kappa0 = nullptr;
     double *u2iso = nullptr;       // [ndirs][12] U2'iso (amx_build_basis)
@@ -416,6 +416,15 @@ int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s)
 int amx_launch_batched(amx_ctx *ctx, amx::BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge, bool dense = false);
 int amx_launch_batched_big(amx_ctx *ctx, const amx::BatchedArgs &a, const amx_dict *dict, const Plan &pl, hipStream_t s);   // amx_batched_big.hip: a dense dictionary's voxels beyond 48 atoms
 int amx_build_dict_gram(amx_ctx *ctx, const amx_dict *dict);                                                              // ... and its Gram tables
+// FreeWater, SANDI and CylinderZeppelinBall on dictionaries of kSmallMaxAtoms + 1 .. kBigMaxAtoms atoms (amx_enet_big.hip): the Gram tables made at
+// the upload, and k_enet_big -- a workgroup per voxel, in bucket order (SANDI: the voxels in order).  The route is chosen from the dictionary's shape alone.
+constexpr int kSmallMaxAtoms = 64;     // what the wavefront-per-voxel kernels of these models hold (a lane per atom)
+constexpr int kBigMaxAtoms = 256;      // a thread per atom
+static inline bool amx_big_dictionary(const amx_lut *lut) { return lut->n_atoms > kSmallMaxAtoms; }
+int amx_build_big_gram(amx_ctx *ctx, amx_lut *lut);
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::FwArgs &a, const Plan &pl, int64_t n, hipStream_t s);
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s);
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s);
 int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
 int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
 // lane-per-voxel variants for dictionaries of <= 16 atoms (amx_fw_lane.hip, amx_sandi_lane.hip)

@@ -125,7 +125,7 @@ int amx_lut_upload_freewater(amx_ctx *ctx, const float *D, const float *CSF, con
     if (!D || !CSF || !htable || !out || n_perp <= 0 || n_iso <= 0 || ndirs <= 0 || nS <= 0)
         return amx_bad(ctx, "amx_lut_upload_freewater: bad argument");
     const int n_atoms = n_perp + n_iso;
-    if (n_atoms > 64 || nS > 512) return amx_bad(ctx, "amx_lut_upload_freewater: unsupported size (n_atoms <= 64, nS <= 512)");
+    if (n_atoms > kBigMaxAtoms || nS > 512) return amx_bad(ctx, "amx_lut_upload_freewater: unsupported size (n_atoms <= 256, nS <= 512)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     amx_lut *lut = new_lut(ctx, 2, nS, n_atoms, ndirs);
     lut->n_perp = n_perp; lut->n_iso = n_iso;
@@ -134,6 +134,7 @@ int amx_lut_upload_freewater(amx_ctx *ctx, const float *D, const float *CSF, con
     if ((rc = build_tiles(ctx, lut, D, (size_t)n_perp * ndirs * nS, CSF, (size_t)n_iso * nS, ones, n_perp))) { amx_lut_destroy(lut); return rc; }
     std::vector<short> ht(htable, htable + 181 * 181);
     if ((rc = amx_upload(ctx, &lut->htable, ht.data(), ht.size()))) { amx_lut_destroy(lut); return rc; }
+    if (amx_big_dictionary(lut) && (rc = amx_build_big_gram(ctx, lut))) { amx_lut_destroy(lut); return rc; }      // (more than 64 atoms: k_enet_big works on A'A)
     *out = lut;
     return AMX_OK;
 }
@@ -146,7 +147,7 @@ int amx_lut_upload_sandi(amx_ctx *ctx, const double *signal, const double *norms
     if (!signal || !norms || !Rs || !d_in || !d_isos || !out || nS <= 0 || n_rs < 0 || n_in < 0 || n_iso < 0)
         return amx_bad(ctx, "amx_lut_upload_sandi: bad argument");
     const int n_atoms = n_rs + n_in + n_iso;
-    if (n_atoms <= 0 || n_atoms > 64 || nS > 512) return amx_bad(ctx, "amx_lut_upload_sandi: unsupported size (n_atoms <= 64, nS <= 512)");
+    if (n_atoms <= 0 || n_atoms > kBigMaxAtoms || nS > 512) return amx_bad(ctx, "amx_lut_upload_sandi: unsupported size (n_atoms <= 256, nS <= 512)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     amx_lut *lut = new_lut(ctx, 3, nS, n_atoms, 1);
     lut->n_rs = n_rs; lut->n_in = n_in; lut->n_isos = n_iso;
@@ -159,6 +160,7 @@ int amx_lut_upload_sandi(amx_ctx *ctx, const double *signal, const double *norms
         (rc = amx_upload(ctx, &lut->Rs, Rs, (size_t)(n_rs ? n_rs : 1))) || (rc = amx_upload(ctx, &lut->d_in, d_in, (size_t)(n_in ? n_in : 1))) ||
         (rc = amx_upload(ctx, &lut->d_isos, d_isos, (size_t)(n_iso ? n_iso : 1)))) { lut->tiles = dt; amx_lut_destroy(lut); return rc; }
     lut->tiles = dt;
+    if (amx_big_dictionary(lut) && (rc = amx_build_big_gram(ctx, lut))) { amx_lut_destroy(lut); return rc; }
     *out = lut;
     return AMX_OK;
 }
@@ -170,7 +172,7 @@ int amx_lut_upload_czb(amx_ctx *ctx, const float *wmr, const float *wmh, const f
     if (!wmr || !wmh || !iso || !Rs || !htable || !out || n_rs <= 0 || n_perp <= 0 || n_iso <= 0 || ndirs <= 0 || nS <= 0)
         return amx_bad(ctx, "amx_lut_upload_czb: bad argument");
     const int n_atoms = n_rs + n_perp + n_iso;
-    if (n_atoms > 64 || nS > 512) return amx_bad(ctx, "amx_lut_upload_czb: unsupported size (n_atoms <= 64, nS <= 512)");
+    if (n_atoms > kBigMaxAtoms || nS > 512) return amx_bad(ctx, "amx_lut_upload_czb: unsupported size (n_atoms <= 256, nS <= 512)");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     amx_lut *lut = new_lut(ctx, 4, nS, n_atoms, ndirs);
     lut->n_rs = n_rs; lut->n_perp = n_perp; lut->n_iso = n_iso;
@@ -183,7 +185,12 @@ int amx_lut_upload_czb(amx_ctx *ctx, const float *wmr, const float *wmh, const f
     if ((rc = build_tiles(ctx, lut, rot.data(), rot.size(), iso, (size_t)n_iso * nS, ones, n_rs + n_perp))) { amx_lut_destroy(lut); return rc; }
     std::vector<short> ht(htable, htable + 181 * 181);
     if ((rc = amx_upload(ctx, &lut->htable, ht.data(), ht.size())) || (rc = amx_upload(ctx, &lut->Rs, Rs, (size_t)n_rs))) { amx_lut_destroy(lut); return rc; }
-    // Gram matrices of every orientation: the solver works on A'A + lambda2 I (amx_gram_solver.hpp)
+    // Gram matrices of every orientation: the solver works on A'A + lambda2 I (amx_gram_solver.hpp; more than 64 atoms: amx_enet_big.hip)
+    if (amx_big_dictionary(lut)) {
+        if ((rc = amx_build_big_gram(ctx, lut))) { amx_lut_destroy(lut); return rc; }
+        *out = lut;
+        return AMX_OK;
+    }
     lut->ldG = 64;
     const size_t gbytes = (size_t)ndirs * n_atoms * lut->ldG * sizeof(double);
     const size_t lds = (size_t)nS * lut->ldA * sizeof(float);

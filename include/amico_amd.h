@@ -78,21 +78,27 @@ int amx_lut_upload_noddi(amx_ctx *ctx, const float *wm, const float *iso, const 
                          const float *icvf, const float *kappa, const int16_t *htable,
                          const int64_t *dwi_idx, int n_wm, int ndirs, int nS, int dwi_count,
                          int is_exvivo, amx_lut **out);
-/* FreeWater.  KERNELS['D'] f32[n_perp][ndirs][nS], ['CSF'] f32[n_iso][nS] (models.pyx:1122-1123) */
+/* FreeWater.  KERNELS['D'] f32[n_perp][ndirs][nS], ['CSF'] f32[n_iso][nS] (models.pyx:1122-1123).
+ * Any shape the reference's loop takes (models.pyx:1231-1276) up to n_perp + n_iso <= 256 atoms, nS <= 512 volumes.  Up to 64 atoms the
+ * dictionary is its tiles; beyond that -- a finer grid of d_perps in model.set() -- the upload also builds the Gram matrices A_d'A_d of every
+ * orientation in HBM (f64, ndirs * n_atoms^2 * 8 bytes: 262 MB at 500 x 256 atoms; "out of device memory" is AMX_E_BADARG) and the fits
+ * take the dense route of csrc/amx_enet_big.hip (k_enet_big: a workgroup per voxel, every output and flag of the smaller dictionaries).
+ * The same holds for SANDI and CylinderZeppelinBall below; the dictionary's shape alone selects the route. */
 int amx_lut_upload_freewater(amx_ctx *ctx, const float *D, const float *CSF, const int16_t *htable,
                              int n_perp, int n_iso, int ndirs, int nS, amx_lut **out);
 /* SANDI.  KERNELS['signal'] f64 column-major [nS][n_atoms], ['norms'] f64[n_atoms]
  * (models.pyx:1456-1482); Rs, d_in, d_isos = model parameters used by the maps (:1540-1542).
- * n_atoms <= 64, nS <= 512: the direction-averaged shells (6 values) as well as the acquisition itself (doDirectionalAverage off, the
+ * n_atoms <= 256, nS <= 512: the direction-averaged shells (6 values) as well as the acquisition itself (doDirectionalAverage off, the
  * reference's default: 306 volumes).  Protocols of more than 128 volumes are fitted in Gram space (A'y of every voxel on the fp64 matrix
  * cores, then H = A'A + lambda2 I per voxel: csrc/amx_sandi_long.hip) and need lambda2 >= 1e-9 -- an isotropic dictionary has rank
- * <= shells + 1 < n_atoms, so without the ridge the optimum is not unique; amx_sandi_fit* answer AMX_E_BADARG there.
+ * <= shells + 1 < n_atoms, so without the ridge the optimum is not unique; amx_sandi_fit* answer AMX_E_BADARG there (whatever the number of atoms).
  * amx_last_kernel_ms of such a fit: 1 = the solver kernel, 2 = the projection. */
 int amx_lut_upload_sandi(amx_ctx *ctx, const double *signal, const double *norms, const double *Rs,
                          const double *d_in, const double *d_isos, int nS, int n_rs, int n_in,
                          int n_iso, amx_lut **out);
 /* CylinderZeppelinBall.  KERNELS['wmr'] f32[n_rs][ndirs][nS] (cylinders), ['wmh'] f32[n_perp][ndirs][nS] (zeppelins),
- * ['iso'] f32[n_iso][nS] (balls) (models.pyx:488-520); Rs = model.Rs f64[n_rs] in metres, used by the maps (:627) */
+ * ['iso'] f32[n_iso][nS] (balls) (models.pyx:488-520); Rs = model.Rs f64[n_rs] in metres, used by the maps (:627).
+ * n_rs + n_perp + n_iso <= 256 atoms, nS <= 512 volumes (more than 64 atoms: see FreeWater above). */
 int amx_lut_upload_czb(amx_ctx *ctx, const float *wmr, const float *wmh, const float *iso, const double *Rs,
                        const int16_t *htable, int n_rs, int n_perp, int n_iso, int ndirs, int nS, amx_lut **out);
 void amx_lut_destroy(amx_lut *lut);
