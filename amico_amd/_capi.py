@@ -27,7 +27,8 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_noddi_fit_device_f32', 'amx_freewater_fit_device_f32', 'amx_sandi_fit_device_f32', 'amx_czb_fit_device_f32',
            'amx_set_debug_x', 'amx_set_fw_iso', 'amx_freewater_corrected_device', 'amx_prep_corrected_device', 'amx_predict_device', 'amx_prep_predicted_device', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
            'amx_set_profiling', 'amx_last_kernel_ms', 'amx_last_stats', 'amx_last_seed_stats', 'amx_last_host_narrowed', 'amx_last_path', 'amx_host_pool_info', 'amx_selftest',
-           'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32', 'amx_prep_gather_device_f32',
+           'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
+           'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
            'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
@@ -185,6 +186,10 @@ def lib():
     L.amx_dti_directions.argtypes = [c_vp, c_vp, c_dp, C.c_int64, c_dp]
     L.amx_dti_directions_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]
     L.amx_dti_directions_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int64, c_vp, c_vp]
+    n_out = len(Dti.OUTPUTS)        # ctx, dti, y, n, min_diffusivity, one pointer per row of Dti.OUTPUTS (, stream)
+    L.amx_dti_fit.argtypes = [c_vp, c_vp, c_dp, C.c_int64, C.c_double] + [c_dp] * n_out
+    L.amx_dti_fit_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 1)
+    L.amx_dti_fit_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 1)
     L.amx_prep_create.argtypes = [c_vp, c_i64p, c_i64p, C.c_int, c_i32p, C.c_int64, c_i32p, c_i32p, C.c_int,
                                   c_i32p, C.c_int, C.c_int, C.POINTER(c_vp)]
     L.amx_prep_destroy.argtypes = [c_vp]
@@ -605,15 +610,20 @@ def sandi_fit_device(ctx, lut, y_t, lambda1, lambda2, rmse=False, nrmse=False, s
     return _fit_device(FIT['sandi'], ctx, lut, y_t, None, lambda1, lambda2, (), dict(rmse=rmse, nrmse=nrmse), stream, return_x, False)
 
 
-def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None):
+def freewater_corrected_device(ctx, lut, y_t, xiso_t, stream=None, into=None):
     """y f32 | f64 [n, nS] and x_iso f64 [n, n_iso] (device tensors) -> y_corrected f64 [n, nS] (models.pyx:1264-1274): the rows
-    AMX_F_CORRECTED writes, from the coefficients a fit with iso=True left (amx_freewater_corrected_device); enqueued on `stream`"""
+    AMX_F_CORRECTED writes, from the coefficients a fit with iso=True left (amx_freewater_corrected_device); enqueued on `stream`.
+    into: the float64 device tensor [n, nS] to write (default: a new one)"""
     import torch
     _check_dev(lut, y_t)
     n = y_t.shape[0]
     if xiso_t.dtype != torch.float64 or tuple(xiso_t.shape) != (n, lut.n_iso) or not xiso_t.is_contiguous() or xiso_t.device != y_t.device:
         raise ValueError(f'x_iso must be a contiguous float64 device tensor [n_vox, {lut.n_iso}] on the device of y')
-    yc = torch.empty((n, lut.nS), dtype=torch.float64, device=y_t.device)
+    yc = into
+    if yc is None:
+        yc = torch.empty((n, lut.nS), dtype=torch.float64, device=y_t.device)
+    elif yc.dtype != torch.float64 or tuple(yc.shape) != (n, lut.nS) or not yc.is_contiguous() or yc.device != y_t.device:
+        raise ValueError(f'into must be a contiguous float64 device tensor [n_vox, {lut.nS}] on the device of y')
     f32 = y_t.dtype == torch.float32
     ctx.check(lib().amx_freewater_corrected_device(ctx._h, lut._h, _dptr(y_t) if f32 else None, None if f32 else _dptr(y_t), _dptr(xiso_t),
                                                    n, _dptr(yc), c_vp(stream or 0)))
@@ -722,6 +732,8 @@ class Dti:
     """amx_dti: principal-direction estimator of one acquisition scheme (include/amico_amd.h, row f1)."""
 
     METHODS = {'OLS': 0, 'WLS': 1, 'NLLS': 2}        # AMX_DTI_* (include/amico_amd.h)
+    # the outputs of amx_dti_fit* in ABI order: (name, values per voxel); all float64.  scalars = FA, MD, AD, RD
+    OUTPUTS = (('directions', 3), ('evals', 3), ('scalars', 4))
 
     def __init__(self, ctx, inv_design, min_signal=1e-4, design=None, method='OLS'):
         w = np.ascontiguousarray(inv_design, dtype=np.float64)
@@ -778,6 +790,27 @@ class Dti:
         """device pointers (ints), enqueued on `stream`; check with ctx.sync(stream).  f32: d_y holds float32 signals."""
         fn = lib().amx_dti_directions_device_f32 if f32 else lib().amx_dti_directions_device
         self.ctx.check(fn(self.ctx._h, self._h, c_vp(d_y), int(n_vox), c_vp(d_dirs), c_vp(stream or 0)))
+
+    def fit(self, y, min_diffusivity, want=None):
+        """y f64[n_vox, nS] (host) -> {name: f64[n_vox, k]} for the rows of OUTPUTS named in `want` (default: all) -- amx_dti_fit"""
+        y = np.ascontiguousarray(y, dtype=np.float64)
+        if y.ndim != 2 or y.shape[1] != self.nS:
+            raise ValueError('y must be [n_vox, %d]' % self.nS)
+        want = [name for name, _ in self.OUTPUTS] if want is None else list(want)
+        unknown = [w for w in want if w not in dict(self.OUTPUTS)]
+        if unknown or not want:
+            raise ValueError('want must name some of %s' % ', '.join(name for name, _ in self.OUTPUTS))
+        out = {name: np.zeros((y.shape[0], k)) for name, k in self.OUTPUTS if name in want}
+        ptrs = [_p(out[name], c_dp) if name in out else None for name, _ in self.OUTPUTS]
+        self.ctx.check(lib().amx_dti_fit(self.ctx._h, self._h, _p(y, c_dp), y.shape[0], float(min_diffusivity), *ptrs))
+        return out
+
+    def fit_device(self, d_y, n_vox, min_diffusivity, d_dirs=None, d_evals=None, d_scalars=None, stream=None, f32=False):
+        """directions_device with the eigenvalues f64 [n_vox, 3] and FA, MD, AD, RD f64 [n_vox, 4]; a pointer of None (or 0) leaves that
+        output out, and with d_evals and d_scalars both None this is directions_device (amx_dti_fit_device[_f32])"""
+        fn = lib().amx_dti_fit_device_f32 if f32 else lib().amx_dti_fit_device
+        ptrs = [c_vp(p or 0) for p in (d_dirs, d_evals, d_scalars)]
+        self.ctx.check(fn(self.ctx._h, self._h, c_vp(d_y), int(n_vox), float(min_diffusivity), *ptrs, c_vp(stream or 0)))
 
 
 class Prep:

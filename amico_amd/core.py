@@ -11,6 +11,7 @@ in-memory volumes, every per-voxel step on the GPU:
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
              principal directions from the tensor fit (DTI_fit_method)          -> ``DIRs``   (amx_dti_directions)
+             with doSaveTensorMaps: the same fit's eigenvalues, FA, MD, AD, RD   -> ``DTI_evals``, ``DTI_MAPs`` (amx_dti_fit)
              model.fit(self)                                                    -> maps       (amx_*_fit)
              scatter into float32 volumes (core.py:472-498)                     -> ``RESULTS`` (amx_prep_scatter)
 
@@ -64,6 +65,7 @@ class Evaluation:
         self.set_config('nthreads', -1)
         self.set_config('DTI_fit_method', 'OLS')
         self.set_config('BLAS_nthreads', 1)
+        self.set_config('doSaveTensorMaps', False)     # not a key of the reference: see fit()
 
     # `niiDWI_img` (core.py:136) is the raw float32 image.  When set_data kept the image in its stored dtype the float32 array is made
     # on first read, by the numpy expression the ingest kernel is held to, and cached; fit() itself never needs it
@@ -240,6 +242,25 @@ class Evaluation:
         self.set_config('load_kernels_time', time.time() - t)
 
     def fit(self):
+        """The chain of the module docstring.  Config keys that are not the reference's:
+
+        doSavePredictedSignal   RESULTS['DWI_predicted'], results['y_est'].
+        doSaveTensorMaps        (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
+            FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
+            the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
+            two kernels, the gather and then the tensor pass, for every method -- here that is the route of always; in the volume
+            pipelines (pipeline.py, tensor_maps=True) it means that the OLS fit no longer rides on the fused gather.  With
+            `directions` given to set_data the tensor pass runs for the maps only and `DIRs` stay the caller's.  'RT' / 'RESTORE'
+            raise NotImplementedError as they do whenever a tensor fit would run; doDirectionalAverage leaves no gradient
+            directions to fit a tensor to and raises ValueError before anything is uploaded.
+            Free-Water: also RESULTS['DTI_MAPs_corrected'] / ['DTI_evals_corrected'], the same fit on the free-water-corrected rows
+            (results['y_corrected'], made in HBM from the fit's isotropic coefficients; doSaveCorrectedDWI need not be set;
+            min_signal clips what the correction left non-positive, as for any signal)."""
+        tensor_maps = bool(self.get_config('doSaveTensorMaps'))
+        # (a contradiction in the configuration itself: said first, before a context is made or anything is uploaded)
+        if tensor_maps and self.get_config('doDirectionalAverage'):
+            raise ValueError('doSaveTensorMaps needs the gradient directions: with doDirectionalAverage the signal is one value per '
+                             'shell and there is no tensor to fit')
         if self._raw is None and self._img32 is None:
             raise RuntimeError('Data not loaded; call "set_data()" first')
         if self.model is None:
@@ -249,6 +270,8 @@ class Evaluation:
         if self.KERNELS['model'] != self.model.id:
             raise RuntimeError('Response functions were not created with the same model')
         _dti.check_fit_method(self.get_config('DTI_fit_method'))     # core.py:419-420: before anything is uploaded
+        if tensor_maps and len(_models.get_contexts()) > 1:
+            raise NotImplementedError('doSaveTensorMaps is not built for several devices (set_devices)')
         if self.get_config('doSavePredictedSignal') and len(_models.get_contexts()) > 1:
             raise NotImplementedError('doSavePredictedSignal is not built for several devices (set_devices)')
         nt = self.get_config('nthreads')
@@ -297,17 +320,26 @@ class Evaluation:
         self.set_config('bad_samples_preprocessed', ctx.sanitize_last())
         _prep.refuse_or_warn(self.get_config('bad_samples_preprocessed'), bad_value, _prep.BAD_PREPROCESSED)
         # precompute directions (core.py:428-458)
-        d_dirs = None
+        d_dirs = est = d_tmaps = None
         if self.get_config('doDirectionalAverage'):
             pass
         elif self._dirs_img is not None:
             d_dirs = torch.from_numpy(np.ascontiguousarray(self._dirs_img[sel, :], dtype=np.float64)).to(dev)
-        else:
+        if (d_dirs is None and not self.get_config('doDirectionalAverage')) or tensor_maps:
             # (raises NotImplementedError for 'RT' / 'RESTORE': only here, where a tensor fit would actually run)
             est = _dti.TensorDirections.from_scheme(self._raw_scheme, do_merge_b0=self.get_config('doMergeB0'), ctx=ctx,
                                                     fit_method=self.get_config('DTI_fit_method'))
-            d_dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
-            est.fit_device(d_y.data_ptr(), n, d_dirs.data_ptr(), f32=True)
+            d_fit_dirs = None
+            if d_dirs is None:
+                d_fit_dirs = d_dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
+            if tensor_maps:
+                # doSaveTensorMaps: the kernel variant that also writes what its eigen-solve has; given directions stay the caller's
+                d_tmaps = {'DTI_evals': torch.empty((n, 3), dtype=torch.float64, device=dev),
+                           'DTI_MAPs': torch.empty((n, 4), dtype=torch.float64, device=dev)}
+                est.fit_device(d_y.data_ptr(), n, None if d_fit_dirs is None else d_fit_dirs.data_ptr(), f32=True,
+                               d_evals=d_tmaps['DTI_evals'].data_ptr(), d_scalars=d_tmaps['DTI_MAPs'].data_ptr())
+            else:
+                est.fit_device(d_y.data_ptr(), n, d_fit_dirs.data_ptr(), f32=True)
         ctx.sync()
         del d_img
         if self._prep.debias_snr is not None:
@@ -379,6 +411,22 @@ class Evaluation:
                 if keep_b0:
                     y_corrected[:, b0_idx] = self.y[:, b0_idx] * np.reshape(self.mean_b0s, (-1, 1))
                 self.RESULTS['DWI_corrected'] = self._prep.scatter(y_corrected)
+        if tensor_maps:
+            if self.model.name == 'Free-Water':
+                # the same tensor fit on the free-water-corrected rows: made in HBM from the isotropic coefficients by the kernel behind
+                # results['y_corrected'], read in place by the tensor pass; they never come to the host
+                x_iso = out.get('x_iso')
+                if x_iso is None:
+                    raise NotImplementedError("doSaveTensorMaps: this Free-Water fit left no isotropic coefficients in HBM")
+                d_yc = _capi.freewater_corrected_device(ctx, self._dev['lut'], self._dev['y'], x_iso)
+                for key, k in (('DTI_evals', 3), ('DTI_MAPs', 4)):
+                    d_tmaps[key + '_corrected'] = torch.empty((n, k), dtype=torch.float64, device=dev)
+                est.fit_device(d_yc.data_ptr(), n, None, d_evals=d_tmaps['DTI_evals_corrected'].data_ptr(),
+                               d_scalars=d_tmaps['DTI_MAPs_corrected'].data_ptr())
+            for key in ('DTI_MAPs', 'DTI_evals', 'DTI_MAPs_corrected', 'DTI_evals_corrected'):
+                if key in d_tmaps:
+                    out[key] = d_tmaps[key]
+                    self.RESULTS[key] = sc(key, None)
         if self.get_config('doSavePredictedSignal'):
             # the fit left its coefficients in HBM: dictionary, x, DIRs (and mean_b0) -> the float32 volume in one kernel, one copy home;
             # neither y nor the rows results['y_est'] come to the host (amx_prep_predicted_device)

@@ -50,10 +50,34 @@ __device__ __forceinline__ void dti_prefetch(double2 (&pre)[kDtiPre], const floa
     }
 }
 
-template <typename YT>
+// The end of every tensor kernel: the thread's tensor of the batch -> its outputs.  MAPS = false is the principal direction alone.
+// MAPS = true (amx_dti_fit*): besides, evals f64[n][3] -- descending, clipped from below at min_diffusivity as dipy's
+// decompose_tensor does for TensorModel -- and scalars f64[n][4] = FA, MD, AD, RD of the clipped eigenvalues; each of the three
+// outputs may be null.
+template <bool MAPS>
+__device__ __forceinline__ void dti_store(const double (&d)[6], long long v, double *__restrict__ dirs, double min_diffusivity,
+                                          double *__restrict__ evals, double *__restrict__ scalars)
+{
+    double o[3];
+    if constexpr (MAPS) {
+        double e[3], sc[4];
+        tensor_eigen(d, e, o);
+        tensor_scalars(e, min_diffusivity, sc);
+        if (evals) { double *dst = evals + v * 3; dst[0] = e[0]; dst[1] = e[1]; dst[2] = e[2]; }
+        if (scalars) { double *dst = scalars + v * 4; dst[0] = sc[0]; dst[1] = sc[1]; dst[2] = sc[2]; dst[3] = sc[3]; }
+        if (!dirs) return;
+    } else {
+        principal_direction(d, o);
+    }
+    double *dst = dirs + v * 3;
+    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+}
+
+template <typename YT, bool MAPS>
 __global__ __launch_bounds__(kDtiThreads, 4) void k_dti_dirs(const YT *__restrict__ y, const double *__restrict__ wt,
                                                          int nS, int ldl, int tv, long long n, double min_signal,
-                                                         double *__restrict__ dirs)
+                                                         double *__restrict__ dirs, double min_diffusivity,
+                                                         double *__restrict__ evals, double *__restrict__ scalars)
 {
     extern __shared__ double sm[];
     double *wl = sm;                                   // nS * 6
@@ -126,12 +150,10 @@ __global__ __launch_bounds__(kDtiThreads, 4) void k_dti_dirs(const YT *__restric
             if (eslot < slot) {
                 const long long e0 = (batch_tile + (long long)eslot * gridDim.x) * tv;
                 if (e0 + evox < n) {
-                    double d[6], o[3];
+                    double d[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) d[k] = dl[(eslot * tv + evox) * 7 + k];
-                    principal_direction(d, o);
-                    double *dst = dirs + (e0 + evox) * 3;
-                    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+                    dti_store<MAPS>(d, e0 + evox, dirs, min_diffusivity, evals, scalars);
                 }
             }
             slot = 0;
@@ -292,11 +314,14 @@ __device__ __forceinline__ int wave_sum(int x)
 // y f64|f32[n][nS] -> dirs f64[n][3].  wt7 f64[nS][7]: pinv(X)^T with row k scaled by the column scale of X; xs f64[nS][7]: X
 // with its columns scaled to unit max-abs.  stats (NLLS): [0] voxels that kept their starting parameters, [1] trips of the
 // voxels, [2] trips their wavefronts made for them (a voxel waits for the slowest of the 8 in its wavefront).
-template <typename YT, bool NLLS>
+// MAPS: dti_store's.
+template <typename YT, bool NLLS, bool MAPS>
 __global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const YT *__restrict__ y, const double *__restrict__ wt7,
                                                                         const double *__restrict__ xs, DtiScale sc,
                                                                         int nS, int ldl, int tv, long long n, double min_signal,
-                                                                        double *__restrict__ dirs, unsigned long long *__restrict__ stats)
+                                                                        double *__restrict__ dirs, unsigned long long *__restrict__ stats,
+                                                                        double min_diffusivity, double *__restrict__ evals,
+                                                                        double *__restrict__ scalars)
 {
     extern __shared__ double sm[];
     double *wl = sm;                                   // nS * 7
@@ -456,12 +481,10 @@ __global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const 
             if (eslot < slot) {
                 const long long e0 = (batch_tile + (long long)eslot * gridDim.x) * tv;
                 if (e0 + evox < n) {
-                    double d[6], o[3];
+                    double d[6];
 #pragma unroll
                     for (int k = 0; k < 6; k++) d[k] = dl[(eslot * tv + evox) * 7 + k];
-                    principal_direction(d, o);
-                    double *dst = dirs + (e0 + evox) * 3;
-                    dst[0] = o[0]; dst[1] = o[1]; dst[2] = o[2];
+                    dti_store<MAPS>(d, e0 + evox, dirs, min_diffusivity, evals, scalars);
                 }
             }
             slot = 0;
@@ -569,8 +592,12 @@ int amx_dti_last_trips(amx_ctx *ctx, const amx_dti *h, int64_t *out_voxel_trips,
 
 }  // extern "C"
 
-template <typename YT, bool NLLS>
-static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, hipStream_t s)
+// what amx_dti_fit* adds to amx_dti_directions*
+struct DtiMapsOut { double min_diffusivity; double *evals, *scalars; };
+
+template <typename YT, bool NLLS, bool MAPS>
+static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, hipStream_t s,
+                                const DtiMapsOut &mo)
 {
     const int nS = h->nS;
     int ldl = (nS + 3) & ~3;
@@ -583,7 +610,7 @@ static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, i
     if (tv < 2 || lds > 160 * 1024) return amx_bad(ctx, "amx_dti_directions: scheme too long for the LDS tile");
     static bool attr_set[64];
     if (!attr_set[ctx->device & 63]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs_w<YT, NLLS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs_w<YT, NLLS, MAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[ctx->device & 63] = true;
     }
     const long long n_tiles = (n_vox + tv - 1) / tv;
@@ -595,26 +622,28 @@ static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, i
     if (NLLS) HIPCHK(ctx, hipMemsetAsync(h->stats, 0, 4 * sizeof(unsigned long long), s));
     h->last_stream = s;
     rec(ctx, 8, s);
-    hipLaunchKernelGGL((k_dti_dirs_w<YT, NLLS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt7, h->xs, sc, nS, ldl, tv,
-                       (long long)n_vox, h->min_signal, d_dirs, h->stats);
+    hipLaunchKernelGGL((k_dti_dirs_w<YT, NLLS, MAPS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt7, h->xs, sc, nS, ldl, tv,
+                       (long long)n_vox, h->min_signal, d_dirs, h->stats, mo.min_diffusivity, mo.evals, mo.scalars);
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, s);
     return AMX_OK;
 }
 
-template <typename YT>
-static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, void *hip_stream)
+template <typename YT, bool MAPS>
+static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, void *hip_stream,
+                              const DtiMapsOut &mo)
 {
     if (!ctx) return AMX_E_BADARG;
     if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_directions: not an estimator of this ctx");
     if (n_vox < 0) return amx_bad(ctx, "amx_dti_directions: bad n_vox");
+    if (MAPS && !(mo.min_diffusivity >= 0.0)) return amx_bad(ctx, "amx_dti_fit: min_diffusivity must be a number >= 0");
     if (n_vox == 0) return AMX_OK;
-    if (!d_y || !d_dirs) return amx_bad(ctx, "amx_dti_directions: null buffer");
+    if (!d_y || (!MAPS && !d_dirs)) return amx_bad(ctx, "amx_dti_directions: null buffer");
     if (sizeof(YT) == 8 && ((uintptr_t)d_y & 15) != 0) return amx_bad(ctx, "amx_dti_directions: y must be 16-byte aligned");
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (h->method == AMX_DTI_WLS) return dti_directions_w_dev<YT, false>(ctx, h, d_y, n_vox, d_dirs, s);
-    if (h->method == AMX_DTI_NLLS) return dti_directions_w_dev<YT, true>(ctx, h, d_y, n_vox, d_dirs, s);
+    if (h->method == AMX_DTI_WLS) return dti_directions_w_dev<YT, false, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
+    if (h->method == AMX_DTI_NLLS) return dti_directions_w_dev<YT, true, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
     const int nS = h->nS;
     int ldl = (nS + 3) & ~3;                  // row stride = 4 * odd doubles: the 16 quads of a wavefront read
     if (((ldl >> 2) & 1) == 0) ldl += 4;      // conflict-free LDS rows
@@ -624,7 +653,7 @@ static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int
     if (tv < 2 || lds > 160 * 1024) return amx_bad(ctx, "amx_dti_directions: scheme too long for the LDS tile");
     static bool attr_set[64];              // (per instantiation of this function template AND device: the attribute belongs to the pair)
     if (!attr_set[ctx->device & 63]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs<YT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)(k_dti_dirs<YT, MAPS>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[ctx->device & 63] = true;
     }
     const long long n_tiles = (n_vox + tv - 1) / tv;
@@ -632,23 +661,34 @@ static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int
     long long grid = 256LL * (per_cu > 8 ? 8 : per_cu);
     if (grid > n_tiles) grid = n_tiles;
     rec(ctx, 8, s);
-    hipLaunchKernelGGL(k_dti_dirs<YT>, dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt, nS, ldl, tv,
-                       (long long)n_vox, h->min_signal, d_dirs);
+    hipLaunchKernelGGL((k_dti_dirs<YT, MAPS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt, nS, ldl, tv,
+                       (long long)n_vox, h->min_signal, d_dirs, mo.min_diffusivity, mo.evals, mo.scalars);
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, s);
     return AMX_OK;
+}
+
+// amx_dti_directions* + the eigenvalues and the scalar maps.  With neither map output this IS amx_dti_directions*: the same checks,
+// the same kernel, the same launch.
+template <typename YT>
+static int dti_fit_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                       double *d_evals, double *d_scalars, void *hip_stream)
+{
+    if (!d_evals && !d_scalars)
+        return dti_directions_dev<YT, false>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{0.0, nullptr, nullptr});
+    return dti_directions_dev<YT, true>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{min_diffusivity, d_evals, d_scalars});
 }
 
 extern "C" {
 
 int amx_dti_directions_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double *d_dirs, void *hip_stream)
 {
-    return dti_directions_dev<double>(ctx, h, d_y, n_vox, d_dirs, hip_stream);
+    return dti_directions_dev<double, false>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{0.0, nullptr, nullptr});
 }
 
 int amx_dti_directions_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double *d_dirs, void *hip_stream)
 {
-    return dti_directions_dev<float>(ctx, h, d_y, n_vox, d_dirs, hip_stream);
+    return dti_directions_dev<float, false>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{0.0, nullptr, nullptr});
 }
 
 int amx_dti_directions(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double *out_dirs)
@@ -665,6 +705,42 @@ int amx_dti_directions(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t 
     HIPCHK(ctx, hipMemcpyAsync(ctx->hy.p, y, yb, hipMemcpyHostToDevice, nullptr));
     if ((rc = amx_dti_directions_device(ctx, h, (const double *)ctx->hy.p, n_vox, (double *)ctx->hdirs.p, nullptr))) return rc;
     HIPCHK(ctx, hipMemcpyAsync(out_dirs, ctx->hdirs.p, db, hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(ctx, hipStreamSynchronize(nullptr));
+    return AMX_OK;
+}
+
+int amx_dti_fit_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                       double *d_evals, double *d_scalars, void *hip_stream)
+{
+    return dti_fit_dev<double>(ctx, h, d_y, n_vox, min_diffusivity, d_dirs, d_evals, d_scalars, hip_stream);
+}
+
+int amx_dti_fit_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                           double *d_evals, double *d_scalars, void *hip_stream)
+{
+    return dti_fit_dev<float>(ctx, h, d_y, n_vox, min_diffusivity, d_dirs, d_evals, d_scalars, hip_stream);
+}
+
+int amx_dti_fit(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double min_diffusivity, double *out_dirs,
+                double *out_evals, double *out_scalars)
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_directions: not an estimator of this ctx");
+    if (n_vox == 0) return AMX_OK;
+    if (n_vox < 0 || !y || (!out_dirs && !out_evals && !out_scalars)) return amx_bad(ctx, "amx_dti_directions: bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    // one device buffer behind y's: 3 + 3 + 4 doubles per voxel
+    const size_t yb = (size_t)n_vox * h->nS * sizeof(double), vb = (size_t)n_vox * sizeof(double);
+    if ((rc = amx_ensure(ctx, ctx->hy, yb))) return rc;
+    if ((rc = amx_ensure(ctx, ctx->hdirs, 10 * vb))) return rc;
+    double *dd = (double *)ctx->hdirs.p, *de = dd + 3 * n_vox, *ds = dd + 6 * n_vox;
+    HIPCHK(ctx, hipMemcpyAsync(ctx->hy.p, y, yb, hipMemcpyHostToDevice, nullptr));
+    if ((rc = amx_dti_fit_device(ctx, h, (const double *)ctx->hy.p, n_vox, min_diffusivity, out_dirs ? dd : nullptr,
+                                 out_evals ? de : nullptr, out_scalars ? ds : nullptr, nullptr))) return rc;
+    if (out_dirs) HIPCHK(ctx, hipMemcpyAsync(out_dirs, dd, 3 * vb, hipMemcpyDeviceToHost, nullptr));
+    if (out_evals) HIPCHK(ctx, hipMemcpyAsync(out_evals, de, 3 * vb, hipMemcpyDeviceToHost, nullptr));
+    if (out_scalars) HIPCHK(ctx, hipMemcpyAsync(out_scalars, ds, 4 * vb, hipMemcpyDeviceToHost, nullptr));
     HIPCHK(ctx, hipStreamSynchronize(nullptr));
     return AMX_OK;
 }

@@ -98,4 +98,53 @@ __device__ inline void principal_direction(const double d[6], double out[3])
     out[0] = x * inv; out[1] = y * inv; out[2] = z * inv;
 }
 
+// principal_direction, keeping what the Jacobi solve has besides: ev = the three eigenvalues of the tensor itself (the scale `mx`
+// put back), in descending order -- `decompose_tensor`'s evals before its clip; out = principal_direction's axis, bit for bit (the
+// same sweeps and the same selection).  A tensor with a NaN entry leaves three NaN eigenvalues.
+__device__ inline void tensor_eigen(const double d[6], double ev[3], double out[3])
+{
+    double mx = fmax(fmax(fabs(d[0]), fabs(d[1])), fmax(fabs(d[2]), fabs(d[3])));
+    mx = fmax(mx, fmax(fabs(d[4]), fabs(d[5])));
+    const double sc = mx > 1e-290 ? fast_rcp(mx) : 0.0;
+    double a[3][3] = {{d[0] * sc, d[1] * sc, d[3] * sc}, {d[1] * sc, d[2] * sc, d[4] * sc}, {d[3] * sc, d[4] * sc, d[5] * sc}};
+    double v[3][3] = {{1.0, 0.0, 0.0}, {0.0, 1.0, 0.0}, {0.0, 0.0, 1.0}};
+#pragma unroll 1
+    for (int sweep = 0; sweep < 6; sweep++) {
+        jacobi_rotate<0, 1>(a, v);
+        jacobi_rotate<0, 2>(a, v);
+        jacobi_rotate<1, 2>(a, v);
+    }
+    const bool c1 = a[1][1] > a[0][0];
+    double best = c1 ? a[1][1] : a[0][0];
+    double x = c1 ? v[0][1] : v[0][0], y = c1 ? v[1][1] : v[1][0], z = c1 ? v[2][1] : v[2][0];
+    const bool c2 = a[2][2] > best;
+    x = c2 ? v[0][2] : x; y = c2 ? v[1][2] : y; z = c2 ? v[2][2] : z;
+    const double inv = fast_rsqrt(x * x + y * y + z * z);
+    out[0] = x * inv; out[1] = y * inv; out[2] = z * inv;
+    // descending order by a three-element network; a NaN anywhere (mx is not NaN then: fmax drops it) is spread to all three, so
+    // that no comparison decides what such a voxel reports
+    double e0 = a[0][0], e1 = a[1][1], e2 = a[2][2], t;
+    if (e0 < e1) { t = e0; e0 = e1; e1 = t; }
+    if (e1 < e2) { t = e1; e1 = e2; e2 = t; }
+    if (e0 < e1) { t = e0; e0 = e1; e1 = t; }
+    const double poison = (e0 + e1 + e2) * 0.0;     // 0, or NaN for a NaN / Inf entry
+    ev[0] = fma(e0, mx, poison); ev[1] = fma(e1, mx, poison); ev[2] = fma(e2, mx, poison);
+}
+
+// FA, MD, AD, RD of the eigenvalues e[0] >= e[1] >= e[2] (dipy/reconst/dti.py: fractional_anisotropy, mean_diffusivity,
+// axial_diffusivity, radial_diffusivity), after decompose_tensor's clip from below at min_diffusivity, which is applied to e in
+// place.  NaN eigenvalues stay NaN (the clip is a comparison, not fmax) and give NaN scalars.
+__device__ inline void tensor_scalars(double e[3], double min_diffusivity, double s[4])
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) e[k] = e[k] < min_diffusivity ? min_diffusivity : e[k];
+    const double d01 = e[0] - e[1], d12 = e[1] - e[2], d20 = e[2] - e[0];
+    const double num = 0.5 * (d01 * d01 + d12 * d12 + d20 * d20);
+    const double den = e[0] * e[0] + e[1] * e[1] + e[2] * e[2];
+    s[0] = den == 0.0 ? 0.0 : sqrt(num / den);
+    s[1] = (e[0] + e[1] + e[2]) / 3.0;
+    s[2] = e[0];
+    s[3] = 0.5 * (e[1] + e[2]);
+}
+
 }  // namespace amx

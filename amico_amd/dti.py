@@ -11,12 +11,17 @@ and the same with `fit_method` 'WLS' or 'NLLS' (the configuration's DTI_fit_meth
 The one-off part (gradient table, design matrix, pseudo-inverse: a 7 x nS matrix per scheme) is host numpy,
 like the reference; the per-voxel part (log, contraction, 3x3 eigen-decomposition) runs on the GPU through
 `amx_dti_directions*` (include/amico_amd.h).  There is no CPU fallback.
+
+The same fit also gives what a study reports beside the model's maps -- `TensorFit.evals`, `.fa`, `.md`, `.ad`, `.rd` -- through
+`amx_dti_fit*`: `TensorDirections.fit_maps`, and `Evaluation`'s config key `doSaveTensorMaps`.
 """
 import numpy as np
 
 from . import _capi
 
 MIN_POSITIVE_SIGNAL = 1e-4      # dipy.reconst.dti.MIN_POSITIVE_SIGNAL (TensorModel.fit default)
+MIN_DIFFUSIVITY_TOL = 1e-6      # TensorModel.__init__: min_diffusivity = tol / -design_matrix.min()
+SCALAR_NAMES = ('FA', 'MD', 'AD', 'RD')     # the columns of `scalars`
 
 
 def gradient_table(bvals, bvecs, b0_threshold=50.0, atol=1e-2):
@@ -90,6 +95,8 @@ class TensorDirections:
         self.design = design_matrix(self.bvals, self.bvecs)
         self.inv_design = np.linalg.pinv(self.design)
         self.min_signal = MIN_POSITIVE_SIGNAL if min_signal is None else float(min_signal)
+        # TensorModel.__init__: the floor decompose_tensor clips the eigenvalues at (every entry of the design matrix is <= 0)
+        self.min_diffusivity = MIN_DIFFUSIVITY_TOL / -self.design.min()
         self.ctx = ctx if ctx is not None else get_context()
         self._dti = _capi.Dti(self.ctx, self.inv_design, self.min_signal, design=self.design, method=self.fit_method)
 
@@ -112,5 +119,18 @@ class TensorDirections:
         """y [n_vox, nS] -> directions f64[n_vox, 3]."""
         return self._dti.directions(y)
 
-    def fit_device(self, d_y, n_vox, d_dirs, stream=None, f32=False):
-        self._dti.directions_device(d_y, n_vox, d_dirs, stream, f32=f32)
+    def fit_maps(self, y):
+        """y [n_vox, nS] -> {'directions': f64[n_vox, 3], 'evals': f64[n_vox, 3], 'scalars': f64[n_vox, 4]}: the fit of `fit`, its
+        eigenvalues in descending order clipped from below at `min_diffusivity` (dipy's decompose_tensor), and FA, MD, AD, RD
+        (SCALAR_NAMES) of the clipped eigenvalues.  The directions are those of `fit`, bit for bit.  A NaN sample counts as
+        min_signal, as every sample below min_signal does; a +Inf sample leaves NaN eigenvalues and scalars; an all-zero or
+        constant voxel gives three times min_diffusivity and FA = 0 (include/amico_amd.h: amx_dti_fit)."""
+        return self._dti.fit(y, self.min_diffusivity)
+
+    def fit_device(self, d_y, n_vox, d_dirs, stream=None, f32=False, d_evals=None, d_scalars=None):
+        """device pointers; d_evals f64 [n_vox, 3] / d_scalars f64 [n_vox, 4] (either may be None; d_dirs too when one of them is
+        given).  Without them: the direction kernel of always, nothing else is launched."""
+        if d_evals is None and d_scalars is None:
+            self._dti.directions_device(d_y, n_vox, d_dirs, stream, f32=f32)
+        else:
+            self._dti.fit_device(d_y, n_vox, self.min_diffusivity, d_dirs, d_evals, d_scalars, stream, f32=f32)

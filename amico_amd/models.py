@@ -675,8 +675,10 @@ class FreeWater(BaseModel):
         # device-resident signals: doSaveCorrectedDWI asks the fit for the isotropic coefficients only (AMX_F_FW_ISO: the fit stays on its
         # fast kernel and reads the float32 signals in place); Evaluation.fit makes the corrected volume from them on the GPU, and the rows
         # results['y_corrected'] (models.pyx:1264-1274) are made by the same kernel if somebody reads them
+        # (doSaveTensorMaps refits the tensor on the corrected rows, so it asks for the same coefficients)
+        iso = want['corrected'] or bool(evaluation.get_config('doSaveTensorMaps'))
         return self._run(evaluation, _capi.FIT['freewater'], lambda c: _capi.upload_freewater(c, evaluation.KERNELS, evaluation.htable),
-                         (self.type == 'Mouse',), want, dict(rmse=want['rmse'], nrmse=want['nrmse'], iso=want['corrected']), self._lazy_corrected)
+                         (self.type == 'Mouse',), want, dict(rmse=want['rmse'], nrmse=want['nrmse'], iso=iso), self._lazy_corrected)
 
     @staticmethod
     def _lazy_corrected(ctx, lut, dev, out, results):

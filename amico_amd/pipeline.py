@@ -11,6 +11,10 @@
     amx_prep_scatter_device     maps / directions into float32 volumes                             core.py:472-498
     amx_prep_corrected_device   FreeWater: the corrected DWI volume (optional: corrected)          models.pyx:1264-1274, core.py:488-498
 
+tensor_maps=True (Evaluation's doSaveTensorMaps) replaces the fused kernel by amx_prep_gather_device + amx_dti_fit_device_f32, which also
+leaves the tensor's eigenvalues and FA, MD, AD, RD; they are scattered into `dti_evals` / `dti_maps`.  FreeWater then makes the
+corrected rows in HBM (amx_freewater_corrected_device) and fits the tensor again on them -> `dti_maps_corrected` / `dti_evals_corrected`.
+
 Everything is enqueued on one HIP stream; the only host synchronisation is `amx_sync_status` at the end.  torch is
 used for device buffers only.  `amico_amd.core.Evaluation` is the host-array (numpy in / numpy out) face of the
 same chain.
@@ -26,8 +30,11 @@ class _VolumePipeline:
     (scan, debias, gather + directions, scan of y) and run()"""
 
     def _setup(self, scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels,
-               raw_dtype=None, scaling=None):
+               raw_dtype=None, scaling=None, tensor_maps=False):
         import torch
+        # tensor_maps: the tensor pass also writes its eigenvalues and FA, MD, AD, RD (amx_dti_fit_device_f32).  The fused gather has no
+        # such variant, so the chain is gather -> tensor pass whatever `fused` says: the OLS fit no longer rides on the gather
+        self.tensor_maps = bool(tensor_maps)
         # raw_dtype: run() is given the image in that stored dtype (the plan's geometry and element strides) and starts with the ingest
         # kernel, which makes the float32 image `self.img` and does the scan of the image in the same pass; a scaling alone means float32
         self.scaling = _prep.check_scaling(scaling)
@@ -66,6 +73,11 @@ class _VolumePipeline:
         self.mean_b0 = torch.empty(n, dtype=torch.float32, device=self.dev)
         self.maps = torch.empty(self.shape + (n_maps,), dtype=torch.float32, device=self.dev)
         self.dirs_vol = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
+        self.dti_maps = self.dti_evals = None
+        if self.tensor_maps:
+            self._evals, self._scalars = torch.empty((n, 3), **f64), torch.empty((n, 4), **f64)
+            self.dti_evals = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
+            self.dti_maps = torch.empty(self.shape + (4,), dtype=torch.float32, device=self.dev)      # FA, MD, AD, RD
 
     def _enqueue_signals(self, d_img, stream):
         """image -> y, mean_b0, dirs (everything ahead of the model fit)"""
@@ -79,6 +91,13 @@ class _VolumePipeline:
             p.sanitize_device(d_img.data_ptr(), r, stream)
         if self.prep.debias_snr is not None:
             p.debias_device(d_img.data_ptr(), self.prep.debias_snr, stream)
+        if self.tensor_maps:
+            p.gather_device(d_img.data_ptr(), self.y.data_ptr(), self.mean_b0.data_ptr(), self.prep.do_normalize, 0.0, stream)
+            if r is not None:
+                _capi.sanitize_device(c, self.y.data_ptr(), self.y.numel(), r, stream)
+            self.tensor.fit_device(self.y.data_ptr(), self.n_vox, self.dirs.data_ptr(), stream, f32=True,
+                                   d_evals=self._evals.data_ptr(), d_scalars=self._scalars.data_ptr())
+            return
         if self.fused:
             # one pass over the image: the tensor fit rides on the gather's LDS tile
             p.gather_directions_device(self.tensor._dti, d_img.data_ptr(), self.y.data_ptr(), self.mean_b0.data_ptr(), self.dirs.data_ptr(),
@@ -95,6 +114,9 @@ class _VolumePipeline:
         p = self.prep._plan
         p.scatter_device(self.est.data_ptr(), self.est.shape[1], self.maps.data_ptr(), stream)
         p.scatter_device(self.dirs.data_ptr(), 3, self.dirs_vol.data_ptr(), stream)
+        if self.tensor_maps:
+            p.scatter_device(self._evals.data_ptr(), 3, self.dti_evals.data_ptr(), stream)
+            p.scatter_device(self._scalars.data_ptr(), 4, self.dti_maps.data_ptr(), stream)
 
     def run(self, d_img, stream=None):
         self.enqueue(d_img, stream)
@@ -109,8 +131,11 @@ class _VolumePipeline:
 
 class NoddiVolumePipeline(_VolumePipeline):
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.5, lambda2=1e-3, do_normalize=True,
-                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None, raw_dtype=None, scaling=None):
-        """raw_dtype / scaling: run() takes the image as it is stored (uint8, int16, uint16, int32, float32 or float64 elements in the
+                 b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None, raw_dtype=None, scaling=None,
+                 tensor_maps=False):
+        """tensor_maps=True: run() also leaves `dti_maps` [X, Y, Z, 4] (FA, MD, AD, RD) and `dti_evals` [X, Y, Z, 3] of the tensor fit
+        in HBM (float32, zero outside the mask); the chain is then gather -> tensor pass, as with fused=False.
+        raw_dtype / scaling: run() takes the image as it is stored (uint8, int16, uint16, int32, float32 or float64 elements in the
         layout of `img_like`, which must be C or Fortran ordered) plus the NIfTI header's (slope, inter); the chain then starts with the
         kernel that makes the float32 image in HBM (amx_prep_ingest_device) and counts its NaN / Inf samples into `bad_samples`.
         replace_bad_voxels: None leaves the chain as it is (no scan; a NaN in the image is the caller's).  A finite number enqueues
@@ -118,7 +143,8 @@ class NoddiVolumePipeline(_VolumePipeline):
         the same stream and without a host wait; run() then leaves the two counts in `bad_samples` (image) and
         `bad_samples_preprocessed` (y).  With fused=True the gather computes the directions in the same kernel as y, so the
         directions of a voxel whose y is replaced afterwards come from the unreplaced values (fused=False fits them from the replaced y)."""
-        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling)
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling,
+                    tensor_maps)
         self.lut = _capi.upload_noddi(self.ctx, kernels, htable, scheme.dwi_idx)
         self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
         self.shape = tuple(img_like.shape[:3])
@@ -138,12 +164,15 @@ class NoddiVolumePipeline(_VolumePipeline):
 class FreeWaterVolumePipeline(_VolumePipeline):
     def __init__(self, scheme, img_like, mask, kernels, htable, lambda1=0.0, lambda2=1e-3, do_normalize=True,
                  b0_min_signal=0.0, device=None, fused=True, debias_snr=None, replace_bad_voxels=None,
-                 corrected=False, keep_b0=False, is_mouse=False, raw_dtype=None, scaling=None):
+                 corrected=False, keep_b0=False, is_mouse=False, raw_dtype=None, scaling=None, tensor_maps=False):
         """The chain of NoddiVolumePipeline (same arguments, same meaning) with the Free-Water fit: leaves `maps` [X, Y, Z, 2 | 4 (Mouse)]
         and `dirs_vol` in HBM.  corrected=True (doSaveCorrectedDWI): also `corrected` [X, Y, Z, nS], the free-water-corrected DWI of
         core.py:488-498 -- rescaled by the b0 mean when do_normalize is set; keep_b0=True (doKeepb0Intact) leaves its b0 volumes
-        as they were.  The fit stays on its fast kernel: it hands over the isotropic coefficients only (AMX_F_FW_ISO)."""
-        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling)
+        as they were.  The fit stays on its fast kernel: it hands over the isotropic coefficients only (AMX_F_FW_ISO).
+        tensor_maps=True: as for NoddiVolumePipeline, and `dti_maps_corrected` / `dti_evals_corrected`: the same tensor fit on the
+        corrected rows, which are made in HBM from the same isotropic coefficients (`corrected` need not be set)."""
+        self._setup(scheme, img_like, mask, do_normalize, b0_min_signal, device, fused, debias_snr, replace_bad_voxels, raw_dtype, scaling,
+                    tensor_maps)
         self.lut = _capi.upload_freewater(self.ctx, kernels, htable)
         self.lambda1, self.lambda2 = float(lambda1), float(lambda2)
         self.is_mouse = bool(is_mouse)
@@ -152,17 +181,31 @@ class FreeWaterVolumePipeline(_VolumePipeline):
         torch = self.torch
         self.want_corrected = bool(corrected)
         self.b0_cols = np.asarray(scheme.b0_idx, dtype=np.int32) if (keep_b0 and scheme.b0_count > 0) else np.zeros(0, dtype=np.int32)
-        self.x_iso = self.corrected = None
-        if self.want_corrected:
+        self.x_iso = self.corrected = self.dti_maps_corrected = self.dti_evals_corrected = None
+        if self.want_corrected or self.tensor_maps:
             self.x_iso = torch.empty((self.n_vox, self.lut.n_iso), dtype=torch.float64, device=self.dev)
+        if self.want_corrected:
             self.corrected = torch.empty(self.shape + (scheme.nS,), dtype=torch.float32, device=self.dev)
+        if self.tensor_maps:
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            self._evals_c, self._scalars_c = torch.empty((self.n_vox, 3), **f64), torch.empty((self.n_vox, 4), **f64)
+            self._y_c = torch.empty((self.n_vox, scheme.nS), **f64)             # the corrected rows: they stay in HBM
+            self.dti_evals_corrected = torch.empty(self.shape + (3,), dtype=torch.float32, device=self.dev)
+            self.dti_maps_corrected = torch.empty(self.shape + (4,), dtype=torch.float32, device=self.dev)
 
     def enqueue(self, d_img, stream=None):
         """d_img: as for NoddiVolumePipeline.enqueue"""
         self._enqueue_signals(d_img, stream)
         _capi._fit_device(_capi.FIT['freewater'], self.ctx, self.lut, self.y, self.dirs, self.lambda1, self.lambda2, (int(self.is_mouse),), {},
-                          stream, False, self.x_iso if self.want_corrected else False, into=self.est)
+                          stream, False, self.x_iso if self.x_iso is not None else False, into=self.est)
         self._enqueue_scatter(stream)
         if self.want_corrected:
             rescale = self.prep.do_normalize and self.scheme.b0_count > 0
             self.prep._plan.corrected_device(self.lut, self.y, self.x_iso, self.corrected, self.mean_b0 if rescale else None, self.b0_cols, stream)
+        if self.tensor_maps:
+            p = self.prep._plan
+            _capi.freewater_corrected_device(self.ctx, self.lut, self.y, self.x_iso, stream, into=self._y_c)
+            self.tensor.fit_device(self._y_c.data_ptr(), self.n_vox, None, stream, d_evals=self._evals_c.data_ptr(),
+                                   d_scalars=self._scalars_c.data_ptr())
+            p.scatter_device(self._evals_c.data_ptr(), 3, self.dti_evals_corrected.data_ptr(), stream)
+            p.scatter_device(self._scalars_c.data_ptr(), 4, self.dti_maps_corrected.data_ptr(), stream)

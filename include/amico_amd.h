@@ -352,6 +352,26 @@ int amx_dti_directions(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t 
 int amx_dti_directions_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double *d_dirs, void *hip_stream);
 int amx_dti_directions_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox,
                               double *d_dirs, void *hip_stream);
+/* The same fit, keeping what its eigen-decomposition has besides the principal axis (TensorFit.evals / .fa / .md / .ad / .rd of
+ * the reference's TensorModel; not part of the reference's own call, which reads .directions only):
+ *   evals   f64[n_vox][3]  eigenvalues of D in descending order, then clipped from below at min_diffusivity -- dipy's
+ *                          decompose_tensor as TensorModel calls it, min_diffusivity = 1e-6 / -min(design matrix)
+ *   scalars f64[n_vox][4]  of the clipped e1 >= e2 >= e3:  FA = sqrt(1/2 ((e1-e2)^2 + (e2-e3)^2 + (e3-e1)^2) / (e1^2 + e2^2 + e3^2))
+ *                          (0 where the denominator is 0), MD = (e1 + e2 + e3) / 3, AD = e1, RD = (e2 + e3) / 2
+ * min_diffusivity >= 0.  Any of dirs / evals / scalars may be NULL (the host call needs one of them).  With evals and scalars
+ * both NULL the call IS amx_dti_directions*: the same checks (dirs must not be NULL then), the same kernel and launch.  With
+ * either present a kernel variant runs that computes the same directions, bit for bit.  Limits, error strings (they keep the
+ * amx_dti_directions prefix) and the NLLS counters are amx_dti_directions*'s.
+ * Samples that are not numbers: a NaN (and -Inf, and any sample below min_signal) counts as min_signal, as it does for the
+ * direction -- max(y, min_signal) is taken with fmax -- so the voxel's outputs are finite.  A +Inf sample makes the tensor NaN:
+ * evals and scalars are NaN for that voxel (the clip does not hide it); its direction is what amx_dti_directions* writes.  An
+ * all-zero or constant voxel has D = 0 to rounding: evals = min_diffusivity three times, FA = 0, MD = AD = RD = min_diffusivity. */
+int amx_dti_fit(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double min_diffusivity, double *out_dirs,
+                double *out_evals, double *out_scalars);
+int amx_dti_fit_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                           double *d_evals, double *d_scalars, void *hip_stream);
+int amx_dti_fit_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                       double *d_evals, double *d_scalars, void *hip_stream);
 
 /* (f2, f3) signal preparation and result scatter, fused around the masked voxel list:
  *   core.py:209-223  mean_b0s = mean(img[..., b0_idx], axis=3); norm_factor = 1 / mean_b0s, 0 where
