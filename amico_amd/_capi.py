@@ -516,8 +516,19 @@ def czb_fit(ctx, lut, y, dirs, lambda1, lambda2, rmse=False, nrmse=False, out=No
 
 # ---- the same four fits on DEVICE-resident inputs (torch tensors used as plain device buffers); outputs are torch
 #      tensors on the same device, enqueued on `stream`; the caller synchronises with ctx.sync(stream)
+# `which` of amx_debug_fetch (include/amico_amd.h holds each table's layout and shape)
+DEBUG_WHICH = dict(
+    perm=0, ytil=1, seeds=2, ytil2=3, seeds2=4, cgemm=5, schunks=6, misc=7,                      # workspace of the last fit (lut = None)
+    basis_U=10, basis_S=11, basis2_U=12, basis2_S=13, tiles=14, gram=15, gram_dwi=16,            # made at the upload
+    screen_S=17, screen2_S=18, screen_kappa=19, screen_kappa0=20, screen2_kappa=21, screen2_kappa0=22,
+    u2iso=23, rowdwi=24, colscale=25, s2_derive=26,
+    fw_prep=30, czb_prep=31, sandi_prep=32, sandi_long_prep=33,                                  # made by the first fit at a lambda2
+    dict_gram=40)                                                                                # `lut` is a Dict
+
+
 def debug_fetch(ctx, lut, which, shape, dtype):
-    """workspace / dictionary tables of the support seeds (include/amico_amd.h: amx_debug_fetch) as a numpy array"""
+    """workspace / dictionary tables (include/amico_amd.h: amx_debug_fetch; which: a code or a name of DEBUG_WHICH) as a numpy array"""
+    which = DEBUG_WHICH.get(which, which)
     out = np.empty(shape, dtype=dtype)
     ctx.check(lib().amx_debug_fetch(ctx._h, lut._h if lut is not None else None, int(which), out.ctypes.data_as(c_vp), out.nbytes))
     return out

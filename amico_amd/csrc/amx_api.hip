@@ -217,31 +217,81 @@ int amx_set_progress(amx_ctx *ctx, void (*callback)(int64_t done, int64_t total,
     return AMX_OK;
 }
 
-// diagnosis / tests: copy a workspace buffer of the LAST fit (0 perm int32[n], 1 y~ f64[n][12], 2 seeds u64[n]) or a
-// dictionary table (10 basis U f64[ndirs][nS][12], 11 compressed dictionary S f64[ndirs][n_atoms][12]) to the host
+// diagnosis / tests: copy a workspace buffer of the LAST fit (which 0 .. 7), a table of the dictionary `lut` (10 .. 33) or the Gram
+// tables of a dense amx_dict (40, the handle in lut's place) to the host.  The codes, their layouts and shapes: include/amico_amd.h.
+// Every copy is checked against the table's own size; a table that was never built or belongs to another model is refused.
 int amx_debug_fetch(amx_ctx *ctx, const amx_lut *lut, int which, void *dst, size_t bytes)
 {
     if (!ctx || !dst) return AMX_E_BADARG;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipDeviceSynchronize());
     const void *src = nullptr;
-    switch (which) {
-    case 0: src = ctx->perm.p; break;
-    case 1: src = ctx->ytil.p; break;
-    case 2: src = ctx->seeds.p; break;
-    case 3: src = ctx->ytil2.p; break;
-    case 4: src = ctx->seeds2.p; break;
-    case 5: src = ctx->cgemm.p; break;
-    case 6: src = ctx->schunks.p; break;
-    case 7: src = ctx->misc.p; break;
-    case 10: src = lut ? lut->basis_U : nullptr; break;
-    case 11: src = lut ? lut->basis_S : nullptr; break;
-    case 12: src = lut ? lut->basis2_U : nullptr; break;
-    case 13: src = lut ? lut->basis2_S : nullptr; break;
-    default: break;
+    size_t have = 0;
+    bool host = false;                 // (a value kept in the handle itself)
+    int s2d = 0;
+    if (which >= 0 && which <= 7) {
+        const DevBuf *b = nullptr;
+        switch (which) {
+        case 0: b = &ctx->perm; break;
+        case 1: b = &ctx->ytil; break;
+        case 2: b = &ctx->seeds; break;
+        case 3: b = &ctx->ytil2; break;
+        case 4: b = &ctx->seeds2; break;
+        case 5: b = &ctx->cgemm; break;
+        case 6: b = &ctx->schunks; break;
+        default: b = &ctx->misc; break;
+        }
+        src = b->p; have = b->cap;
+        if (!src) return amx_bad(ctx, "amx_debug_fetch: no fit on this context has made that workspace buffer");
+    } else if (which == 40) {
+        const amx_dict *dict = reinterpret_cast<const amx_dict *>(lut);
+        if (!dict || dict->model != kDictModel) return amx_bad(ctx, "amx_debug_fetch: which = 40 reads an amx_dict handle");
+        if (dict->ctx != ctx) return amx_bad(ctx, "amx_debug_fetch: the dictionary belongs to another context");
+        if (!dict->dense || !dict->gram) return amx_bad(ctx, "amx_debug_fetch: the dictionary is not dense (amx_dict_set_dense): it has no Gram tables");
+        src = dict->gram; have = (size_t)dict->n_dicts * dict->n * dict->ldG * sizeof(double);
+    } else if (which >= 10 && which <= 33) {
+        if (!lut) return amx_bad(ctx, "amx_debug_fetch: this table needs a dictionary handle");
+        if (lut->model < 1 || lut->model > 4) return amx_bad(ctx, "amx_debug_fetch: not an amx_lut handle");
+        if (lut->ctx != ctx) return amx_bad(ctx, "amx_debug_fetch: the dictionary belongs to another context");
+        const bool noddi = lut->model == 1;
+        const size_t nd = (size_t)lut->ndirs, f64 = sizeof(double);
+        int want_model = 1;            // 0: any
+        switch (which) {
+        case 10: src = lut->basis_U; have = nd * lut->nS * kSeedKD * f64; break;
+        case 11: src = lut->basis_S; have = nd * lut->n_atoms * kSeedKD * f64; break;
+        case 12: src = lut->basis2_U; have = nd * lut->nS * kSeedKD * f64; break;
+        case 13: src = lut->basis2_S; have = nd * lut->n_wm * kSeedKD * f64; break;
+        case 14: want_model = 0; src = lut->tiles; have = nd * lut->tile_stride * (lut->model == 3 ? f64 : sizeof(float)); break;
+        case 15: want_model = 0; src = lut->gram; have = nd * lut->n_atoms * lut->ldG * f64; break;
+        case 16: src = lut->gram_dwi; have = nd * lut->n_atoms * lut->ldG * f64; break;
+        case 17: src = lut->screen_S; have = nd * kSeedKD * kScreenLd * sizeof(float); break;
+        case 18: src = lut->screen2_S; have = nd * kSeedKD * kScreenLd * sizeof(float); break;
+        case 19: src = lut->screen_kappa; have = nd * f64; break;
+        case 20: src = lut->screen_kappa0; have = nd * f64; break;
+        case 21: src = lut->screen2_kappa; have = nd * f64; break;
+        case 22: src = lut->screen2_kappa0; have = nd * f64; break;
+        case 23: src = lut->u2iso; have = nd * kSeedKD * f64; break;
+        case 24: src = lut->rowdwi; have = (size_t)lut->nS; break;
+        case 25: src = lut->colscale; have = (size_t)lut->n_atoms * f64; break;
+        case 26: host = true; s2d = lut->s2_derive; src = &s2d; have = sizeof(int); break;
+        case 30: want_model = 2; src = lut->fw_prep; have = src ? nd * amx_fw_table_words(lut) * f64 : 0; break;
+        case 31: want_model = 4; src = lut->czb_prep; have = nd * amx_czb_table_stride(lut->nS) * f64; break;
+        case 32: want_model = 3; src = lut->sandi_prep; have = amx_sandi_table_words() * f64; break;
+        case 33: want_model = 3; src = lut->sandi_long_prep; have = amx_sandi_long_table_words(lut) * f64; break;
+        default: return amx_bad(ctx, "amx_debug_fetch: no such table");
+        }
+        if (want_model && lut->model != want_model) return amx_bad(ctx, "amx_debug_fetch: the dictionary's model has no such table");
+        if (!src) return amx_bad(ctx, (which >= 30) ? "amx_debug_fetch: no fit has built that table yet (it is made for one lambda2 by the first fit that reads it)"
+                                      : (noddi && which != 15 && which != 14) ? "amx_debug_fetch: the dictionary has no such table (no seeds for more than 160 atoms)"
+                                                                               : "amx_debug_fetch: the dictionary has no such table");
+    } else return amx_bad(ctx, "amx_debug_fetch: no such buffer");
+    if (bytes > have) {
+        char b[160];
+        snprintf(b, sizeof b, "amx_debug_fetch: %zu bytes asked of a table of %zu (which = %d)", bytes, have, which);
+        return amx_bad(ctx, b);
     }
-    if (!src) return amx_bad(ctx, "amx_debug_fetch: no such buffer");
-    HIPCHK(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+    if (host) memcpy(dst, src, bytes);
+    else HIPCHK(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
     return AMX_OK;
 }
 

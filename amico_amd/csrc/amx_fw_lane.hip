@@ -1129,6 +1129,9 @@ static int fw_prepare_n(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t
     return AMX_OK;
 }
 
+// doubles per orientation of the cached tables (amx_debug_fetch)
+size_t amx_fw_table_words(const amx_lut *lut) { return lut->fw_N == 11 ? (size_t)fw_prep_words<11>(lut->nS) : (size_t)fw_prep_words<12>(lut->nS); }
+
 int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t s)
 {
     return lut->n_atoms <= 11 ? fw_prepare_n<11>(ctx, lut, a, s) : fw_prepare_n<12>(ctx, lut, a, s);

@@ -216,6 +216,8 @@ inline constexpr amx_switch kSwitches[] = {
 constexpr long long kLeftSmall1 = 150000, kLeftSmall3 = 600000;
 constexpr long long kRescueFrom = 2000000;   // voxels from which the NNLS certificates run their rescue pass (amx_launch_noddi_gcert; AMX_RESCUE_FROM)
 
+constexpr int kDictModel = 100;   // amx_dict::model
+
 struct amx_lut {
     amx_ctx *ctx = nullptr;
     int model = 0;                 // 1 NODDI, 2 FreeWater, 3 SANDI, 4 CylinderZeppelinBall
@@ -263,6 +265,7 @@ struct amx_lut {
 // dictionaries of the batched solver entry points (amx_nnls_batched / amx_lasso_batched)
 struct amx_dict {
     amx_ctx *ctx = nullptr;
+    int model = kDictModel;        // where amx_lut holds its model: amx_debug_fetch tells the two kinds of handle apart by it
     int m = 0, n = 0, ldA = 0, tile_stride = 0, n_dicts = 0;
     double *tiles = nullptr;       // device f64 [n_dicts][m][ldA] (row-major, odd leading dimension)
     // amx_dict_set_dense: the Gram matrices G_d = A_d'A_d, device f64 [n_dicts][n][ldG]; voxels whose support outgrows the 48-atom re-run
@@ -426,6 +429,11 @@ int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::FwArgs &a, 
 int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s);
 int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s);
 int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
+// doubles of the per-lambda2 tables cached in a dictionary handle (per orientation where the model has orientations): amx_debug_fetch
+size_t amx_czb_table_stride(int nS);
+size_t amx_fw_table_words(const amx_lut *lut);
+size_t amx_sandi_table_words();
+size_t amx_sandi_long_table_words(const amx_lut *lut);
 int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
 // lane-per-voxel variants for dictionaries of <= 16 atoms (amx_fw_lane.hip, amx_sandi_lane.hip)
 int amx_launch_fw_small(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);

@@ -347,6 +347,8 @@ __global__ void __launch_bounds__(256, kRowsOcc) k_sandi_rows(const SandiArgs a)
 
 }  // namespace
 
+size_t amx_sandi_table_words() { return (size_t)kSandiTableWords; }      // (amx_debug_fetch)
+
 // tables of the row-space solver, cached in the dictionary handle for one (lambda1, lambda2)
 int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, SandiArgs &a, hipStream_t s)
 {

@@ -366,13 +366,20 @@ void launch_gram_lane(const SandiLongArgs &f, hipStream_t s) { hipLaunchKernelGG
 
 }  // namespace
 
+// doubles of the cached tables (amx_debug_fetch)
+size_t amx_sandi_long_table_words(const amx_lut *lut)
+{
+    const int NP = sl_padded_atoms(lut->n_atoms), KS = sl_ksteps(lut->nS);
+    return (size_t)2 * NP * NP + (size_t)(NP / 16) * KS * 64;
+}
+
 // G, H and the operand A' of one dictionary and one lambda2, cached in the dictionary handle
 int amx_sandi_long_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s)
 {
     const int NP = sl_padded_atoms(lut->n_atoms), KS = sl_ksteps(lut->nS);
     if (lut->sandi_long_lam2 != lam2 || !lut->sandi_long_prep) {
         if (lut->sandi_long_prep) HIPCHK(ctx, hipDeviceSynchronize());                          // (a fit with the old tables may still run)
-        if (!lut->sandi_long_prep) HIPCHK(ctx, hipMalloc((void **)&lut->sandi_long_prep, ((size_t)2 * NP * NP + (size_t)(NP / 16) * KS * 64) * sizeof(double)));
+        if (!lut->sandi_long_prep) HIPCHK(ctx, hipMalloc((void **)&lut->sandi_long_prep, amx_sandi_long_table_words(lut) * sizeof(double)));
         if (!lut->sandi_long_ready) HIPCHK(ctx, hipEventCreateWithFlags(&lut->sandi_long_ready, hipEventDisableTiming));
         hipLaunchKernelGGL(k_sandi_long_tables, dim3(16), dim3(256), 0, s, reinterpret_cast<const double *>(lut->tiles), lut->nS, lut->ldA, lut->n_atoms,
                            lam2, NP, KS, lut->sandi_long_prep);

@@ -128,6 +128,8 @@ __global__ void __launch_bounds__(256) k_build_basis(const float *__restrict__ t
         R[e] = v;
     }
     __syncthreads();
+    const double dead_rel = 64.0 * nS * 0x1p-52, dead = dead_rel * dead_rel;      // squared pivot norm, relative, at rounding level
+    double nn0 = 0.0;                                                             // squared norm of the largest original column
     for (int d = 0; d < KD; d++) {
         double nr = -1.0;
         if (tid < n_cols) { nr = 0.0; for (int i = 0; i < nS; i++) { const double v = R[i * ldA + tid]; nr += v * v; } }
@@ -140,7 +142,12 @@ __global__ void __launch_bounds__(256) k_build_basis(const float *__restrict__ t
         }
         __syncthreads();
         const double nn = s_n;
-        const bool live = nn > 1e-280;
+        if (d == 0) nn0 = nn;
+        // A dictionary of rank < KD (a small grid of atoms, a protocol of fewer than KD volumes) runs out of directions: what is left of
+        // the columns then is the rounding noise of the deflation, ~1e-16 of the largest column, and normalising it gives a vector that two
+        // passes no longer make orthogonal to the others.  Such a direction is DEAD (all zero), and so is every one after it; what the
+        // columns keep stays in R and so in kappa0.  (A full-rank dictionary's smallest pivot is ~1e-15 of nn0: nothing changes for it.)
+        const bool live = nn > 1e-280 && nn > dead * nn0;
         for (int i = tid; i < nS; i += nt) Q[d * nS + i] = live ? R[i * ldA + s_j] / sqrt(nn) : 0.0;
         __syncthreads();
         // re-orthogonalise against the previous directions, twice, and renormalise

@@ -263,7 +263,30 @@ int amx_predict_device(amx_ctx *ctx, const amx_lut *lut, const double *d_x, int6
  * all ones = no seed), 3: projected clipped signals of the LASSO stage f64[n][12], 4: LASSO passive-set seeds uint64[n][4]
  * (bit j = atom j; word 3 all ones = no seed) -- or a table of the dictionary `lut` -- 10: orientation bases U
  * f64[ndirs][nS][12], 11: compressed dictionaries S = U'A f64[ndirs][n_atoms][12], 12 / 13: the same for the LASSO stage's
- * dictionary, f64[ndirs][nS][12] / f64[ndirs][n_wm][12] (the seed solver reads the first 8 components) -- into the HOST buffer dst (synchronises the device).              */
+ * dictionary, f64[ndirs][nS][12] / f64[ndirs][n_wm][12] (the seed solver reads the first 8 components) -- into the HOST buffer dst (synchronises the device).
+ * Further tables of `lut` (ldA = n_atoms rounded up to odd, tile_stride = nS * ldA rounded up to a multiple of 4):
+ *   made at the upload
+ *   14  tiles           f32 [ndirs][tile_stride] (SANDI: f64 [tile_stride]): tile[i * ldA + j] = atom j at volume i, padding 0.  Atoms of
+ *                       NODDI: wm, (the dot, ex vivo), iso; FreeWater: D, CSF; CylinderZeppelinBall: wmr, wmh, iso
+ *   15  gram            f64 [ndirs][n_atoms][ldG] = A'A, padding 0.  ldG: NODDI 192 (256 above 192 atoms), CylinderZeppelinBall 64,
+ *                       any model of more than 64 atoms (n_atoms + 3) & ~3; the other dictionaries have none
+ *   16  gram_dwi        the same over the stage-2 rows only (NODDI)
+ *   17 / 18  screen_S / screen2_S    f32 [ndirs][12][192]: [d][j] = (float)S[j][d] of table 11 / 13, padding 0 (NODDI)
+ *   19 / 20  screen_kappa / screen_kappa0,  21 / 22  screen2_kappa / screen2_kappa0    f64 [ndirs]: kappa0 = max_j ||a_j - U U'a_j||,
+ *                       kappa = kappa0 + 2e-6 max_j ||a_j|| (stage 2: DWI rows, atoms times colscale)
+ *   23  u2iso           f64 [ndirs][12] = U2'iso
+ *   24  rowdwi          u8 [nS]: 1 = a row of stage 2;  25  colscale  f64 [n_atoms];  26  s2_derive  int32 [1]
+ *   made by the first fit that reads them, for one lambda2 (refused until then)
+ *   30  FreeWater       f64 [ndirs][W], N = 11 (n_atoms <= 11) or 12, NP = 12: A [nS][NP] | H^-1 [N][NP] | H [N][N], W = the sum rounded up to
+ *                       even (that word is not written); padding atoms: 0 in A, identity in H
+ *   31  CylinderZeppelinBall   f64 [ndirs][2 * 32 * 33 + 32 + 2 * 32 * nSp], nSp = 100 (nS <= 100) or 160: M [32][33] | H [32][33] | M 1 [32] |
+ *                       B = M A' [32][nSp] | A' [32][nSp], all 0 outside the dictionary
+ *   32  SANDI 6 x 15    f64 [15 * 22 + 15 * 6 + 16 + 8 * 16]: T [15][22] | G [15][6] | g0 [16] | A [6][16] | 32 unused words
+ *   33  SANDI, more than 128 volumes   f64 [2 NP^2 + (NP / 16) KS 64], NP = n_atoms rounded up to 16, KS = 4 ceil(nS / 16): G [NP][NP] |
+ *                       H [NP][NP] (identity on the padding) | A' in MFMA operand order: [(mt KS + s) 64 + l] = A[16 (s / 4) + 4 (l / 16) + s % 4][16 mt + l % 16]
+ *   40  the Gram tables of a dense amx_dict, whose handle is passed in lut's place: f64 [n_dicts][n][ldG], ldG = n rounded up to odd, padding 0
+ * AMX_E_BADARG with a message, and nothing copied: bytes larger than the table, a table that was never built, a handle of another model
+ * or of another context.                                                                                                              */
 int amx_debug_fetch(amx_ctx *ctx, const amx_lut *lut, int which, void *dst, size_t bytes);
 
 /* ---- the solvers themselves, batched.  What the reference's FFI binds for this path is (models.pyx:18)
