@@ -337,6 +337,11 @@ struct ScanSlots {
         const int lo = __builtin_amdgcn_ds_bpermute(slot << 2, __double2loint(v)), hi = __builtin_amdgcn_ds_bpermute(slot << 2, __double2hiint(v));
         return __hiloint2double(hi, lo);
     }
+    __device__ __forceinline__ unsigned long long fetch(unsigned long long v) const
+    {
+        const unsigned lo = (unsigned)__builtin_amdgcn_ds_bpermute(slot << 2, (int)(unsigned)v), hi = (unsigned)__builtin_amdgcn_ds_bpermute(slot << 2, (int)(unsigned)(v >> 32));
+        return ((unsigned long long)hi << 32) | lo;
+    }
 };
 
 // the scan over the first GN voxel groups; returns to lane l the tagged maximum of column l (lanes of the groups >= GN: -inf)
@@ -2417,7 +2422,7 @@ struct Seed2Args {
     double lam1, lam2;
     int *gcount;                  // [max_schunks + 1]: see SeedArgs
     int n_gcount;
-    int *stats;
+    int *stats;                   // optional counters (AMX_STATS): [0] trips, [1] lane-trips in use, [22 .. 26] kcycles of taking voxels, scan, leave test, changes, factor + solve
     double *trace;                // unused (a retired per-trip trace); kept so that the kernel argument layout stays as it is
     int trip_cap;                 // see SeedArgs
     int max_atoms;                // a voxel whose passive set reaches this many atoms and wants more is given up (its set goes on as an incomplete seed)
@@ -2485,11 +2490,50 @@ __global__ void __launch_bounds__(1024) k_noddi_project2(const Seed2Args a)
 // the even and one for the odd tiles: one v_max_f64 per element, where the best and the runner-up of the class take three (5.74
 // against 5.67 trips per voxel in tools/lab/s2_block_lab.py) -- as tagged values, in no particular order (lanes of the groups
 // >= GN: -inf).
+// The scan also says which PASSIVE atoms leave (lam1: the LASSO operand is not normalised, so s_j'r - lambda1 of a passive atom is
+// its t_j = lambda2 x_j): leave[0 .. 2], to lane l for column l, holds the passive atoms with !(t_j > 0) in the layout of P (zero in
+// the lanes of the groups >= GN).  A lane's element (mt, rr) is bit 16 mt + 4 rr of the row-shifted mask -- every fourth bit of three
+// words -- so ONE 64-bit word per lane and group takes all its verdicts (LeavePack): a compare, a select and an and-or per element,
+// beside the matrix pipe, where a loop over the set bits of P computed every t_j a second time.
+struct LeavePack {
+    // bit of the element (mt, rr) in the lane's word: word k of the row-shifted mask moved up by k
+    static constexpr int pos(int mt, int rr) { return ((16 * mt + 4 * rr) & 63) + ((16 * mt + 4 * rr) >> 6); }
+    // ... and back: the atom that bit p of row q's word stands for (unpacked: word p & 3, bit (p & ~3) + q)
+    static constexpr int atom(int p, int q) { return 64 * (p & 3) + (p & ~3) + q; }
+    static constexpr unsigned long long kEvery4th = 0x1111111111111111ull;
+    static constexpr bool round_trips(int mt_n)
+    {
+        unsigned long long seen = 0ull;
+        for (int mt = 0; mt < mt_n; mt++) {
+            for (int rr = 0; rr < 4; rr++) {
+                const int p = pos(mt, rr);
+                if (p < 0 || p > 63 || ((seen >> p) & 1ull)) return false;
+                seen |= 1ull << p;
+                for (int q = 0; q < 4; q++) {
+                    const int j = 16 * mt + 4 * rr + q;
+                    if (atom(p, q) != j) return false;
+                    // the unpacking ((m >> k) & kEvery4th) << q puts it on bit j & 63 of word k = j >> 6
+                    const int k = j >> 6;
+                    if (k > 2 || !(((((1ull << p) >> k) & kEvery4th) << q) == (1ull << (j & 63)))) return false;
+                }
+            }
+        }
+        return true;
+    }
+};
+static_assert(LeavePack::round_trips(1) && LeavePack::round_trips(2) && LeavePack::round_trips(3) && LeavePack::round_trips(4) && LeavePack::round_trips(5) &&
+              LeavePack::round_trips(6) && LeavePack::round_trips(7) && LeavePack::round_trips(8) && LeavePack::round_trips(9) && LeavePack::round_trips(10),
+              "LeavePack: (mt, rr, q) -> bit -> atom must round-trip");
 template <int KS, int MT, bool PIPE, int GN>
-__device__ __forceinline__ void lasso_scan_groups(const double *Aop, const double *Rb, const unsigned long long *Pb, int lane, double (&top)[4])
+__device__ __forceinline__ void lasso_scan_groups(const double *Aop, const double *Rb, const unsigned long long *Pb, int lane, double lam1, double (&top)[4],
+                                                  unsigned long long (&leave)[3])
 {
+    static_assert(MT <= 12, "LeavePack: three words of passive bits");
     constexpr int KDP = 4 * KS + 1;
     const int q = lane >> 4, c16 = lane & 15;
+    unsigned lw[GN][2];                                    // the lane's leave verdicts (LeavePack), low and high half
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) { lw[nt][0] = 0u; lw[nt][1] = 0u; }
     double b[GN][KS];
 #pragma unroll
     for (int nt = 0; nt < GN; nt++) {
@@ -2538,12 +2582,40 @@ __device__ __forceinline__ void lasso_scan_groups(const double *Aop, const doubl
                 const unsigned lo = ((unsigned)__double2loint(v) & 0xffffff00u) | (unsigned)(mt * 4 + rr);
                 const int hi = (pas & (int)0xffe00000) | (~pas & __double2hiint(v));     // passive: -9e307 (finite whatever the low word is; 0xfff... would be a NaN)
                 bv[nt][mt & 1] = seed_max(bv[nt][mt & 1], __hiloint2double(hi, (int)lo));
+                // a passive atom with !(t_j > 0) leaves; v > lam1 is t_j = v - lam1 > 0 bit for bit (the difference of two doubles is
+                // zero only where they are equal) and false for a NaN, which leaves
+                const int lp = LeavePack::pos(mt, rr);
+                lw[nt][lp >> 5] |= (unsigned)((v > lam1) ? 0 : pas) & (1u << (lp & 31));
             }
         }
         __builtin_amdgcn_sched_barrier(0);
         if (PIPE) {
 #pragma unroll
             for (int nt = 0; nt < GN; nt++) cur[nt] = nxt[PIPE ? nt : 0];
+        }
+    }
+    // the verdicts back to the column's row: a transpose of the four rows' words over the four groups (row swaps between TWO registers:
+    // v_permlane16_swap exchanges the odd rows of the first with the even rows of the second, v_permlane32_swap the upper half of the first
+    // with the lower half of the second), after which row q holds, for column 16 q + c16, the words fr[0 .. 3] of the rows 0 .. 3
+    {
+        unsigned long long fr[4];
+        unsigned fh[4][2];
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            const unsigned l0 = lw[0][h], l1 = GN > 1 ? lw[GN > 1 ? 1 : 0][h] : 0u, l2 = GN > 2 ? lw[GN > 2 ? 2 : 0][h] : 0u, l3 = GN > 3 ? lw[GN > 3 ? 3 : 0][h] : 0u;
+            const auto A = __builtin_amdgcn_permlane16_swap(l0, l1, false, false);         // A[0]: rows (l0.0, l1.0, l0.2, l1.2), A[1]: (l0.1, l1.1, l0.3, l1.3)
+            const auto B = __builtin_amdgcn_permlane16_swap(l2, l3, false, false);
+            const auto C = __builtin_amdgcn_permlane32_swap(A[0], B[0], false, false);     // C[0]: (l0.0, l1.0, l2.0, l3.0), C[1]: (l0.2, l1.2, l2.2, l3.2)
+            const auto D = __builtin_amdgcn_permlane32_swap(A[1], B[1], false, false);     // D[0]: (l0.1, l1.1, l2.1, l3.1), D[1]: (l0.3, l1.3, l2.3, l3.3)
+            fh[0][h] = C[0]; fh[1][h] = D[0]; fh[2][h] = C[1]; fh[3][h] = D[1];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; s++) fr[s] = ((unsigned long long)fh[s][1] << 32) | fh[s][0];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            leave[k] = 0ull;
+#pragma unroll
+            for (int s = 0; s < 4; s++) leave[k] |= ((fr[s] >> k) & LeavePack::kEvery4th) << s;
         }
     }
 #pragma unroll
@@ -2606,6 +2678,7 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
     constexpr int SLD = kSeed2Ld;
 #ifdef AMX_STATS
     int st_trips = 0, st_used = 0;
+    long long ph[5] = {0, 0, 0, 0, 0}, pt = (long long)__builtin_readcyclecounter();      // (SEED_PH: see k_nnls_seed)
 #endif
     // the workgroup's own chunk first, then the largest chunks that still have voxels (SeedFeed)
     for (int round = 0; round < 256; round++) {
@@ -2614,7 +2687,7 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
     const Chunk ck = a.schunks[cid];
     const double *__restrict__ Sg = a.Sb + (size_t)ck.dir * n_wm * SLD;
     stage_rows<KD, LD>(Sl, Sg, n_wm, SLD);
-    stage_operand<KS, MT>(Aop, Sg, n_wm, SLD);
+    stage_operand<KS, MT>(Aop, Sg, n_wm, SLD);          // (NOT normalised: the scan's values are s_j'r themselves -- its leave verdicts and the entering test rest on that)
     __syncthreads();
     const double lam1 = a.lam1, lam2 = a.lam2, tol = 1e-9, inf = __builtin_huge_val();
     const int trip_cap = a.trip_cap;
@@ -2704,10 +2777,13 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
 #ifdef AMX_STATS
         st_trips++; st_used += __builtin_popcountll(__ballot(active));
 #endif
+        SEED_PH(0);
         trips++;
         // ------------------------------------------------------------ dual values of all atoms for the 64 voxels (fp64 MFMA),
         // passive atoms masked out, arg-max in the low mantissa bits (see seed_scan_mfma): the best four of the voxel's pool
+        // ... and the passive atoms that leave, L (an inactive lane's slot is some other voxel's, or nobody's: nothing leaves there)
         double cnd[4];
+        unsigned long long L[3];
         {
             // (only the active lanes publish a column, and only the voxel groups that hold one are scanned: see ScanSlots)
             const ScanSlots sl(active);
@@ -2718,13 +2794,15 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
                 for (int w3 = 0; w3 < 3; w3++) Pb[sl.slot * 3 + w3] = P[w3];
             }
             switch (sl.groups) {
-            case 1: lasso_scan_groups<KS, MT, PREF2, 1>(Aop, Rb, Pb, lane, cnd); break;
-            case 2: lasso_scan_groups<KS, MT, PREF2, 2>(Aop, Rb, Pb, lane, cnd); break;
-            case 3: lasso_scan_groups<KS, MT, PREF2, 3>(Aop, Rb, Pb, lane, cnd); break;
-            default: lasso_scan_groups<KS, MT, PREF2, 4>(Aop, Rb, Pb, lane, cnd); break;
+            case 1: lasso_scan_groups<KS, MT, PREF2, 1>(Aop, Rb, Pb, lane, lam1, cnd, L); break;
+            case 2: lasso_scan_groups<KS, MT, PREF2, 2>(Aop, Rb, Pb, lane, lam1, cnd, L); break;
+            case 3: lasso_scan_groups<KS, MT, PREF2, 3>(Aop, Rb, Pb, lane, lam1, cnd, L); break;
+            default: lasso_scan_groups<KS, MT, PREF2, 4>(Aop, Rb, Pb, lane, lam1, cnd, L); break;
             }
 #pragma unroll
             for (int u = 0; u < 4; u++) cnd[u] = sl.fetch(cnd[u]);
+#pragma unroll
+            for (int k = 0; k < 3; k++) { const unsigned long long f = sl.fetch(L[k]); L[k] = active ? f : 0ull; }      // (every lane fetches: its own is some lane's source)
         }
         // in descending order (the tags make them distinct): when the set is nearly full the best ones enter
         {
@@ -2739,29 +2817,14 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
             ej[u] = 16 * (int)((code >> 2) & 15u) + 4 * (int)(code & 3u) + (int)(code >> 6);
             ev[u] = active && cnd[u] - lam1 > tol && ej[u] < n_wm;
         }
-        // ------------------------------------------------------------ which passive atoms leave: ONE loop over the set bits of P
-        // (per lane; the wavefront runs it for its fullest set), t_j = s_j'r - lambda1 <= 0 (x_j = t_j / lambda2) and the atom leaves
-        // -- ALL of them in the same trip.  Then, into the room that is left, up to four of the candidates enter.
+        SEED_PH(1);
+        // ------------------------------------------------------------ which passive atoms leave: t_j = s_j'r - lambda1 <= 0
+        // (x_j = t_j / lambda2) and the atom leaves -- ALL of them in the same trip, as the scan found them (L).  Then, into the room
+        // that is left, up to four of the candidates enter.
         // (5.7 instead of 8.0 trips per voxel, 95th percentile 10 instead of 15, same final supports: tools/lab/s2_block_lab.py)
-        unsigned long long L[3] = {0ull, 0ull, 0ull}, E[3] = {0ull, 0ull, 0ull};
-        {
-            unsigned long long W[3] = {active ? P[0] : 0ull, active ? P[1] : 0ull, active ? P[2] : 0ull};
-#pragma unroll 1
-            for (int it = 0; it < 32; it++) {      // (at most max_atoms atoms, TWO per pass: the gathers and the sums of one hide the other's)
-                int wq0, wq1; unsigned long long low0, low1;
-                const int j0 = seed_next_bit(W, wq0, low0);
-                if (__ballot(j0 >= 0) == 0ull) break;
-                const int j1 = seed_next_bit(W, wq1, low1);
-                const double *col0 = Sl + (j0 >= 0 ? j0 : 0) * LD, *col1 = Sl + (j1 >= 0 ? j1 : 0) * LD;
-                double t0 = -lam1, t1 = -lam1;
-#pragma unroll
-                for (int d = 0; d < KD; d++) { t0 += col0[d] * r[d]; t1 += col1[d] * r[d]; }
-                const bool out0 = j0 >= 0 && !(t0 > 0.0), out1 = j1 >= 0 && !(t1 > 0.0);
-#pragma unroll
-                for (int k = 0; k < 3; k++) L[k] |= ((out0 && wq0 == k) ? low0 : 0ull) | ((out1 && wq1 == k) ? low1 : 0ull);
-            }
-        }
+        unsigned long long E[3] = {0ull, 0ull, 0ull};
         const bool left = (L[0] | L[1] | L[2]) != 0ull;
+        SEED_PH(2);
         bool enters[4];
         {
             const int mx = a.max_atoms;            // (20; 26 where a third certificate pass takes supports of up to 24 atoms)
@@ -2812,6 +2875,7 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
 #pragma unroll
             for (int k = 0; k < 3; k++) P[k] = (P[k] & ~L[k]) | E[k];
         }
+        SEED_PH(3);
         // ------------------------------------------------------------ w = M^-1 g, r = y~ - w of the new set
         {
             LeanLane<KD> V;
@@ -2837,11 +2901,15 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
             sd[0] = P[0]; sd[1] = P[1]; sd[2] = P[2]; sd[3] = noseed ? ~0ull : 0ull;
             active = false;
         }
+        SEED_PH(4);
     }
     __syncthreads();                          // every wavefront is through with this chunk's tables
     }
 #ifdef AMX_STATS
-    if (a.stats && lane == 0) { atomicAdd(&a.stats[0], st_trips); atomicAdd(&a.stats[1], st_used); }
+    if (a.stats && lane == 0) {
+        atomicAdd(&a.stats[0], st_trips); atomicAdd(&a.stats[1], st_used);
+        for (int k = 0; k < 5; k++) atomicAdd(&a.stats[22 + k], (int)(ph[k] >> 10));
+    }
 #endif
 }
 
