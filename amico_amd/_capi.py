@@ -30,7 +30,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
            'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
-           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32',
+           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_prep_last_launch',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
@@ -165,6 +165,8 @@ def lib():
     L.amx_last_seed_stats.argtypes = [c_vp, c_i64p]
     L.amx_last_host_narrowed.argtypes = [c_vp]
     L.amx_last_path.argtypes = [c_vp, C.c_char_p, C.c_int]
+    L.amx_prep_route.argtypes = [C.c_int] * 7 + [c_i64p]
+    L.amx_prep_last_launch.argtypes = [c_vp, C.c_char_p, C.c_int, c_i64p]
     L.amx_host_pool_info.argtypes = [c_vp, C.POINTER(C.c_int)]
     L.amx_set_call_voxels.argtypes = [c_vp, C.c_int64]
     L.amx_dict_upload.argtypes = [c_vp, c_dp, C.c_int, C.c_int, C.c_int, C.POINTER(c_vp)]
@@ -870,6 +872,13 @@ class Prep:
         flat = np.lib.stride_tricks.as_strided(img, shape=(self.extent,), strides=(4,))
         return flat
 
+    def last_launch(self):
+        """-> (kernel name, workgroups, threads per workgroup, LDS bytes) of the plan's last gather (amx_prep_last_launch)"""
+        buf = C.create_string_buffer(128)
+        out = np.zeros(3, dtype=np.int64)
+        self.ctx.check(lib().amx_prep_last_launch(self._h, buf, 128, _p(out, c_i64p)))
+        return (buf.value.decode(),) + tuple(int(v) for v in out)
+
     def gather(self, img, normalize=True, b0_threshold=0.0):
         buf = self._img_buffer(img)
         y = np.zeros((self.n_vox, self.n_out))
@@ -1010,6 +1019,19 @@ class Prep:
         out = np.zeros(self.shape[:3] + (v.shape[1],), dtype=np.float32)
         self.ctx.check(lib().amx_prep_scatter(self.ctx._h, self._h, _p(v, c_dp), v.shape[1], _p(out, c_fp)))
         return out
+
+
+PREP_ROUTES = ('refused', 'tile', 'long')      # amx_prep_route: out[0]
+
+
+def prep_route(nS, n_out, n_b0, n_gidx, identity, direct, inplace):
+    """the gather's route for a plan of these sizes, without a device (amx_prep_route)
+    -> {'route': one of PREP_ROUTES, 'waves': wavefronts per workgroup, 'lds': bytes per workgroup, 'per_wave': words of one tile}"""
+    out = np.zeros(4, dtype=np.int64)
+    if lib().amx_prep_route(int(nS), int(n_out), int(n_b0), int(n_gidx), int(bool(identity)), int(bool(direct)), int(bool(inplace)),
+                            _p(out, c_i64p)) != 0:
+        raise ValueError('amx_prep_route: bad sizes')
+    return {'route': PREP_ROUTES[int(out[0])], 'waves': int(out[1]), 'lds': int(out[2]), 'per_wave': int(out[3])}
 
 
 def _replacement(replace, dtype):

@@ -312,6 +312,9 @@ struct amx_prep {
     unsigned char *dmask = nullptr; // device u8[d2][d1][d0]: mask != 0 (amx_prep_set_debias_mask; null until then)
     mutable unsigned launch_seq = 0;
     long long n_live64 = 0;
+    // what the plan's last gather launched (amx_prep_last_launch): kernel name, workgroups, threads per workgroup, LDS bytes
+    mutable const char *last_kernel = "";
+    mutable long long last_launch[3] = {0, 0, 0};
 };
 
 #define HIPCHK(ctx, call)                                                                         \

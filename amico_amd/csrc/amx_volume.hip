@@ -4,6 +4,7 @@
 // 225-268 (b0 merge, directional average), 451-452 (mask gather + clip), 472-498 (scatter).
 #include "amx_host.hpp"
 #include "amx_tensor.hpp"
+#include "amx_prep_route.hpp"
 
 using namespace amx;
 
@@ -12,8 +13,7 @@ namespace amx {
 // the lanes of a wavefront exchange data through LDS: order the accesses, no workgroup barrier needed
 #define WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
-constexpr int kDirectLd = 65;              // words per volume row of the direct-load tile (k_prep_gather)
-constexpr int kPrepWaves = 2;               // wavefronts per workgroup, one 64-voxel tile each
+// (kDirectLd, kPrepWaves and the arithmetic that picks a tile kernel: amx_prep_route.hpp)
 
 struct PrepArgs {
     const float *img; const int *rank; double *y; float *y32; float *mean_b0;     // y32: float32 output instead of y (lossless: the values ARE float32)
@@ -186,6 +186,154 @@ __global__ __launch_bounds__(64 * kPrepWaves) void k_prep_gather(PrepArgs a)
                 val = val < 0.0f ? 0.0f : val;
                 if (a.y32) dst32[j] = val;
                 else dst[j] = (double)val;
+            }
+        }
+        WAVE_SYNC();
+    }
+}
+
+// Long protocols (amx_prep_route.hpp: PREP_ROUTE_LONG -- two of k_prep_gather's tiles no longer fit 160 KB, up to 512 volumes): the
+// same tile, the same three phases and the same float32 operations in the same order, with ONE wavefront per workgroup, so one
+// T[volume][voxel] (133 KB at 512 volumes) or T[voxel][volume] (131 KB) tile per CU.  Groups that may not write in place (a scheme
+// whose first volume is a DWI, merged b0) have no room for a second tile of n_out outputs: lane = voxel makes kPrepLongChunk
+// outputs at a time into O[voxel][chunk] from the untouched T, and the wavefront writes those rows out before the next chunk.
+// No tensor fit rides on this tile: on a long protocol the directions come from the rows it wrote (prep_gather_dev).
+template <bool IDENTITY, bool DIRECT>
+__global__ __launch_bounds__(64) void k_prep_long(PrepArgs a)
+{
+    extern __shared__ float smf[];
+    const int lane = threadIdx.x;
+    constexpr bool direct = IDENTITY && DIRECT;
+    const bool chunked = !IDENTITY && !a.inplace;
+    const int tile = direct ? a.nS * kDirectLd : 64 * a.ldt;
+    float *T = smf;
+    float *O = smf + tile;                                    // (chunked only) [64][kPrepLongChunkLd]
+    int *P = reinterpret_cast<int *>(smf + tile + (chunked ? 64 * kPrepLongChunkLd : 0));
+    int *Pb0 = P, *Pgp = P + a.n_b0, *Pgi = Pgp + a.n_out + 1;
+    for (int i = lane; i < a.n_b0; i += 64) Pb0[i] = a.b0idx[i];
+    if (!IDENTITY) {
+        for (int i = lane; i <= a.n_out; i += 64) Pgp[i] = a.gptr[i];
+        for (int i = lane; i < a.n_gidx; i += 64) Pgi[i] = a.gidx[i];
+    }
+    WAVE_SYNC();
+    for (long long t = next_live_tile(a, lane); t >= 0; t = next_live_tile(a, lane)) {
+        const long long row = t / a.tiles_per_row;
+        const long long x0 = (t - row * a.tiles_per_row) * 64;
+        const long long i2 = row / a.d1, i1 = row - i2 * a.d1;
+        const long long x = x0 + lane;
+        const int r = x < a.d0 ? a.rank[(i2 * a.d1 + i1) * a.d0 + x] : -1;
+        const unsigned long long live = __ballot(r >= 0);
+        if (live == 0ull) continue;
+        const long long base = x0 * a.s0 + i1 * a.s1 + i2 * a.s2;
+        float *row_l = T + lane * a.ldt;
+        if (a.layout == 2) {
+            // interleaved: one row of nS samples per live voxel, global -> LDS, 64 samples per load
+            for (int k = 0; k < 64; k++) {
+                if (!((live >> k) & 1ull)) continue;
+                const float *rowp = a.img + base + k * a.s0;
+                for (int v0 = 0; v0 < a.nS; v0 += 64) {
+                    if (v0 + lane < a.nS)
+                        __builtin_amdgcn_global_load_lds(rowp + v0 + lane, (__attribute__((address_space(3))) void *)(T + k * a.ldt + v0), 4, 0, 0);
+                }
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if (direct) {
+            // planar, identity groups: one 256-byte run per volume, global -> LDS
+            if (r >= 0) {
+                const float *src = a.img + base + lane * a.s0;
+                int v = 0;
+                for (; v + 8 <= a.nS; v += 8) {
+#pragma unroll
+                    for (int u = 0; u < 8; u++)
+                        __builtin_amdgcn_global_load_lds(src + (long long)(v + u) * a.sv, (__attribute__((address_space(3))) void *)(T + (v + u) * kDirectLd), 4, 0, 0);
+                }
+                for (; v < a.nS; v++)
+                    __builtin_amdgcn_global_load_lds(src + (long long)v * a.sv, (__attribute__((address_space(3))) void *)(T + v * kDirectLd), 4, 0, 0);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        } else if (r >= 0) {
+            // planar with groups, or generic strides: through registers into the voxel's row, 32 volumes in flight
+            const float *src = a.img + base + lane * a.s0;
+            int v = 0;
+            for (; v + 32 <= a.nS; v += 32) {
+                float tv[32];
+#pragma unroll
+                for (int u = 0; u < 32; u++) tv[u] = src[(long long)(v + u) * a.sv];
+#pragma unroll
+                for (int u = 0; u < 32; u++) row_l[v + u] = tv[u];
+            }
+            for (; v < a.nS; v++) row_l[v] = src[(long long)v * a.sv];
+        }
+        WAVE_SYNC();
+        float f = 1.0f;
+        if (r >= 0) {
+            if (a.normalize) {
+                float m = 0.0f;
+                if (direct) { for (int i = 0; i < a.n_b0; i++) m = m + T[Pb0[i] * kDirectLd + lane]; }
+                else { for (int i = 0; i < a.n_b0; i++) m = m + row_l[Pb0[i]]; }
+                m = m / (float)a.n_b0;
+                if (a.mean_b0) a.mean_b0[r] = m;
+                f = (m <= a.thr) ? 0.0f : 1.0f / m;
+            }
+            if (!IDENTITY && a.normalize)
+                for (int v = 0; v < a.nS; v++) row_l[v] = row_l[v] * f;            // rounded (stored) before any group sum reads it
+            if (!IDENTITY && !chunked) {
+                // in place: output j takes volume j's slot of the row, and a later group reads what stands there (core.py:231-245)
+                for (int j = 0; j < a.n_out; j++) {
+                    const int g0 = Pgp[j], g1 = Pgp[j + 1];
+                    float acc = row_l[Pgi[g0]];
+                    if (g1 - g0 > 1) {
+                        for (int g = g0 + 1; g < g1; g++) acc = acc + row_l[Pgi[g]];
+                        acc = acc / (float)(g1 - g0);
+                    }
+                    row_l[j] = acc;
+                }
+            }
+        }
+        if (!IDENTITY) WAVE_SYNC();
+        if (!chunked) {
+            const bool scale = IDENTITY && a.normalize;
+            for (int k = 0; k < 64; k++) {
+                if (!((live >> k) & 1ull)) continue;
+                const int rk = __builtin_amdgcn_readlane(r, k);
+                const float fk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, f), k));
+                double *dst = a.y + (long long)rk * a.n_out;
+                float *dst32 = a.y32 + (long long)rk * a.n_out;
+                for (int j = lane; j < a.n_out; j += 64) {
+                    float val = direct ? T[j * kDirectLd + k] : T[k * a.ldt + j];
+                    if (scale) val = val * fk;
+                    val = val < 0.0f ? 0.0f : val;
+                    if (a.y32) dst32[j] = val;
+                    else dst[j] = (double)val;
+                }
+            }
+        } else {
+            for (int j0 = 0; j0 < a.n_out; j0 += kPrepLongChunk) {
+                const int jn = a.n_out - j0 < kPrepLongChunk ? a.n_out - j0 : kPrepLongChunk;
+                if (r >= 0) {
+                    float *out_l = O + lane * kPrepLongChunkLd;
+                    for (int jj = 0; jj < jn; jj++) {
+                        const int g0 = Pgp[j0 + jj], g1 = Pgp[j0 + jj + 1];
+                        float acc = row_l[Pgi[g0]];
+                        if (g1 - g0 > 1) {
+                            for (int g = g0 + 1; g < g1; g++) acc = acc + row_l[Pgi[g]];
+                            acc = acc / (float)(g1 - g0);
+                        }
+                        out_l[jj] = acc;
+                    }
+                }
+                WAVE_SYNC();
+                for (int k = 0; k < 64; k++) {
+                    if (!((live >> k) & 1ull)) continue;
+                    const int rk = __builtin_amdgcn_readlane(r, k);
+                    if (lane < jn) {
+                        float val = O[k * kPrepLongChunkLd + lane];
+                        val = val < 0.0f ? 0.0f : val;
+                        if (a.y32) a.y32[(long long)rk * a.n_out + j0 + lane] = val;
+                        else a.y[(long long)rk * a.n_out + j0 + lane] = (double)val;
+                    }
+                }
+                WAVE_SYNC();
             }
         }
         WAVE_SYNC();
@@ -541,6 +689,60 @@ int amx_prep_gather_directions_device_f32(amx_ctx *ctx, const amx_prep *p, const
     return prep_gather_dev(ctx, p, d_img, normalize, b0_threshold, nullptr, d_y, d_mean_b0, hip_stream, h, d_dirs);
 }
 
+int amx_prep_route(int nS, int n_out, int n_b0, int n_gidx, int identity, int direct, int inplace, int64_t out[4])
+{
+    if (!out || nS < 1 || n_out < 1 || n_out > nS || n_b0 < 0 || n_gidx < n_out || (direct && !identity)) return AMX_E_BADARG;
+    const PrepRoute rt = prep_route(nS, n_out, n_b0, n_gidx, identity != 0, direct != 0, inplace != 0);
+    out[0] = rt.route; out[1] = rt.waves; out[2] = (int64_t)rt.lds; out[3] = (int64_t)rt.per_wave;
+    return AMX_OK;
+}
+
+int amx_prep_last_launch(const amx_prep *p, char *buf, int cap, int64_t out[3])
+{
+    if (!p || !buf || cap <= 0 || !out) return AMX_E_BADARG;
+    snprintf(buf, (size_t)cap, "%s", p->last_kernel);
+    for (int k = 0; k < 3; k++) out[k] = p->last_launch[k];
+    return AMX_OK;
+}
+
+static void note_launch(const amx_prep *p, const char *kernel, long long grid, long long block, size_t lds)
+{
+    p->last_kernel = kernel;
+    p->last_launch[0] = grid; p->last_launch[1] = block; p->last_launch[2] = (long long)lds;
+}
+
+// PREP_ROUTE_LONG: k_prep_long, one workgroup of one wavefront per CU (its tile leaves no room for a second); `a` as prep_gather_dev
+// filled it.  With a tensor helper the directions are fitted from the rows the gather wrote, as for the WLS / NLLS methods.
+static int prep_gather_long(amx_ctx *ctx, const amx_prep *p, PrepArgs a, const PrepRoute &rt, hipStream_t s, const amx_dti *dti, double *d_dirs)
+{
+    static bool attr_set[64];                                        // per device, k_prep_long's instantiations only
+    if (!attr_set[ctx->device & 63]) {
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
+        attr_set[ctx->device & 63] = true;
+    }
+    const int per_cu = (int)(kPrepLdsMax / rt.lds);                  // 1; 2 for groups not in place up to about 245 volumes
+    long long grid = 256LL * per_cu;
+    if (grid > p->n_live64) grid = p->n_live64;
+    int *const my_counter = p->tile_counter + (p->launch_seq++ % amx_prep::kCounterRing);
+    a.live = p->live64; a.n_live = p->n_live64; a.counter = my_counter;
+    a.wt = nullptr; a.dirs = nullptr;
+    HIPCHK(ctx, hipMemsetAsync(my_counter, 0, sizeof(int), s));
+    rec(ctx, 8, s);
+    const bool identity = p->identity != 0;
+    if (identity && a.direct) hipLaunchKernelGGL((k_prep_long<true, true>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
+    else if (identity) hipLaunchKernelGGL((k_prep_long<true, false>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
+    else hipLaunchKernelGGL((k_prep_long<false, false>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
+    note_launch(p, identity ? (a.direct ? "k_prep_long<true,true>" : "k_prep_long<true,false>") : "k_prep_long<false,false>", grid, 64, rt.lds);
+    HIPCHK(ctx, hipGetLastError());
+    rec(ctx, 9, s);
+    if (dti != nullptr)
+        return a.y32 ? amx_dti_directions_device_f32(ctx, dti, a.y32, p->n_vox, d_dirs, (void *)s)
+                     : amx_dti_directions_device(ctx, dti, a.y, p->n_vox, d_dirs, (void *)s);
+    return AMX_OK;
+}
+
 static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, int normalize, float b0_threshold,
                            double *d_y, float *d_y32, float *d_mean_b0, void *hip_stream, const amx_dti *dti, double *d_dirs)
 {
@@ -575,9 +777,13 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     if (dti != nullptr) { a.wt = dti->wt; a.min_signal = dti->min_signal; a.dirs = d_dirs; }
     const bool identity = p->identity != 0;
     a.direct = (identity && p->layout != 2) ? 1 : 0;
-    const size_t per_wave = identity ? (a.direct ? (size_t)a.nS * kDirectLd : (size_t)64 * a.ldt) : (size_t)64 * a.ldt * (a.inplace ? 1 : 2);
-    const size_t lds = ((size_t)kPrepWaves * per_wave + (size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(float);
-    if (lds > 160 * 1024) return amx_bad(ctx, "amx_prep_gather: scheme too long for the LDS tile");
+    // grouped outputs on a planar image whose groups read no earlier output: the streaming kernels, which hold no tile
+    const bool stream = !identity && !p->hazard && p->layout == 1;
+    const PrepRoute rt = prep_route(p->nS, p->n_out, p->n_b0, p->n_gidx, identity, a.direct != 0, p->inplace != 0);
+    if (rt.route == PREP_ROUTE_REFUSED)
+        return amx_bad(ctx, "amx_prep_gather: scheme too long for the LDS tile (at most 512 volumes)");
+    if (rt.route == PREP_ROUTE_LONG && !stream) return prep_gather_long(ctx, p, a, rt, s, dti, d_dirs);
+    const size_t lds = rt.lds;
     static bool attr_set[64];                                        // per device: the attribute belongs to (function, device)
     if (!attr_set[ctx->device & 63]) {
         HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
@@ -596,7 +802,7 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     // be in flight together (two streams, double-buffered images sharing a mask) without sharing or resetting each other's ticket
     int *const my_counter = p->tile_counter + (p->launch_seq++ % amx_prep::kCounterRing);
     a.live = p->live64; a.n_live = p->n_live64; a.counter = my_counter;
-    if (!identity && !p->hazard && p->layout == 1) {
+    if (stream) {
         // grouped outputs on a planar image: streaming kernel, no transposition tile
         const size_t lds_s = ((size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(int);
         long long g2 = (a.n_tiles + 3) / 4;
@@ -608,8 +814,10 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
             long long g4 = ((p->d[0] * p->d[1] * p->d[2] + 255) / 256 + 3) / 4;
             if (g4 > 256LL * 16) g4 = 256LL * 16;
             hipLaunchKernelGGL(k_prep_stream4, dim3((unsigned)g4), dim3(256), lds_s, s, a);
+            note_launch(p, "k_prep_stream4", g4, 256, lds_s);
         } else {
             hipLaunchKernelGGL(k_prep_stream, dim3((unsigned)g2), dim3(256), lds_s, s, a);
+            note_launch(p, "k_prep_stream", g2, 256, lds_s);
         }
         HIPCHK(ctx, hipGetLastError());
         rec(ctx, 9, s);
@@ -629,6 +837,9 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     else if (identity && a.direct) hipLaunchKernelGGL((k_prep_gather<true, true>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
     else if (identity) hipLaunchKernelGGL((k_prep_gather<true, false>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
     else hipLaunchKernelGGL((k_prep_gather<false, false>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
+    note_launch(p, dti != nullptr ? (identity ? (a.direct ? "k_prep_gather<true,true,true>" : "k_prep_gather<true,false,true>") : "k_prep_gather<false,false,true>")
+                                  : (identity ? (a.direct ? "k_prep_gather<true,true>" : "k_prep_gather<true,false>") : "k_prep_gather<false,false>"),
+                grid, 64 * kPrepWaves, lds);
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, s);
     return AMX_OK;

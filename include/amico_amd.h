@@ -431,8 +431,20 @@ int amx_prep_gather(amx_ctx *ctx, const amx_prep *p, const float *img, int norma
  * amx_*_fit_device_f32 / amx_dti_directions_device_f32 calls read them in place)                                                  */
 int amx_prep_gather_device_f32(amx_ctx *ctx, const amx_prep *p, const float *d_img, int normalize, float b0_threshold,
                                float *d_y, float *d_mean_b0, void *hip_stream);
+/* Limit: protocols of up to 512 volumes (nS <= 512, the limit of the fits), in every layout and with every grouping; a longer one is
+ * refused with AMX_E_BADARG ("scheme too long for the LDS tile (at most 512 volumes)").  The kernel keeps all nS samples of a
+ * 64-voxel tile in LDS.  While two such tiles fit 160 KB (up to about 310 volumes; 158 when the groups may not write in place) a
+ * workgroup holds two wavefronts with a tile each; above that it holds one (the long route), and groups that may not write in place
+ * are made 64 output volumes at a time.  Both routes compute the same float32 operations in the same order.                       */
 int amx_prep_gather_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, int normalize,
                            float b0_threshold, double *d_y, float *d_mean_b0, void *hip_stream);
+/* The arithmetic that picks the route, without a device: out = {route (0 refused, 1 two tiles per workgroup, 2 long), wavefronts per
+ * workgroup, LDS bytes per workgroup, words of one wavefront's tile}.  identity: every output volume is its input volume; direct:
+ * identity and the image not interleaved; inplace: no group reads a volume an earlier output replaced, or overwrite_in_order.
+ * (Grouped outputs on a planar image whose groups read no earlier output take the streaming kernels, which hold no tile.)          */
+int amx_prep_route(int nS, int n_out, int n_b0, int n_gidx, int identity, int direct, int inplace, int64_t out[4]);
+/* What the plan's last gather launched (read-only): the kernel's name into buf, out = {workgroups, threads per workgroup, LDS bytes} */
+int amx_prep_last_launch(const amx_prep *p, char *buf, int cap, int64_t out[3]);
 /* The gather with the tensor fit taken along (round 5): y AND the principal directions of core.py:431-436, 456-458 in ONE pass over
  * the image -- lane = voxel contracts log(max(y, min_signal)) with the helper's pseudo-inverse while the voxel's values are in the
  * gather's LDS tile; what amx_prep_gather_device[_f32] followed by amx_dti_directions_device[_f32] computes (y bit-identical, the
