@@ -177,7 +177,7 @@ int amx_sync_status(amx_ctx *ctx, void *hip_stream)
     if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificates LASSO, second pass: %d voxels, %d certified (more than 18 atoms %d, x <= 0 %d, dual %d), %d dual values\n",
                              st[ST_SEED + 48], st[ST_SEED + 49], st[ST_SEED + 50], st[ST_SEED + 51], st[ST_SEED + 52], st[ST_SEED + 53]);
     if (ctx->opt_debug) fprintf(stderr, "[amx] LASSO seeds: tried %d certified %d; seed solver trips %d lane-trips used %d\n", st[ST_SEED + 18], st[ST_SEED + 19], st[ST_SEED + 20], st[ST_SEED + 21]);
-    if (ctx->opt_debug) fprintf(stderr, "[amx] LASSO seed solver kcycles (wave sums / 1024): take %d scan %d leave-test %d changes %d factor+solve %d\n", st[ST_SEED + 42], st[ST_SEED + 43], st[ST_SEED + 44], st[ST_SEED + 45], st[ST_SEED + 46]);
+    if (ctx->opt_debug) fprintf(stderr, "[amx] LASSO seed solver kcycles (wave sums / 1024): take %d scan %d changes %d factor+solve %d; change() calls %d (one loop over the lanes' own lists: %d)\n", st[ST_SEED + 42], st[ST_SEED + 43], st[ST_SEED + 45], st[ST_SEED + 46], st[ST_SEED + 44], st[ST_SEED + 47]);
     if (ctx->opt_debug) fprintf(stderr, "[amx] seed solver kcycles (wave sums / 1024): take %d solve+drop %d residual %d scan %d append %d store %d\n", st[ST_SEED + 12], st[ST_SEED + 13], st[ST_SEED + 14], st[ST_SEED + 15], st[ST_SEED + 16], st[ST_SEED + 17]);
     if (ctx->opt_debug) fprintf(stderr, "[amx] Gram certificate kcycles (decode | gather+factor+solve | screening | exact duals | output): stage 1 %d %d %d %d %d, stage 3 %d %d %d %d %d\n",
                              st[ST_SEED + 60], st[ST_SEED + 61], st[ST_SEED + 62], st[ST_SEED + 63], st[ST_SEED + 64], st[ST_SEED + 65], st[ST_SEED + 66], st[ST_SEED + 67], st[ST_SEED + 68], st[ST_SEED + 69]);

@@ -2422,7 +2422,7 @@ struct Seed2Args {
     double lam1, lam2;
     int *gcount;                  // [max_schunks + 1]: see SeedArgs
     int n_gcount;
-    int *stats;                   // optional counters (AMX_STATS): [0] trips, [1] lane-trips in use, [22 .. 26] kcycles of taking voxels, scan, leave test, changes, factor + solve
+    int *stats;                   // optional counters (AMX_STATS): [0] trips, [1] lane-trips in use, [22, 23, 25, 26] kcycles of taking voxels, scan, changes, factor + solve, [24] change() calls a wavefront issued, [27] the calls ONE loop over the lanes' own lists (leavers, then enterers) would have issued
     double *trace;                // unused (a retired per-trip trace); kept so that the kernel argument layout stays as it is
     int trip_cap;                 // see SeedArgs
     int max_atoms;                // a voxel whose passive set reaches this many atoms and wants more is given up (its set goes on as an incomplete seed)
@@ -2493,14 +2493,19 @@ __global__ void __launch_bounds__(1024) k_noddi_project2(const Seed2Args a)
 // The scan also says which PASSIVE atoms leave (lam1: the LASSO operand is not normalised, so s_j'r - lambda1 of a passive atom is
 // its t_j = lambda2 x_j): leave[0 .. 2], to lane l for column l, holds the passive atoms with !(t_j > 0) in the layout of P (zero in
 // the lanes of the groups >= GN).  A lane's element (mt, rr) is bit 16 mt + 4 rr of the row-shifted mask -- every fourth bit of three
-// words -- so ONE 64-bit word per lane and group takes all its verdicts (LeavePack): a compare, a select and an and-or per element,
+// words -- so ONE 64-bit word per lane and group takes all its verdicts (LeavePack): a compare, a select of the element's constant
+// bit and half an or per element -- EVERY atom's !(t_j > 0), masked with the passive bits, packed the same way, once per group --
 // beside the matrix pipe, where a loop over the set bits of P computed every t_j a second time.
+// The passive atoms stay out of the maxima by their SIGN: the passive bit, shifted to bit 31, is or-ed into the value's high word,
+// and a value <= -0 never enters (lambda1 >= 0).  A shift and an and-or, where a select of the high word took three instructions.
 struct LeavePack {
     // bit of the element (mt, rr) in the lane's word: word k of the row-shifted mask moved up by k
     static constexpr int pos(int mt, int rr) { return ((16 * mt + 4 * rr) & 63) + ((16 * mt + 4 * rr) >> 6); }
     // ... and back: the atom that bit p of row q's word stands for (unpacked: word p & 3, bit (p & ~3) + q)
     static constexpr int atom(int p, int q) { return 64 * (p & 3) + (p & ~3) + q; }
     static constexpr unsigned long long kEvery4th = 0x1111111111111111ull;
+    // word k of P, shifted down by the lane's row q, in the layout of the verdicts: the passive bits of the lane's elements of that word
+    static constexpr unsigned long long pack(unsigned long long row_shifted, int k) { return (row_shifted & kEvery4th) << k; }
     static constexpr bool round_trips(int mt_n)
     {
         unsigned long long seen = 0ull;
@@ -2515,6 +2520,8 @@ struct LeavePack {
                     // the unpacking ((m >> k) & kEvery4th) << q puts it on bit j & 63 of word k = j >> 6
                     const int k = j >> 6;
                     if (k > 2 || !(((((1ull << p) >> k) & kEvery4th) << q) == (1ull << (j & 63)))) return false;
+                    // ... and the atom's bit of P, row-shifted, packs onto the very bit p
+                    if (pack((1ull << (j & 63)) >> q, k) != (1ull << p)) return false;
                 }
             }
         }
@@ -2575,17 +2582,19 @@ __device__ __forceinline__ void lasso_scan_groups(const double *Aop, const doubl
 #pragma unroll
             for (int rr = 0; rr < 4; rr++) {
                 const int bit = 16 * mt + 4 * rr;        // position of this atom in the row-shifted mask
-                // the atom's passive bit spread over a word (bit-field extract, sign extended), then a bit-wise select of the high word
+                // the atom's passive bit becomes the value's SIGN: a passive atom's value is at most -0 in the maxima, and only values
+                // above lambda1 >= 0 (amx_fit_dev.hip refuses a negative one) enter -- the same atoms as with any other mask (a
+                // non-passive value keeps its sign; a NaN stays a NaN, which v_max_f64 drops)
                 const unsigned half = (unsigned)(pw[nt] >> (bit & 32));
-                const int pas = (int)(half << (31 - (bit & 31))) >> 31;
+                const unsigned pas = (half << (31 - (bit & 31))) & 0x80000000u;
                 const double v = cur[nt][rr];
                 const unsigned lo = ((unsigned)__double2loint(v) & 0xffffff00u) | (unsigned)(mt * 4 + rr);
-                const int hi = (pas & (int)0xffe00000) | (~pas & __double2hiint(v));     // passive: -9e307 (finite whatever the low word is; 0xfff... would be a NaN)
+                const int hi = (int)(pas | (unsigned)__double2hiint(v));
                 bv[nt][mt & 1] = seed_max(bv[nt][mt & 1], __hiloint2double(hi, (int)lo));
-                // a passive atom with !(t_j > 0) leaves; v > lam1 is t_j = v - lam1 > 0 bit for bit (the difference of two doubles is
-                // zero only where they are equal) and false for a NaN, which leaves
+                // an atom with !(t_j > 0) leaves if it is passive (masked once per group, below); v > lam1 is t_j = v - lam1 > 0 bit for
+                // bit (the difference of two doubles is zero only where they are equal) and false for a NaN, which leaves
                 const int lp = LeavePack::pos(mt, rr);
-                lw[nt][lp >> 5] |= (unsigned)((v > lam1) ? 0 : pas) & (1u << (lp & 31));
+                lw[nt][lp >> 5] |= (v > lam1) ? 0u : (1u << (lp & 31));
             }
         }
         __builtin_amdgcn_sched_barrier(0);
@@ -2593,6 +2602,15 @@ __device__ __forceinline__ void lasso_scan_groups(const double *Aop, const doubl
 #pragma unroll
             for (int nt = 0; nt < GN; nt++) cur[nt] = nxt[PIPE ? nt : 0];
         }
+    }
+    // only passive atoms leave: ONE and per group, where every element had its own -- with the lane's passive bits packed the way the
+    // verdicts are (LeavePack::pack; read once more here: held through the scan they would cost two registers a group)
+#pragma unroll
+    for (int nt = 0; nt < GN; nt++) {
+        unsigned long long pk = 0ull;
+#pragma unroll
+        for (int k = 0; k < (16 * MT + 63) / 64; k++) pk |= LeavePack::pack(Pb[(16 * nt + c16) * 3 + k] >> q, k);
+        lw[nt][0] &= (unsigned)pk; lw[nt][1] &= (unsigned)(pk >> 32);
     }
     // the verdicts back to the column's row: a transpose of the four rows' words over the four groups (row swaps between TWO registers:
     // v_permlane16_swap exchanges the odd rows of the first with the even rows of the second, v_permlane32_swap the upper half of the first
@@ -2677,7 +2695,7 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
     const int lane = threadIdx.x & 63, q = lane >> 4, c16 = lane & 15;
     constexpr int SLD = kSeed2Ld;
 #ifdef AMX_STATS
-    int st_trips = 0, st_used = 0;
+    int st_trips = 0, st_used = 0, st_calls = 0, st_calls_one = 0;
     long long ph[5] = {0, 0, 0, 0, 0}, pt = (long long)__builtin_readcyclecounter();      // (SEED_PH: see k_nnls_seed)
 #endif
     // the workgroup's own chunk first, then the largest chunks that still have voxels (SeedFeed)
@@ -2824,7 +2842,6 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
         // (5.7 instead of 8.0 trips per voxel, 95th percentile 10 instead of 15, same final supports: tools/lab/s2_block_lab.py)
         unsigned long long E[3] = {0ull, 0ull, 0ull};
         const bool left = (L[0] | L[1] | L[2]) != 0ull;
-        SEED_PH(2);
         bool enters[4];
         {
             const int mx = a.max_atoms;            // (20; 26 where a third certificate pass takes supports of up to 24 atoms)
@@ -2856,7 +2873,17 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
 #pragma unroll
                     for (int j = 0; j <= i; j++) M[stri<KD>(i, j)] += sk[i] * sv[j];
                 }
+#ifdef AMX_STATS
+                st_calls++;
+#endif
             };
+#ifdef AMX_STATS
+            {   // what ONE loop over every lane's own list (its leavers, then its enterers) would issue for this trip
+                int mx = __builtin_popcountll(L[0]) + __builtin_popcountll(L[1]) + __builtin_popcountll(L[2]) + (int)enters[0] + (int)enters[1] + (int)enters[2] + (int)enters[3];
+                for (int o = 32; o >= 1; o >>= 1) mx = max(mx, __shfl_xor(mx, o));
+                st_calls_one += mx;
+            }
+#endif
             unsigned long long W[3] = {L[0], L[1], L[2]};
 #pragma unroll 1
             for (int it = 0; it < 64; it++) {      // (at most max_atoms atoms)
@@ -2908,7 +2935,8 @@ __global__ void __launch_bounds__(256, OCC2 ? 2 : kSeed2Occ) k_lasso_seed(const 
 #ifdef AMX_STATS
     if (a.stats && lane == 0) {
         atomicAdd(&a.stats[0], st_trips); atomicAdd(&a.stats[1], st_used);
-        for (int k = 0; k < 5; k++) atomicAdd(&a.stats[22 + k], (int)(ph[k] >> 10));
+        for (int k = 0; k < 5; k++) if (k != 2) atomicAdd(&a.stats[22 + k], (int)(ph[k] >> 10));
+        atomicAdd(&a.stats[24], st_calls); atomicAdd(&a.stats[27], st_calls_one);
     }
 #endif
 }
