@@ -30,7 +30,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
            'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
-           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_prep_last_launch',
+           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_noddi_route', 'amx_prep_last_launch',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
@@ -166,6 +166,7 @@ def lib():
     L.amx_last_host_narrowed.argtypes = [c_vp]
     L.amx_last_path.argtypes = [c_vp, C.c_char_p, C.c_int]
     L.amx_prep_route.argtypes = [C.c_int] * 7 + [c_i64p]
+    L.amx_noddi_route.argtypes = [C.c_int] * 5 + [C.c_int64] * 2 + [C.c_double] * 2 + [C.c_char_p, C.c_int, c_i64p]
     L.amx_prep_last_launch.argtypes = [c_vp, C.c_char_p, C.c_int, c_i64p]
     L.amx_host_pool_info.argtypes = [c_vp, C.POINTER(C.c_int)]
     L.amx_set_call_voxels.argtypes = [c_vp, C.c_int64]
@@ -1032,6 +1033,35 @@ def prep_route(nS, n_out, n_b0, n_gidx, identity, direct, inplace):
                             _p(out, c_i64p)) != 0:
         raise ValueError('amx_prep_route: bad sizes')
     return {'route': PREP_ROUTES[int(out[0])], 'waves': int(out[1]), 'lds': int(out[2]), 'per_wave': int(out[3])}
+
+
+NODDI_BUILDS = ('none', 'small', 'f32_8', 'f64_12', 'f64_nw', 'f32_nw', 'global', 'gram', 'gram_left', 'qr', 'big_all')      # NoddiBuild (csrc/amx_noddi_route.hpp)
+NODDI_ROUTE_WORDS = ('seeds', 'global', 'gemm_ks', 'gemm_passes', 'gemm_window', 'gcert', 'repair', 'rescue', 'tile_in_lds', 'seeds2', 'gcert2', 'wide',
+                     'third', 'min_items', 'seed2_max_atoms', 'seed2_trip_add', 'left2_second_half', 'left2_count', 'seed_occ2', 'seed2_occ2',
+                     'seed_chunk', 'seed_waves', 'seed1_waves', 'seed2_waves', 's1', 's2', 's2_gram', 's3', 'n_launch')
+
+
+def noddi_route(nS, n_wm, n_dwi, ndirs, is_exvivo, n_vox, call_vox=0, lambda1=0.5, lambda2=1e-3):
+    """which kernels a NODDI fit of n_vox voxels (a batch of a call of call_vox voxels; 0: the call itself) launches on a dictionary of this
+    shape, every switch at its default, without a device (amx_noddi_route) -> the words of NODDI_ROUTE_WORDS (flags as bool, s1 / s2 / s3 as
+    names of NODDI_BUILDS), 'path' in the format of Context.last_path() and 'launches': [(kernel, wavefronts, LDS bytes, LDS bytes of its
+    re-run pass)] in launch order"""
+    out = np.zeros(96, dtype=np.int64)
+    buf = C.create_string_buffer(2048)
+    if lib().amx_noddi_route(int(nS), int(n_wm), int(n_dwi), int(ndirs), int(bool(is_exvivo)), int(n_vox), int(call_vox), float(lambda1),
+                             float(lambda2), buf, 2048, _p(out, c_i64p)) != 0:
+        raise ValueError('amx_noddi_route: bad sizes')
+    rt = {k: int(v) for k, v in zip(NODDI_ROUTE_WORDS, out)}
+    for k in ('seeds', 'global', 'gcert', 'repair', 'rescue', 'tile_in_lds', 'seeds2', 'gcert2', 'wide', 'third', 'left2_second_half', 'seed_occ2',
+              'seed2_occ2', 's2_gram'):
+        rt[k] = bool(rt[k])
+    for k in ('s1', 's2', 's3'):
+        rt[k] = NODDI_BUILDS[rt[k]]
+    rt['path'] = buf.value.decode()
+    names = rt['path'].split(' -> ')
+    w = out[len(NODDI_ROUTE_WORDS):len(NODDI_ROUTE_WORDS) + 3 * rt['n_launch']].reshape(-1, 3)
+    rt['launches'] = [(names[i], int(w[i, 0]), int(w[i, 1]), int(w[i, 2])) for i in range(rt['n_launch'])]
+    return rt
 
 
 def _replacement(replace, dtype):

@@ -33,6 +33,24 @@ __global__ void k_selftest(double *out)
 
 }  // namespace
 
+// one switch of the table into its field: v is what the environment holds for it, or null for its default
+static void set_switch(amx_ctx *ctx, const amx_switch &w, const char *v)
+{
+    const bool given = v && *v;
+    long long c[3] = {w.dflt[0], w.dflt[1], w.dflt[2]};
+    switch (w.kind) {
+    case SW_FLAG: ctx->*w.flag = given && *v != '0'; break;
+    case SW_OFF: ctx->*w.flag = v && *v == '0'; break;
+    case SW_GIVEN: ctx->*w.flag = v != nullptr; break;
+    case SW_CHAR: ctx->*w.num = v ? (unsigned char)*v : w.dflt[0]; break;
+    case SW_INT: ctx->*w.num = given ? w.fix(atoll(v), w.dflt[0]) : w.dflt[0]; break;
+    case SW_LIST:
+        if (given) sscanf(v, w.fmt, &c[0], &c[1], &c[2]);
+        for (int k = 0; k < 3; k++) (ctx->*w.list)[k] = given ? w.fix(c[k], w.dflt[k]) : c[k];
+        break;
+    }
+}
+
 // =================================================================== C ABI
 extern "C" {
 
@@ -70,22 +88,7 @@ int amx_ctx_create(int device, amx_ctx **out)
         return AMX_E_HIP;
     }
     for (int k = 0; k < kEv; k++) { hipEventCreate(&ctx->ev[k]); ctx->ev_valid[k] = false; }
-    for (const amx_switch &w : kSwitches) {                  // the ONE place that reads the environment (amx_host.hpp)
-        const char *v = getenv(w.name);
-        const bool given = v && *v;
-        long long c[3] = {w.dflt[0], w.dflt[1], w.dflt[2]};
-        switch (w.kind) {
-        case SW_FLAG: ctx->*w.flag = given && *v != '0'; break;
-        case SW_OFF: ctx->*w.flag = v && *v == '0'; break;
-        case SW_GIVEN: ctx->*w.flag = v != nullptr; break;
-        case SW_CHAR: ctx->*w.num = v ? (unsigned char)*v : w.dflt[0]; break;
-        case SW_INT: ctx->*w.num = given ? w.fix(atoll(v), w.dflt[0]) : w.dflt[0]; break;
-        case SW_LIST:
-            if (given) sscanf(v, w.fmt, &c[0], &c[1], &c[2]);
-            for (int k = 0; k < 3; k++) (ctx->*w.list)[k] = given ? w.fix(c[k], w.dflt[k]) : c[k];
-            break;
-        }
-    }
+    for (const amx_switch &w : kSwitches) set_switch(ctx, w, getenv(w.name));      // the ONE place that reads the environment (amx_host.hpp)
     reset_status(ctx, nullptr);
     hipStreamSynchronize(nullptr);
     *out = ctx;
@@ -370,6 +373,32 @@ int amx_last_path(amx_ctx *ctx, char *buf, int cap)
 {
     if (!ctx || !buf || cap <= 0) return AMX_E_BADARG;
     snprintf(buf, (size_t)cap, "%s", ctx->path.c_str());
+    return AMX_OK;
+}
+
+// the route of a NODDI fit (amx_noddi_route.hpp) for a dictionary of this shape, as amx_lut_upload_noddi would build it, with every switch at its default
+int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64_t n_vox, int64_t call_vox, double lambda1, double lambda2,
+                    char *path, int cap, int64_t out[AMX_ROUTE_WORDS])
+{
+    if (!path || cap <= 0 || !out || nS < 1 || nS > 512 || n_wm < 1 || n_wm + 1 + (is_exvivo ? 1 : 0) > 256 || n_dwi < 0 || n_dwi > nS || ndirs < 1 ||
+        n_vox < 1 || call_vox < 0 || !(lambda1 >= 0.0) || !(lambda2 >= 0.0)) return AMX_E_BADARG;
+    amx_ctx defaults;      // (holds the switches only: nothing in here touches the device)
+    for (const amx_switch &w : kSwitches) set_switch(&defaults, w, nullptr);      // (no environment here: every switch at the table's default)
+    const int n_atoms = n_wm + 1 + (is_exvivo ? 1 : 0);
+    const amx::NoddiShape sh{nS, (n_atoms & 1) ? n_atoms : n_atoms + 1, n_atoms, n_wm, n_dwi, ndirs, is_exvivo ? 1 : 0, is_exvivo ? 0 : 1, amx::noddi_tables(n_atoms, n_wm)};
+    const amx::NoddiRoute r = amx::noddi_route(sh, {n_vox, call_vox > n_vox ? call_vox : n_vox, lambda1, lambda2}, noddi_switches(&defaults));
+    const int64_t words[] = {r.seeds, r.global, r.gemm_ks, r.gemm_n_pass, r.gemm_win, r.gcert, r.repair, r.rescue, r.tile_in_lds, r.seeds2, r.gcert2, r.wide, r.third,
+                             r.min_items, r.seed2_max_atoms, r.seed2_trip_add, r.left2_second_half, r.left2_count, r.seed_occ2, r.seed2_occ2, r.seed_chunk,
+                             r.seed_waves, r.seed1_waves, r.seed2_waves, r.s1.build, r.s2.build, r.s2.gram, r.s3.build, r.n_launch};
+    static_assert(sizeof words / sizeof words[0] + 3 * (sizeof r.launch / sizeof r.launch[0]) <= AMX_ROUTE_WORDS, "amx_noddi_route: out[] too short");
+    int k = 0;
+    for (int64_t w : words) out[k++] = w;
+    std::string p;
+    for (int l = 0; l < r.n_launch; l++) {
+        p += (l ? " -> " : ""); p += r.launch[l].note;
+        out[k++] = r.launch[l].waves; out[k++] = (int64_t)r.launch[l].lds; out[k++] = (int64_t)r.launch[l].lds_list;
+    }
+    snprintf(path, (size_t)cap, "%s", p.c_str());
     return AMX_OK;
 }
 

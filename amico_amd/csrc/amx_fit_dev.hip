@@ -73,11 +73,10 @@ int fit_close(amx_ctx *ctx, const FitCall &c, int rc, bool fold = true)
 struct NoddiChain {
     amx_ctx *ctx; const amx_lut *lut; int64_t n; hipStream_t s;
     Plan pl; NoddiArgs a;
-    bool seeds = false;            // the seed -> certificate chain runs (a dictionary with a basis, a call of at least AMX_SEED_MIN_VOXELS)
-    int gemm_ks = 0;               // 0: no table kernels for this shape (seeds certified on the true residual only)
+    NoddiRoute rt;                 // every choice of kernel build of this fit (amx_noddi_route.hpp), made once in noddi_fit_dev
     // AMX_FORK (a recorded negative result, kSwitches): the side stream and its events, what went there
     hipStream_t fs = nullptr; hipEvent_t *fev = nullptr;
-    bool fork1 = false, joined1 = false, fork2 = false;
+    bool joined1 = false;
     int late_rc = AMX_OK;          // of the LASSO stage's own launch: the epilogue still runs behind it, as it always has
 };
 
@@ -131,24 +130,24 @@ int fork_join(NoddiChain &q, int ev)
 // NNLS on all atoms: x_iso (and x_dot)
 int noddi_stage1(NoddiChain &q)
 {
-    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; int rc;
-    if (q.seeds) {
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; const NoddiRoute &rt = q.rt; int rc;
+    if (rt.seeds) {
         ctx->seeded_vox += q.n;
         // y~ = U'y once; the seed solver proposes the stage's support, the stage kernel certifies it (amx_seed.hpp)
         rec(ctx, 10, s);
-        const bool gcert = !ctx->opt_no_gcert && q.gemm_ks > 0;
-        if (gcert && (rc = amx_launch_noddi_gemm(ctx, lut, a, pl, s, false))) return rc;
-        if (!gcert && (rc = amx_launch_noddi_project(ctx, lut, a, pl, s))) return rc;      // (the GEMM writes y~ as well)
+        const bool gcert = rt.gcert;
+        if (gcert && (rc = amx_launch_noddi_gemm(ctx, lut, a, pl, s, rt, false))) return rc;
+        if (!gcert && (rc = amx_launch_noddi_project(ctx, lut, a, pl, s, rt))) return rc;      // (the GEMM writes y~ as well)
         if (!ctx->opt_no_screen) { a.scr_S = lut->screen_S; a.scr_kappa = lut->screen_kappa; a.scr_ytil = (const double *)ctx->ytil.p; a.scr_Sg = lut->basis_S; }
-        if (ctx->opt_seed_stages & 1) {
+        if (rt.seed1) {
             a.seeds = (const unsigned long long *)ctx->seeds.p;
             rec(ctx, 16, s);
-            if ((rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, 1))) return rc;
+            if ((rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, rt, 1))) return rc;
             rec(ctx, 17, s);
             if (!gcert) ctx->uncert_vox[0] += q.n;
             if (gcert) {
                 size_t off = 0; const int *cnt = nullptr;
-                if ((rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, 1, &off, &cnt))) return rc;
+                if ((rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, rt, 1, &off, &cnt))) return rc;
                 walk_leftovers(q, (const int *)ctx->rlist.p + off, cnt, ctx->opt_no_hard_first ? nullptr : (const unsigned char *)ctx->done.p);
             }
         }
@@ -156,11 +155,10 @@ int noddi_stage1(NoddiChain &q)
     }
     // AMX_FORK bit 0 (TIMING PROBE, not a fit): the stage-1 left-over kernel on the side stream beside the LASSO seed solver, which reads
     // the x_iso the previous call left for those voxels; joined before the LASSO certificates
-    q.fork1 = (ctx->opt_fork & 1) && a.rlist != nullptr;
     if (ctx->opt_fork && (rc = fork_ready(q))) return rc;
     q.fev = ctx->fork_ev[ctx->work_idx];
-    if (q.fork1) rc = fork_side(q, 0, [&](hipStream_t side) { return amx_launch_noddi_s1(ctx, a, pl, side); });
-    else rc = amx_launch_noddi_s1(ctx, a, pl, s);
+    if (rt.fork1) rc = fork_side(q, 0, [&](hipStream_t side) { return amx_launch_noddi_s1(ctx, a, pl, side, rt.s1); });
+    else rc = amx_launch_noddi_s1(ctx, a, pl, s, rt.s1);
     if (rc) return rc;
     progress_tick(ctx, s, q.n / 3, q.n);                       // (three stages: a third of the work each, roughly)
     walk_all(q);
@@ -170,45 +168,39 @@ int noddi_stage1(NoddiChain &q)
 // LASSO on the white-matter atoms: the support
 int noddi_stage2(NoddiChain &q)
 {
-    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s;
-    const double lambda1 = a.c.lam1, lambda2 = a.c.lam2; int rc;
-    // the LASSO seeds need x_iso: Gram-space solver only (lambda2 >= 1e-5), with the default dictionary shape
-    if (q.seeds && (ctx->opt_seed_stages & 4) && lut->basis2_S != nullptr && lambda2 >= 1e-5 && (q.gemm_ks > 0 || lut->nS <= 128) &&
-        (lambda1 > 0.0 || ctx->opt_no_big_all || lut->n_wm <= 64)) {       // (lambda1 = 0: a dense optimum -- no seeds to propose, amx_launch_noddi_s2 goes to k_noddi_lasso_big)
-        const bool gcert2 = !ctx->opt_no_gcert && q.gemm_ks > 0 && lut->screen2_kappa0 != nullptr && lut->u2iso != nullptr;
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; const NoddiRoute &rt = q.rt; int rc;
+    if (rt.seeds2) {       // (the LASSO seeds need x_iso: Gram-space solver only)
+        const bool gcert2 = rt.gcert2;
         rec(ctx, 12, s);
         // y2~ of every voxel and c2 = A2'y2, ||y2||^2 of the unclipped ones derive from the stage-1 table; the clipped voxels' exactly
-        if (gcert2 && (rc = amx_launch_noddi_s2prep(ctx, lut, a, pl, s))) return rc;
+        if (gcert2 && (rc = amx_launch_noddi_s2prep(ctx, lut, a, pl, s, rt))) return rc;
         rec(ctx, 18, s);
-        if ((rc = amx_launch_noddi_seed2(ctx, lut, a, pl, s, gcert2))) return rc;
+        if ((rc = amx_launch_noddi_seed2(ctx, lut, a, pl, s, rt))) return rc;
         rec(ctx, 19, s);
         a.seeds2 = (const unsigned long long *)ctx->seeds2.p;
         a.list_is_pos = 1;
         if (!ctx->opt_no_screen && lut->screen2_S) { a.scr2_S = lut->screen2_S; a.scr2_kappa = lut->screen2_kappa; a.scr2_ytil = (const double *)ctx->ytil2.p; a.scr2_Sg = lut->basis2_S; }
         if (!gcert2) ctx->uncert_vox[1] += q.n;
-        if (q.fork1) { if ((rc = fork_join(q, 0))) return rc; q.joined1 = true; }
+        if (rt.fork1) { if ((rc = fork_join(q, 0))) return rc; q.joined1 = true; }
         if (gcert2) {
-            const bool wide = !ctx->opt_no_gcert_wide;
-            if ((rc = amx_launch_noddi_gcert2(ctx, lut, a, pl, s, wide))) return rc;
+            if ((rc = amx_launch_noddi_gcert2(ctx, lut, a, pl, s, rt))) return rc;
             a.cand_lists = 1;       // (k_lasso_gcert: the candidate lists of stage 3 wait in seeds2 for the voxels it settled)
-            const bool third = amx_gcert2_third(ctx, lut, wide);
-            walk_leftovers(q, (const int *)ctx->rlist.p + amx_gcert2_leftover_offset(pl, wide, third), amx_gcert2_leftover_counts(pl, wide, third), nullptr);   // (two wide passes end in the first half again)
+            walk_leftovers(q, (const int *)ctx->rlist.p + (rt.left2_second_half ? amx_rlist_half(pl) : 0), pl.zcount(rt.left2_count), nullptr);
             // AMX_FORK bit 1: the voxels these certificates left over (0.6 %) do not come back to the lane kernels -- k_noddi<4> and then
             // k_noddi<3> (no seed: Lawson-Hanson on the support it has just found, plus iso) finish them, a wavefront per voxel, on the side
-            // stream, while k_nnls_seed<3> / k_nnls_gcert<3> work on everybody else (they skip the voxels whose certificate flag is not 1)
-            q.fork2 = (ctx->opt_fork & 2) && (ctx->opt_seed_stages & 2) && !ctx->opt_no_gcert && q.gemm_ks > 0;
+            // stream, while k_nnls_seed<3> / k_nnls_gcert<3> work on everybody else (they skip the voxels whose certificate flag is not 1): rt.fork2
         }
         rec(ctx, 13, s);
     }
-    if (q.fork1 && !q.joined1 && (rc = fork_join(q, 0))) return rc;
-    if (!q.fork2) { q.late_rc = amx_launch_noddi_s2(ctx, a, pl, s); return AMX_OK; }
+    if (rt.fork1 && !q.joined1 && (rc = fork_join(q, 0))) return rc;
+    if (!rt.fork2) { q.late_rc = amx_launch_noddi_s2(ctx, a, pl, s, rt.s2); return AMX_OK; }
     rc = fork_side(q, 2, [&](hipStream_t side) {
         NoddiArgs b = a;
-        int r = amx_launch_noddi_s2(ctx, b, pl, side);
+        int r = amx_launch_noddi_s2(ctx, b, pl, side, rt.s2);
         if (r) return r;
         b = a;      // (same left-over lists, same chunks: now stage 3 without seeds)
         b.seeds = nullptr; b.done = nullptr; b.seeds2 = nullptr; b.cand_lists = 0;
-        return amx_launch_noddi_s3(ctx, b, pl, side);
+        return amx_launch_noddi_s3(ctx, b, pl, side, rt.s3_fork);
     });
     if (!rc) a.fork_l2 = 1;
     return rc;
@@ -217,33 +209,32 @@ int noddi_stage2(NoddiChain &q)
 // NNLS on the support + iso: the maps
 int noddi_stage3(NoddiChain &q)
 {
-    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; int rc = AMX_OK;
+    amx_ctx *ctx = q.ctx; const amx_lut *lut = q.lut; NoddiArgs &a = q.a; const Plan &pl = q.pl; hipStream_t s = q.s; const NoddiRoute &rt = q.rt; int rc = AMX_OK;
     progress_tick(ctx, s, 2 * (q.n / 3), q.n);
     a.seeds = nullptr;
     walk_all(q);
-    if (q.seeds && (ctx->opt_seed_stages & 2)) {
+    if (rt.seed3) {
         a.seeds = (const unsigned long long *)ctx->seeds.p;
         rec(ctx, 14, s);
-        rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, 3);
-        const bool gcert3 = !ctx->opt_no_gcert && q.gemm_ks > 0;
+        rc = amx_launch_noddi_seed(ctx, lut, a, pl, s, rt, 3);
+        const bool gcert3 = rt.gcert;
         if (!gcert3) ctx->uncert_vox[2] += q.n;
         if (!rc && gcert3) {
             size_t off = 0; const int *cnt = nullptr;
-            rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, 3, &off, &cnt);
+            rc = amx_launch_noddi_gcert(ctx, lut, a, pl, s, rt, 3, &off, &cnt);
             walk_leftovers(q, (const int *)ctx->rlist.p + off, cnt, ctx->opt_no_hard_first ? nullptr : (const unsigned char *)ctx->done.p);
         }
         rec(ctx, 15, s);
     }
-    return rc ? rc : amx_launch_noddi_s3(ctx, a, pl, s);
+    return rc ? rc : amx_launch_noddi_s3(ctx, a, pl, s, rt.s3);
 }
 
 int noddi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
 {
     const amx_lut *lut = c.lut; int rc;
     NoddiChain q{ctx, lut, c.n, c.stream};
-    q.seeds = lut->basis_S != nullptr && lut->gram != nullptr && !ctx->opt_no_seed && ctx->call_vox >= ctx->opt_seed_min_voxels;
-    q.gemm_ks = q.seeds ? amx_gemm_ksteps(lut) : 0;
-    if ((rc = make_plan(ctx, c.n, lut->ndirs, q.pl, q.seeds, gemm_rows(lut->n_atoms)))) return rc;
+    q.rt = noddi_route(noddi_shape(lut), {c.n, ctx->call_vox, c.lam1, c.lam2}, noddi_switches(ctx));      // (fit_check has set ctx->call_vox)
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, q.pl, q.rt.seeds ? &q.rt : nullptr, gemm_rows(lut->n_atoms)))) return rc;
     if ((rc = amx_ensure(ctx, ctx->xiso, (size_t)c.n * 2 * sizeof(double)))) return rc;
     if ((rc = amx_ensure(ctx, ctx->supp, (size_t)c.n * 4 * sizeof(unsigned long long)))) return rc;
     // (every voxel's maps are written by the kernel that settles its stage 3 -- tests/test_gpu_parity.py::test_noddi_fit_writes_every_voxel)
@@ -257,7 +248,7 @@ int noddi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     // the launch of the LASSO stage's own kernels on the main stream reports through late_rc: behind it the counters still fold and the call's
     // event pair still ends (fit_close), so a profiled or polled call sees a finished call and the error, as it always has
     rc = q.late_rc ? q.late_rc : noddi_stage3(q);
-    if (q.fork2) { const int rj = fork_join(q, 2); if (rj) return rj; }      // the side stream's voxels are part of this fit
+    if (q.rt.fork2) { const int rj = fork_join(q, 2); if (rj) return rj; }      // the side stream's voxels are part of this fit
     return fit_close(ctx, c, rc);
 }
 
@@ -312,7 +303,7 @@ int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     // the default problem (strong ridge, <= 32 atoms, maps only): complementary form, one voxel per lane (amx_czb.hip)
     const bool fast = lut->n_atoms <= 32 && c.lam2 >= 1e-2 && !(c.flags & (AMX_F_RMSE | AMX_F_NRMSE)) &&
                       !ctx->opt_wave_per_voxel && lut->nS <= 160 && lut->gram != nullptr;
-    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl, false, 64, fast ? 2048 : 0))) return rc;
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl, nullptr, 64, fast ? 2048 : 0))) return rc;
     CzbArgs a;
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;
     a.n_rs = lut->n_rs; a.n_perp = lut->n_perp; a.Rs = lut->Rs; a.gram = lut->gram; a.ldG = lut->ldG;

@@ -2,6 +2,7 @@
 #pragma once
 #include "../../include/amico_amd.h"
 #include "amx_kernels.hpp"
+#include "amx_noddi_route.hpp"
 #include "amx_stage.hpp"
 #include <climits>
 #include <cstdio>
@@ -146,9 +147,9 @@ inline constexpr amx_switch kSwitches[] = {
     // (never below kChunk: the left-over passes size their grid by the FIRST plan's chunk count, n / kChunk + ndirs + 1.  Lanes refill from the
     //  chunk: the more voxels per lane, the smaller the share of the tail; 1 M voxels: 1024 -> 7.2 ms, 2048 -> 7.3, 4096 -> 5.5 for stage 1)
     sw_int("AMX_SEED_CHUNK", &amx_ctx::opt_seed_chunk, 0, [](long long v, long long d) { return v >= kChunk ? ((v + 63) & ~63LL) : d; },
-           "voxels of one orientation per workgroup of the seed solvers (at least 256, rounded up to a multiple of 64; 0 = by the call's size, make_plan)"),
+           "voxels of one orientation per workgroup of the seed solvers (at least 256, rounded up to a multiple of 64; 0 = by the call's size, noddi_route)"),
     sw_int("AMX_SEED_WAVES", &amx_ctx::opt_seed_waves, 0, [](long long v, long long) { return (v == 1 || v == 2 || v == 4) ? v : 0; },
-           "wavefronts per workgroup of the lane kernels: 1, 2 or 4 (0 = by the number of chunks, make_plan)"),
+           "wavefronts per workgroup of the lane kernels: 1, 2 or 4 (0 = by the number of chunks, noddi_route)"),
     // (the seeded chain of ~16 kernels has a floor of ~1.5 ms; measured, tools/r04/round8.sh: 20 000 voxels 1.58 against 1.49 ms, 25 000 voxels 1.60 against 1.78, 40 000 1.70 against 2.34)
     sw_int("AMX_SEED_MIN_VOXELS", &amx_ctx::opt_seed_min_voxels, 22528, sw_any, "smaller calls run the wavefront-per-voxel kernels on all voxels"),
     // (a third more time per trip, twice the wavefronts: wins when the kernel is throughput bound -- 1 M voxels 2.80 -> 2.14 ms --, loses when the longest voxel's path bounds it:
@@ -206,15 +207,13 @@ inline constexpr amx_switch kSwitches[] = {
     sw_flag("AMX_DEBUG", &amx_ctx::opt_debug, "synchronise after every launch and trace progress and counters on stderr"),
 };
 
-// defaults of switches that were retired with nothing setting them (the measurements stay):
-// calls of fewer voxels run the left-over kernels of stage 1 / stage 3 in their small-call builds (float32 tile, 4 wavefronts, two workgroups per CU:
-// amx_noddi_s1.hip).  Measured (tools/r06/a05.sh; 50 000 / 100 000 / 200 000 / 300 000 / 500 000 / 1 M voxels, fit in ms, round-5 builds 1.441 / 1.817 /
-// 2.386 / 2.885 / 4.000 / 6.421): stage 1 alone 1.421 / 1.793 / 2.394 / 2.921 / 4.072 / 6.591; stage 3 alone 1.415 / 1.797 / 2.371 / 2.849 / 3.989 / 6.506
-// (its 12-wavefront build spills 117 registers, this one none); the LASSO stage's (two wavefronts, no screening table) lost at every size (1.460 / 1.905 /
-// 2.511 / ...) and is gone.  The gain is ~20 us per kernel, not the ~100 the "one round of workgroups instead of two" arithmetic promised: a left-over
-// kernel lasts as long as its longest voxel's Lawson-Hanson, whatever the rounds.
-constexpr long long kLeftSmall1 = 150000, kLeftSmall3 = 600000;
-constexpr long long kRescueFrom = 2000000;   // voxels from which the NNLS certificates run their rescue pass (amx_launch_noddi_gcert; AMX_RESCUE_FROM)
+// (defaults of switches that were retired with nothing setting them -- kLeftSmall1, kLeftSmall3 -- and kRescueFrom: amx_noddi_route.hpp, with their measurements)
+// the switches that steer a NODDI fit's route, as noddi_route() takes them
+inline amx::NoddiSwitches noddi_switches(const amx_ctx *c)
+{
+    return {c->opt_no_seed, c->opt_no_gcert, c->opt_no_gcert_wide, c->opt_no_screen, c->opt_no_big_all, c->opt_seed_stages, c->opt_seed_chunk, c->opt_seed_waves,
+            c->opt_seed_min_voxels, c->opt_seed_occ2_from, c->opt_seed2_occ2_from, c->opt_rescue_from, c->opt_gcert_repair, c->opt_gcert2_third, c->opt_fork};
+}
 
 constexpr int kDictModel = 100;   // amx_dict::model
 
@@ -378,7 +377,7 @@ struct Plan {
     static constexpr int kFeedSetsN = 7;
 };
 enum { FEED_SEED1 = 0, FEED_SEED2, FEED_SEED3, FEED_GEMM, FEED_CERT1, FEED_CERT2, FEED_CERT3, kFeedSets };
-enum { ZC_CERT1 = 0, ZC_RESC1, ZC_CLIP, ZC_CERT2, ZC_CERT2W, ZC_CERT2W3, ZC_CERT3, ZC_RESC3, ZC_CERT2Q, kZCounts };   // ZC_CERT2Q: per chunk, what the second LASSO certificate pass leaves that a third could settle
+// (ZC_*, the arrays of Plan::zcount: amx_noddi_route.hpp)
 static_assert(kFeedSets == Plan::kFeedSetsN, "Plan::zcount sits behind the feed sets");
 
 // AMX_DEBUG=1: synchronise after every launch and trace progress on stderr
@@ -399,23 +398,24 @@ static inline void rec(amx_ctx *ctx, int k, hipStream_t s)
 
 // defined in the per-model launch units (amx_noddi.hip, amx_fw.hip, amx_sandi.hip)
 int amx_build_basis(amx_ctx *ctx, amx_lut *lut);
-int amx_launch_noddi_project(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_noddi_seed(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, int stage);
-int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, int stage, size_t *list_off, const int **count_out);
-int amx_launch_noddi_gemm(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, bool lasso);
-int amx_launch_noddi_s2prep(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s);
-int amx_gemm_ksteps(const amx_lut *lut);   // K-steps of the table kernels for this dictionary (25 / 40), 0 = shape not supported
-int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, bool wide);
-bool amx_gcert2_third(const amx_ctx *ctx, const amx_lut *lut, bool wide);
-int amx_gcert2_third_min_items(const amx_ctx *ctx, const amx_lut *lut);   // list entries a chunk must hold for that pass to work on it (amx_seed.hip)
-size_t amx_gcert2_leftover_offset(const Plan &pl, bool wide, bool third);      // which half of ctx->rlist the LASSO certificate passes end in (amx_seed.hip)
-const int *amx_gcert2_leftover_counts(const Plan &pl, bool wide, bool third);  // ... and the per-chunk counts of those lists (Plan::zcount)
+// the NODDI launchers follow the fit's route (amx_noddi_route.hpp: noddi_fit_dev computes it once); none decides anything itself
+inline amx::NoddiShape noddi_shape(const amx_lut *l)
+{
+    return {l->nS, l->ldA, l->n_atoms, l->n_wm, l->n_dwi, l->ndirs, l->is_exvivo, l->s2_derive,
+            {l->basis_S != nullptr, l->gram != nullptr, l->gram_dwi != nullptr, l->basis2_S != nullptr, l->screen2_S != nullptr && l->screen2_kappa0 != nullptr && l->u2iso != nullptr}};
+}
+int amx_launch_noddi_project(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt);
+int amx_launch_noddi_seed(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt, int stage);
+int amx_launch_noddi_gcert(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt, int stage, size_t *list_off, const int **count_out);
+int amx_launch_noddi_gemm(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt, bool lasso);
+int amx_launch_noddi_s2prep(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt);
+int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt);
 static inline size_t amx_rlist_half(const Plan &pl) { return (size_t)pl.n + pl.max_schunks + 64; }   // ints per left-over list + counts
-int amx_launch_noddi_seed2(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, bool have_ytil2);
+int amx_launch_noddi_seed2(amx_ctx *ctx, const amx_lut *lut, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiRoute &rt);
 int amx_launch_noddi_big(amx_ctx *ctx, const amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const int *list, const int *count, int n_all);   // amx_big.hip: LASSO stage, any support size
-int amx_launch_noddi_s1(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_noddi_s2(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_noddi_s3(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s);
+int amx_launch_noddi_s1(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
+int amx_launch_noddi_s2(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
+int amx_launch_noddi_s3(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
 int amx_launch_fw(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);
 int amx_launch_sandi(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
 int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
@@ -520,7 +520,7 @@ inline void fill_common(amx::FitCommon &c, const void *tiles, const double *y, c
 }
 
 // amx_plan.hip: the per-call plan and the small launches around the solvers
-int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, bool seeds = false, int table_rows = 0, int blocks_chunk = 0);
+int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, const amx::NoddiRoute *seeds = nullptr, int table_rows = 0, int blocks_chunk = 0);   // seeds: a NODDI fit on the seeded chain, its route
 int enqueue_bucketing(amx_ctx *ctx, const amx_lut *lut, const double *d_dirs, int64_t n, Plan &pl, hipStream_t s, int chunk = kChunk,
                       double *zero_rows = nullptr, int zero_cols = 0, double *zero_rows2 = nullptr, int zero_cols2 = 0);
 int enqueue_index_bucketing(amx_ctx *ctx, const int32_t *d_idx, int n_dicts, int64_t n, Plan &pl, hipStream_t s);   // the batched solvers' plan

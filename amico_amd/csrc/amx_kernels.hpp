@@ -16,12 +16,7 @@
 namespace amx {
 
 struct Chunk { int dir, start, count, pad; };
-constexpr int kSeedKD = 12;      // compressed dimensions of the support-seed problem (amx_seed.hpp)
-// rows of a block of the A'y table (k_noddi_gemm, amx_seed.hpp): atoms 0 .. n_atoms - 1, then from aux0 = n_atoms: U'y (12), U2'y (12),
-// sum_b0 y, ||y||^2, sum_b0 y^2, t_min = min_dwi y_i / iso_i; padded to whole 16-row MFMA tiles
-constexpr int kAuxU = 0, kAuxU2 = 12, kAuxB0 = 24, kAuxYY = 25, kAuxYB = 26, kAuxTmin = 27, kAuxN = 28;
-__host__ __device__ constexpr int gemm_rows(int n_atoms) { return ((n_atoms + kAuxN + 15) / 16) * 16; }
-constexpr int kScreenLd = 192;   // atoms per row of the float32 screening table [KD][kScreenLd]
+// (kSeedKD, kAux*, gemm_rows, kScreenLd, solver_lds_words, fit_lds_bytes: amx_sizes.hpp)
 
 enum StatusSlot { ST_ERRVOX = 0, ST_II1 = 1, ST_II2 = 2, ST_OVERFLOW = 3, ST_ITCAP = 4, ST_RERUN = 5, ST_GUARD = 6, ST_GUARDVOX = 7, ST_EXACT = 8, ST_GRAM = 11, ST_ITERS = 14, ST_SEED = 17, ST_LEFT = 92, ST_CLIP = 95, ST_ERRPACK = 96, ST_ERRKIND = 98, ST_DENSE = 100, ST_WORDS = 102 };   // ST_LEFT + 0..2: voxels the Gram-space certificates of stage 1 / LASSO / stage 3 left to the wavefront-per-voxel kernels; ST_CLIP: voxels whose stage-2 signal was clipped; ST_ERRPACK (two words, 8-byte aligned): first offending voxel << 32 | what it held, ONE 64-bit atomicMin (amx_sync_status decodes it into ST_ERRVOX / ST_II1 / ST_II2 of the host mirror); ST_ERRKIND: 1 = the payload is a dictionary index of the batched solvers; ST_DENSE + 0, 1: voxels k_batched_big solved and the pivoting steps it took (amx_batched_last_dense)
 
@@ -629,14 +624,6 @@ __device__ __forceinline__ void czb_voxel(const CzbArgs &a, const float *As, dou
     }   // ok
 }
 
-// doubles of per-wavefront LDS the solver needs besides the residual scratch:
-// QR solver: R and the ridge rows, (MAXP+1)^2 each; Gram solver: two packed triangles
-// (without the ridge the QR solver has no augmented rows: R only)
-__host__ __device__ constexpr int solver_lds_words(bool gram, int maxp, bool ridge = true)
-{
-    return gram ? (maxp + 1) * (maxp + 2) : (ridge ? 2 : 1) * (maxp + 1) * (maxp + 1);
-}
-
 // XCD-aware block -> chunk map.  Workgroup b runs on XCD b % 8 (observed dispatch order; only a
 // speed assumption).  The chunk list is sorted by orientation, so XCD x takes the x-th CONTIGUOUS
 // eighth of it: the dictionary tile and the Gram columns of one orientation are then fetched into
@@ -976,18 +963,6 @@ __global__ void __launch_bounds__(NW * 64) k_batched(const BatchedArgs a)
             }
         }
     }
-}
-
-template <typename AT>
-static inline size_t fit_lds_bytes(int nS, int ldA, int NR, int NQ, int NW, int MAXP, bool gram = false, bool ridge = true, bool global_tile = false)
-{
-    const size_t words_pad = global_tile ? 0 : (((size_t)nS * ldA + kWave * NQ + 3) & ~(size_t)3);
-    size_t b = (words_pad * sizeof(AT) + 15) & ~(size_t)15;
-    b += (size_t)NW * NR * kWave * sizeof(double);
-    b += (size_t)NW * solver_lds_words(gram, MAXP, ridge) * sizeof(double);
-    b += (size_t)NW * 4 * sizeof(unsigned long long);
-    b += 16;
-    return b;
 }
 
 }  // namespace amx

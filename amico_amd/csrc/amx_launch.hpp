@@ -22,17 +22,14 @@ static int launch_lds(amx_ctx *ctx, K kern, dim3 grid, dim3 block, size_t lds, h
 }
 
 // main pass over the orientation chunks + re-run of the voxels whose passive set overflowed
-constexpr size_t kLdsPerCU = 160 * 1024;
+using amx::kLdsPerCU;
 
-// NODDI wavefront-per-voxel kernels: does this shape run the global-tile variants (amx_kernels.hpp: GT)?  The LDS variants hold
-// <= 256 rows (4 per lane), <= 192 atoms (3 per lane) and need the float32 tile + the blocks of at least two wavefronts in LDS
-// (the widest: the LASSO stage's Gram solver with 32 passive atoms; the re-run kernels with 64)
-static inline bool amx_noddi_tile_global(int nS, int ldA, int n_atoms)
+// launch_pair's LDSF for a NODDI stage kernel, whose wavefront count and LDS the route has fixed.  launch_pair halves nw while LDSF(nw) does
+// not fit: this one REPORTS every count above the route's as too large (kLdsPerCU + 1, not a real size), so that the loop stops at the
+// route's count with the route's LDS; a route that does not fit is still refused by launch_pair's own check.
+static inline auto route_lds(const amx::NoddiKernel &k)
 {
-    if (nS > 256 || n_atoms > 192) return true;
-    const int NR = nS <= 128 ? 2 : 4;
-    return amx::fit_lds_bytes<float>(nS, ldA, NR, 3, 2, 32, true) + (size_t)amx::kSeedKD * amx::kScreenLd * sizeof(float) > kLdsPerCU ||
-           amx::fit_lds_bytes<float>(nS, ldA, NR, 3, 1, 64, true) > kLdsPerCU;
+    return [waves = k.waves, lds = k.lds](int nw) { return nw > waves ? kLdsPerCU + 1 : lds; };
 }
 
 // LDSF(nw) -> dynamic LDS bytes of the main kernel with nw wavefronts per workgroup

@@ -5,30 +5,16 @@
 
 using namespace amx;
 
-int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, bool seeds, int table_rows, int blocks_chunk)
+int make_plan(amx_ctx *ctx, int64_t n, int ndirs, Plan &pl, const NoddiRoute *seeds, int table_rows, int blocks_chunk)
 {
     int rc;
     const int max_chunks = (int)(n / kChunk) + ndirs + 1;
     pl.n = (size_t)n;
     if (seeds) {
-        // Chunk of the second plan: whole orientations wherever possible (a lane then walks many voxels and the tail of the chunk
-        // is a small share), i.e. about twice the mean population -- 4 M voxels, ndirs 500: 4096 -> 103 M voxels/s (every
-        // orientation cut in two or three), 8192 -> 83 M, 16384 -> 123 M; never below 4096 (1 M voxels: 2048 -> 72 M, 4096 -> 99 M).
-        int sc = ctx->opt_seed_chunk;
-        if (sc <= 0) {
-            const long long want = 2 * (long long)n / (ndirs > 512 ? ndirs : 512);
-            sc = (int)(want < 4096 ? 4096 : (want > 65536 ? 65536 : ((want + 63) & ~63LL)));
-        }
-        pl.seed_chunk = sc;
-        pl.max_schunks = (int)(n / sc) + ndirs + 1;
-        pl.seed_waves = ctx->opt_seed_waves ? ctx->opt_seed_waves : 4;
-        // (measured, ndirs = 500: 100 000 / 200 000 / 400 000 / 1 M voxels -> stage-1 group 1.11 / 1.55 / 2.31 / 4.66 ms with two
-        //  wavefronts per workgroup against 1.33 / 1.80 / 2.39 / 4.14 ms with four; every other lane kernel is best with four)
-        pl.seed1_waves = ctx->opt_seed_waves ? ctx->opt_seed_waves : ((double)n / (double)pl.max_schunks < 640.0 ? 2 : 4);
-        pl.seed_occ2 = ctx->call_vox >= ctx->opt_seed_occ2_from;      // (batches of one host call all take the same build)
-        pl.seed2_occ2 = ctx->call_vox >= ctx->opt_seed2_occ2_from;
-        pl.seed2_waves = pl.seed1_waves;
-        if (!ctx->opt_seed_waves) { if (pl.seed_occ2) pl.seed1_waves = 4; if (pl.seed2_occ2) pl.seed2_waves = 4; }
+        // the second plan: its chunk, the wavefronts and builds of the lane kernels are the route's (amx_noddi_route.hpp)
+        pl.seed_chunk = seeds->seed_chunk; pl.max_schunks = seeds->max_schunks;
+        pl.seed_waves = seeds->seed_waves; pl.seed1_waves = seeds->seed1_waves; pl.seed2_waves = seeds->seed2_waves;
+        pl.seed_occ2 = seeds->seed_occ2; pl.seed2_occ2 = seeds->seed2_occ2;
         if ((rc = amx_ensure(ctx, ctx->schunks, (size_t)pl.max_schunks * sizeof(Chunk)))) return rc;
         if ((rc = amx_ensure(ctx, ctx->ytil, (size_t)n * amx::kSeedKD * sizeof(double)))) return rc;
         if ((rc = amx_ensure(ctx, ctx->seeds, (size_t)n * sizeof(unsigned long long)))) return rc;

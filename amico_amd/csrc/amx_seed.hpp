@@ -25,7 +25,7 @@
 namespace amx {
 
 constexpr int kSeedMax = 8;      // passive-set capacity of the seed solver (= MAXP of the NNLS stage kernels)
-constexpr int kSeed3ListRow = 36;      // bytes per lane of the stage-3 candidate lists in LDS (k_nnls_seed<3>)
+// (kSeed3ListRow, kSeedLd, kSeed2KD -- what sizes a launch's LDS: amx_noddi_route.hpp)
 constexpr int kSeed3ScanMax = 32;      // (diagnosis: a smaller value truncates the stage-3 candidate scan)
 // one column of S for THIS lane from the LDS copy (row stride kSeedLd doubles = 112 bytes: 16-byte aligned rows): 16-byte reads --
 // the per-lane gathers are bound by the NUMBER of LDS instructions (a float32 copy with half the bytes changed nothing, reads of
@@ -95,7 +95,6 @@ __device__ __forceinline__ void seed_col(const double *col, double (&cv)[KD])
 #pragma unroll
     for (int d = 0; d < KD; d += 2) { const double2 p = c2[d >> 1]; cv[d] = p.x; cv[d + 1] = p.y; }
 }
-constexpr int kSeedLd = 14;      // LDS row stride of S (odd: per-lane column gathers spread over the banks)
 constexpr unsigned long long kNoSeed = kSeedNone;
 // round 6 (AMX_FORK bit 1): a voxel the LASSO certificates left over is finished on a SIDE stream (k_noddi<4> -> k_noddi<3>, a wavefront per
 // voxel) while the stage-3 lane kernels run: k_nnls_seed<3> marks it so, k_nnls_gcert<3> neither certifies it nor lists it
@@ -2401,7 +2400,6 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
 // with t_j <= 0 leaves and up to four candidates enter (the best four of eight maxima the scan keeps in registers), M and g take
 // the changes additively, and one Cholesky factorisation and solve give the next r.  Greedy, no step back -- it is a proposal,
 // certified afterwards by k_lasso_gcert in the full problem.
-constexpr int kSeed2KD = 8;       // components the LASSO seed solver works with (the first 8 of the 12 stored: the pivoted basis is nested)
 constexpr int kSeed2Ld = kSeedKD; // stride of U2 / S2 / y2~ rows
 struct Seed2Args {
     const double *y;              // [n_vox][nS]

@@ -28,10 +28,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "amx_sizes.hpp"      // kWave and the sizes kernels and launchers share (plain arithmetic)
 
 namespace amx {
-
-constexpr int kWave = 64;
 
 // -DAMX_PHASES: wall-clock split of solve() by phase (s_memtime), accumulated per wavefront (diagnosis builds only)
 #ifdef AMX_PHASES

@@ -443,6 +443,16 @@ int amx_prep_gather_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
  * identity and the image not interleaved; inplace: no group reads a volume an earlier output replaced, or overwrite_in_order.
  * (Grouped outputs on a planar image whose groups read no earlier output take the streaming kernels, which hold no tile.)          */
 int amx_prep_route(int nS, int n_out, int n_b0, int n_gidx, int identity, int direct, int inplace, int64_t out[4]);
+/* The same for the NODDI fit: which kernels a fit of n_vox voxels (a batch of a call of call_vox voxels; 0: the call itself) launches on a
+ * dictionary of this shape, as amx_lut_upload_noddi builds it, with every switch at its default -- without a device or a context.  path: the
+ * launches in the format of amx_last_path.  out: seeds, global tile, gemm K-steps, gemm passes, gemm window, gcert, repair, rescue, rescue tile
+ * in LDS, seeds2, gcert2, wide, third, third-pass min_items, seed-2 max_atoms, seed-2 trip-cap increment, LASSO left-overs in the second half,
+ * their count array, seed occ2, seed-2 occ2, seed chunk, wavefronts of the lane kernels / of k_nnls_seed<1> / of k_lasso_seed, build of the
+ * stage-1 / stage-2 kernel (NoddiBuild, csrc/amx_noddi_route.hpp), stage 2 in Gram space, build of the stage-3 kernel, number of launches;
+ * then per launch {wavefronts per workgroup, LDS bytes, LDS bytes of its re-run pass}.                                                      */
+#define AMX_ROUTE_WORDS 96
+int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64_t n_vox, int64_t call_vox, double lambda1, double lambda2,
+                    char *path, int cap, int64_t out[AMX_ROUTE_WORDS]);
 /* What the plan's last gather launched (read-only): the kernel's name into buf, out = {workgroups, threads per workgroup, LDS bytes} */
 int amx_prep_last_launch(const amx_prep *p, char *buf, int cap, int64_t out[3]);
 /* The gather with the tensor fit taken along (round 5): y AND the principal directions of core.py:431-436, 456-458 in ONE pass over

@@ -302,7 +302,7 @@ def inverse_inputs():
 
 # NODDI dictionaries, one per branch of the upload (amx_lut.hip, amx_seed.hip): name -> what noddi_case builds
 NODDI_SHAPES = ('bench', 'v150', 'v288', 'exvivo', 'single_b0', 'nonunit_b0', 'grid3x3', 'atoms5', 'v10', 'dup3', 'noseed')
-LDS_PER_CU = 160 * 1024          # kLdsPerCU (amx_launch.hpp)
+LDS_PER_CU = 160 * 1024          # kLdsPerCU (amx_noddi_route.hpp)
 
 
 def noddi_branches(nS, n_atoms):
