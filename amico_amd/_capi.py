@@ -38,7 +38,8 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device',
-           'amx_dict_set_dense', 'amx_batched_last_dense']
+           'amx_dict_set_dense', 'amx_batched_last_dense',
+           'amx_bootstrap_resample_device', 'amx_bootstrap_resample_device_f32', 'amx_bootstrap_accumulate_device', 'amx_bootstrap_std_device']
 
 # one row per model fit: what the C entry points amx_<stem>_fit[_f32] / amx_<stem>_fit_device[_f32] differ in.  lib() makes their argtypes
 # from it, _fit_host / _fit_device their calls, models.BaseModel._run the results dict.
@@ -155,6 +156,10 @@ def lib():
     L.amx_prep_corrected_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32p, C.c_int, c_vp, c_vp]  # ctx, plan, lut, y32, x_iso, mean_b0, b0_cols (host), n, volume, stream
     L.amx_predict_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, C.c_int64, c_vp, c_vp]      # ctx, lut, x, x_stride, x_offset, dirs, n, y_est, stream
     L.amx_prep_predicted_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, c_vp, c_vp]   # ctx, plan, lut, x, x_stride, x_offset, dirs, mean_b0, volume, stream
+    for f_ in (L.amx_bootstrap_resample_device, L.amx_bootstrap_resample_device_f32):
+        f_.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_int, C.c_int64, C.c_uint64, C.c_int64, c_vp, c_vp]   # ctx, y, y_est, n, nS, first_voxel, seed, replicate, y_b, stream
+    L.amx_bootstrap_accumulate_device.argtypes = [c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp, c_vp]              # ctx, maps, n_elems, t, mean, m2, stream
+    L.amx_bootstrap_std_device.argtypes = [c_vp, c_vp, C.c_int64, C.c_int64, c_vp, c_vp]                           # ctx, m2, n_elems, B, std, stream
     L.amx_debug_fetch.argtypes = [c_vp, c_vp, C.c_int, c_vp, C.c_size_t]
     L.amx_set_progress.argtypes = [c_vp, PROGRESS_CB, c_vp]
     L.amx_lut_upload_czb.argtypes = [c_vp, c_fp, c_fp, c_fp, c_dp, c_i16p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -591,9 +596,10 @@ def _fit_device(row, ctx, lut, y_t, dirs_t, lambda1, lambda2, extras, want, stre
     if iso is not False:
         xi = torch.empty((n, lut.n_iso), **f64) if iso is True else _own_tensor('iso', iso, (n, lut.n_iso), y_t)
         flags |= F_FW_ISO
-    res = [torch.empty((n,) + o.shape(lut, extras), **f64) if k else None for o, k in zip(row.outputs, on)]
+    res = [torch.empty((n,) + o.shape(lut, extras), **f64) if k and not (o.key is None and into is not None) else None
+           for o, k in zip(row.outputs, on)]
     if into is not None:
-        res[0] = _own_tensor('into', into, tuple(res[0].shape), y_t)
+        res[0] = _own_tensor('into', into, (n,) + row.outputs[0].shape(lut, extras), y_t)
     fn = getattr(lib(), 'amx_%s_fit_device%s' % (row.stem, '_f32' if y_t.dtype == torch.float32 else ''))
     args = [ctx._h, lut._h, _dptr(y_t)] + ([_dptr(dirs_t)] if row.dirs else [])
     args += (n, float(lambda1), float(lambda2)) + tuple(extras[:len(row.extras)]) + (flags,)
@@ -666,6 +672,53 @@ def predict_device(ctx, lut, x_t, dirs_t=None, stream=None):
     ye = torch.empty((n, lut.nS), dtype=torch.float64, device=x_t.device)
     ctx.check(lib().amx_predict_device(ctx._h, lut._h, _dptr(x_t), stride, offset, _dptr(dirs_t), n, _dptr(ye), c_vp(stream or 0)))
     return ye
+
+
+def _f64_like(name, t, like, shape=None):
+    import torch
+    if t.dtype != torch.float64 or not t.is_contiguous() or t.device != like.device or (shape is not None and tuple(t.shape) != tuple(shape)):
+        raise ValueError('%s must be a contiguous float64 device tensor%s on the device of the other arguments'
+                         % (name, '' if shape is None else ' of shape %s' % (tuple(shape),)))
+    return t
+
+
+def bootstrap_resample_device(ctx, y_t, yest_t, seed, replicate, first_voxel=0, stream=None, into=None):
+    """one wild-bootstrap replicate of the signals (amx_bootstrap_resample_device[_f32]): y_b = max(0, y_est + s (y - y_est)) with the
+    Rademacher sign s of (seed, replicate, first_voxel + i, j, nS) -- include/amico_amd.h has the generator.  y_t f32 | f64 [n, nS],
+    yest_t f64 [n, nS] (predict_device); the replicate has the dtype of y.  into: the tensor to write (it must not be y or y_est)"""
+    import torch
+    if y_t.dtype not in (torch.float64, torch.float32) or y_t.dim() != 2 or not y_t.is_contiguous():
+        raise ValueError('y must be a contiguous float64 (or float32) device tensor [n_vox, nS]')
+    _f64_like('y_est', yest_t, y_t, y_t.shape)
+    if not 0 <= int(seed) < 2 ** 64:
+        raise ValueError('seed must be an integer in 0 .. 2^64 - 1')
+    yb = into
+    if yb is None:
+        yb = torch.empty_like(y_t)
+    elif yb.dtype != y_t.dtype or yb.shape != y_t.shape or not yb.is_contiguous() or yb.device != y_t.device:
+        raise ValueError('into must be a contiguous device tensor of the shape and dtype of y, on its device')
+    fn = lib().amx_bootstrap_resample_device_f32 if y_t.dtype == torch.float32 else lib().amx_bootstrap_resample_device
+    ctx.check(fn(ctx._h, _dptr(y_t), _dptr(yest_t), y_t.shape[0], y_t.shape[1], int(first_voxel), int(seed), int(replicate), _dptr(yb),
+                 c_vp(stream or 0)))
+    return yb
+
+
+def bootstrap_accumulate_device(ctx, maps_t, t, mean_t, m2_t, stream=None):
+    """Welford's step for the t-th replicate's maps (t from 1; amx_bootstrap_accumulate_device): mean_t / m2_t are updated in place"""
+    _f64_like('mean', mean_t, maps_t, maps_t.shape)
+    _f64_like('M2', m2_t, maps_t, maps_t.shape)
+    _f64_like('maps', maps_t, mean_t)
+    ctx.check(lib().amx_bootstrap_accumulate_device(ctx._h, _dptr(maps_t), maps_t.numel(), int(t), _dptr(mean_t), _dptr(m2_t),
+                                                    c_vp(stream or 0)))
+
+
+def bootstrap_std_device(ctx, m2_t, samples, stream=None, into=None):
+    """std = sqrt(M2 / (samples - 1)) (amx_bootstrap_std_device); into: the tensor to write (default: a new one)"""
+    import torch
+    sd = torch.empty_like(m2_t) if into is None else _f64_like('into', into, m2_t, m2_t.shape)
+    _f64_like('M2', m2_t, sd)
+    ctx.check(lib().amx_bootstrap_std_device(ctx._h, _dptr(m2_t), m2_t.numel(), int(samples), _dptr(sd), c_vp(stream or 0)))
+    return sd
 
 
 class Dict:

@@ -26,6 +26,7 @@ from . import models as _models
 from . import _capi
 from . import prep as _prep
 from . import dti as _dti
+from . import bootstrap as _bootstrap
 from .synthetic import SimpleScheme
 
 
@@ -245,6 +246,14 @@ class Evaluation:
         """The chain of the module docstring.  Config keys that are not the reference's:
 
         doSavePredictedSignal   RESULTS['DWI_predicted'], results['y_est'].
+        bootstrap_samples       B in 2 .. 10 000 (None or 0: off), with bootstrap_seed (default 0): the wild (residual) bootstrap of the
+            maps, B refits per voxel on the GPU (amico_amd.bootstrap).  RESULTS['MAPs_std'] and RESULTS['MAPs_boot_mean'],
+            float32 [X, Y, Z, n_maps], zero outside the mask: standard deviation (ddof = 1) and mean of the maps over the replicates;
+            results['estimates_std'] / ['estimates_boot_mean'] float64 [n, n_maps].  The replicates keep the original fit's
+            directions (the tensor fit is not repeated: the uncertainty is conditional on the direction); RESULTS['MAPs'] is what the
+            fit without the key gives, bit for bit.  NODDI, FreeWater and CylinderZeppelinBall; SANDI, several devices and an assigned
+            `y` raise NotImplementedError, a bad value ValueError, before anything is uploaded.  A progress_callback sees the ticks
+            of every replicate's fit.
         doSaveTensorMaps        (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
@@ -274,6 +283,11 @@ class Evaluation:
             raise NotImplementedError('doSaveTensorMaps is not built for several devices (set_devices)')
         if self.get_config('doSavePredictedSignal') and len(_models.get_contexts()) > 1:
             raise NotImplementedError('doSavePredictedSignal is not built for several devices (set_devices)')
+        boot = _bootstrap.config(self)                                # (ValueError for a bad bootstrap_samples / bootstrap_seed)
+        if boot is not None and self.model.id == 'SANDI':
+            raise NotImplementedError(_bootstrap.REFUSE_SANDI)
+        if boot is not None and len(_models.get_contexts()) > 1:
+            raise NotImplementedError('bootstrap_samples is not built for several devices (set_devices)')
         nt = self.get_config('nthreads')
         self.nthreads = nt if nt > 0 else cpu_count()
         self.model.scheme = self.scheme
@@ -380,6 +394,11 @@ class Evaluation:
 
         self.RESULTS = {}
         self.RESULTS['MAPs'] = sc('estimates', results['estimates'])
+        if boot is not None:
+            if 'estimates_std' not in results:
+                raise NotImplementedError("bootstrap_samples: this model's fit() ran no bootstrap (it does not go through BaseModel._run)")
+            self.RESULTS['MAPs_std'] = sc('estimates_std', results['estimates_std'])
+            self.RESULTS['MAPs_boot_mean'] = sc('estimates_boot_mean', results['estimates_boot_mean'])
         if d_dirs is not None:
             out['DIRs'] = d_dirs
             self.RESULTS['DIRs'] = sc('DIRs', None)

@@ -8,6 +8,7 @@ dictionaries directly in signal space for tests and benchmarks.
 from abc import ABC, abstractmethod
 import numpy as np
 from . import _capi
+from . import bootstrap as _bootstrap
 
 _CTX = None
 _CTXS = None          # one context per device of the fit's device set (set_devices / AMX_DEVICES); _CTXS[0] is _CTX
@@ -316,20 +317,37 @@ class BaseModel(ABC):
         if predict and (dev is None or len(get_contexts()) > 1):
             raise NotImplementedError('doSavePredictedSignal needs the signals Evaluation.fit() left on one GPU: it is not built for an '
                                       'assigned evaluation.y or for several devices (set_devices)')
+        # bootstrap_samples / bootstrap_seed (not keys of the reference): results['estimates_std'] / ['estimates_boot_mean'] from that
+        # many wild-bootstrap refits (amico_amd/bootstrap.py); refused, like the prediction, before anything is uploaded
+        boot = _bootstrap.config(evaluation)
+        if boot is not None:
+            if dev is None or len(get_contexts()) > 1:
+                raise NotImplementedError('bootstrap_samples needs the signals Evaluation.fit() left on one GPU: it is not built for an '
+                                          'assigned evaluation.y or for several devices (set_devices)')
+            if row.stem == 'sandi':
+                raise NotImplementedError(_bootstrap.REFUSE_SANDI)
         lut = self._lut(evaluation, lambda: upload(ctx))
         lambdas = (self.solver_params['lambda1'], self.solver_params['lambda2'])
         names = [o.name for o in row.outputs]
         if dev is not None:
             dirs = (self._dev_dirs(evaluation, dev),) if row.dirs else ()
-            more = dict(return_x=True) if predict else {}       # (AMX_F_DEBUG_X selects no path: the same kernels, and they write x)
+            # (AMX_F_DEBUG_X selects no path: the same kernels, and they write x; the prediction and the bootstrap share the one hand-over)
+            more = dict(return_x=True) if predict or boot is not None else {}
             out = getattr(_capi, row.stem + '_fit_device')(ctx, lut, dev['y'], *dirs, *lambdas, *extras, **(dev_want or want), **more)
             x = None
-            if predict:                                          # (the coefficients come back right behind the row's outputs)
+            if more:                                             # (the coefficients come back right behind the row's outputs)
                 x, out = out[len(names)], out[:len(names)] + out[len(names) + 1:]
             results = self._finish_device(ctx, dev, dict(zip(names, out)))
             if dev_tail is not None:
                 results = dev_tail(ctx, lut, dev, out, results)
-            return results if x is None else self._lazy_predicted(ctx, lut, dev, x, dirs[0] if dirs else None, results)
+            if boot is not None:
+                # the replicates' fits follow on the same stream; their moments stay in dev['out'] for Evaluation.fit's scatter
+                mean, std = _bootstrap.wild_bootstrap(ctx, row, lut, dev['y'], dirs[0] if dirs else None, *lambdas, extras, x, *boot)
+                ctx.sync()
+                self._warn_if_capped(ctx)
+                dev['out']['estimates_std'], dev['out']['estimates_boot_mean'] = std, mean
+                results['estimates_std'], results['estimates_boot_mean'] = std.cpu().numpy(), mean.cpu().numpy()
+            return results if not predict else self._lazy_predicted(ctx, lut, dev, x, dirs[0] if dirs else None, results)
         fit, y, d = getattr(_capi, row.stem + '_fit'), evaluation.y, evaluation.DIRs
         on = [o.key is None or want[o.key] for o in row.outputs]
         if len(get_contexts()) > 1:

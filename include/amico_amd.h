@@ -257,6 +257,41 @@ int amx_predict_device(amx_ctx *ctx, const amx_lut *lut, const double *d_x, int6
                        int64_t n_vox, double *d_yest, void *hip_stream);
 /* (volume form: amx_prep_predicted_device, beside amx_prep_corrected_device below) */
 
+/* ---- wild (residual) bootstrap of the maps: a per-voxel standard error from B refits (no counterpart in the reference, whose
+ * Evaluation.fit() gives one fit per subject).  Everything a replicate needs lies in HBM after a fit: the signals y, the directions,
+ * the coefficients (AMX_F_DEBUG_X) and from them the prediction y_est = A x (amx_predict_device).  These three calls add the replicate
+ * signal and the running moments; the refit itself is the ordinary amx_<model>_fit_device[_f32] on d_yb with the ORIGINAL fit's
+ * directions (the tensor fit is not repeated: the uncertainty is conditional on the direction).  amico_amd/bootstrap.py drives them.
+ * For replicate b = 0 .. B-1, voxel i of the call (+ the caller's first_voxel), volume j of nS:
+ *     ctr = (first_voxel + i) * nS + j                                   (uint64, wraps)
+ *     z   = seed + (b + 1) * 0x9E3779B97F4A7C15 + ctr * 0xD1B54A32D192ED03
+ *     z   = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *     z   = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *     z   =  z ^ (z >> 31)
+ *     s   = (z >> 63) ? -1 : +1                                          (Rademacher weight)
+ *     v   = y_est[i][j] + s * ((double)y[i][j] - y_est[i][j])            (fp64; s * r is exact, so contraction cannot change v)
+ *     y_b[i][j] = (v < 0) ? 0 : v                                        (the gather's clip, core.py:452; a NaN stays a NaN)
+ * The sign depends on (seed, b, first_voxel + i, j, nS) only -- not on n_vox, the launch shape or how a call is split: first_voxel is
+ * there so that a shard of a larger call reproduces that call's signs.  Every row is resampled, the b0 rows included.  y_b has the dtype
+ * of y (float32: (float)v), so a replicate takes the same fit entry, and therefore the same kernels, as the original fit.
+ * SANDI has no prediction of y (amx_predict_device gives the reference's quirk: rescaled coefficients on the normalised dictionary), so
+ * its residuals mean nothing; the Python driver refuses it.
+ * Device pointers, enqueued on hip_stream, no synchronisation; n_vox == 0 is a no-op.  AMX_E_BADARG with a message: a NULL buffer,
+ * nS < 1, a negative n_vox / first_voxel / replicate, d_yb overlapping d_y or d_yest. */
+int amx_bootstrap_resample_device(amx_ctx *ctx, const double *d_y, const double *d_yest, int64_t n_vox, int nS, int64_t first_voxel,
+                                  uint64_t seed, int64_t replicate, double *d_yb, void *hip_stream);
+int amx_bootstrap_resample_device_f32(amx_ctx *ctx, const float *d_y, const double *d_yest, int64_t n_vox, int nS, int64_t first_voxel,
+                                      uint64_t seed, int64_t replicate, float *d_yb, void *hip_stream);
+/* Welford's moments of the maps over the replicates, fp64, every operation rounded on its own (no fused multiply-add).  The t-th
+ * replicate's maps (t = 1 .. B), for each of the n_elems = n_vox * n_maps elements m:
+ *     d = m - mean;   mean += d / t;   M2 += d * (m - mean)
+ * t = 1 takes mean = M2 = 0 without reading them, so neither buffer needs a memset.  A NaN map makes that element NaN from there on.
+ * The three buffers must not overlap.  AMX_E_BADARG: t < 1, a NULL buffer, overlap. */
+int amx_bootstrap_accumulate_device(amx_ctx *ctx, const double *d_maps, int64_t n_elems, int64_t t, double *d_mean, double *d_m2,
+                                    void *hip_stream);
+/* std = sqrt(M2 / (B - 1)) (division and root correctly rounded; d_std may be d_m2 itself).  AMX_E_BADARG for B < 2. */
+int amx_bootstrap_std_device(amx_ctx *ctx, const double *d_m2, int64_t n_elems, int64_t B, double *d_std, void *hip_stream);
+
 /* ---- diagnosis / tests of the support seeds (csrc/amx_seed.hpp; no counterpart in the reference): copies a workspace
  * buffer of the LAST NODDI fit of this ctx -- which = 0: voxel permutation int32[n] (bucket order), 1: projected signals
  * f64[n][12] (bucket order), 2: support seeds uint64[n] (bucket order; up to 8 atom ids, one per byte, >= 0xf0 = empty;
