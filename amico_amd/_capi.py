@@ -27,8 +27,8 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_noddi_fit_device_f32', 'amx_freewater_fit_device_f32', 'amx_sandi_fit_device_f32', 'amx_czb_fit_device_f32',
            'amx_set_debug_x', 'amx_set_fw_iso', 'amx_freewater_corrected_device', 'amx_prep_corrected_device', 'amx_predict_device', 'amx_prep_predicted_device', 'amx_debug_fetch', 'amx_lut_upload_czb', 'amx_czb_fit', 'amx_czb_fit_f32', 'amx_czb_fit_device', 'amx_noddi_fit_f32', 'amx_freewater_fit_f32', 'amx_sandi_fit_f32', 'amx_set_progress',
            'amx_set_profiling', 'amx_last_kernel_ms', 'amx_last_stats', 'amx_last_seed_stats', 'amx_last_host_narrowed', 'amx_last_path', 'amx_host_pool_info', 'amx_selftest',
-           'amx_dti_create', 'amx_dti_create_method', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
-           'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_prep_gather_device_f32',
+           'amx_dti_create', 'amx_dti_create_method', 'amx_dti_create_robust', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_last_robust', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
+           'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_dti_fit_robust', 'amx_dti_fit_robust_device', 'amx_dti_fit_robust_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
            'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_noddi_route', 'amx_prep_last_launch',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
@@ -187,7 +187,9 @@ def lib():
     L.amx_selftest.argtypes = [c_vp, c_dp]
     L.amx_dti_create.argtypes = [c_vp, c_dp, C.c_int, C.c_double, C.POINTER(c_vp)]
     L.amx_dti_create_method.argtypes = [c_vp, c_dp, c_dp, C.c_int, C.c_double, C.c_int, C.POINTER(c_vp)]
+    L.amx_dti_create_robust.argtypes = [c_vp, c_dp, c_dp, C.c_int, C.c_double, C.c_double, C.POINTER(c_vp)]
     L.amx_dti_last_unconverged.argtypes = [c_vp, c_vp, C.POINTER(C.c_int64)]
+    L.amx_dti_last_robust.argtypes = [c_vp, c_vp, C.POINTER(C.c_int64)]
     L.amx_dti_last_trips.argtypes = [c_vp, c_vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.amx_dti_destroy.argtypes = [c_vp]
     L.amx_dti_destroy.restype = None
@@ -198,6 +200,10 @@ def lib():
     L.amx_dti_fit.argtypes = [c_vp, c_vp, c_dp, C.c_int64, C.c_double] + [c_dp] * n_out
     L.amx_dti_fit_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 1)
     L.amx_dti_fit_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 1)
+    # (the robust calls: the outlier counts int32 [n] behind the other outputs)
+    L.amx_dti_fit_robust.argtypes = [c_vp, c_vp, c_dp, C.c_int64, C.c_double] + [c_dp] * n_out + [c_i32p]
+    L.amx_dti_fit_robust_device.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 2)
+    L.amx_dti_fit_robust_device_f32.argtypes = [c_vp, c_vp, c_vp, C.c_int64, C.c_double] + [c_vp] * (n_out + 2)
     L.amx_prep_create.argtypes = [c_vp, c_i64p, c_i64p, C.c_int, c_i32p, C.c_int64, c_i32p, c_i32p, C.c_int,
                                   c_i32p, C.c_int, C.c_int, C.POINTER(c_vp)]
     L.amx_prep_destroy.argtypes = [c_vp]
@@ -795,19 +801,35 @@ def dir_to_lut_idx(ctx, lut, dirs):
     return out
 
 
+def check_sigma(sigma):
+    """the noise level of the robust tensor fit: a finite number > 0 (ValueError otherwise), as a float"""
+    try:
+        ok = not isinstance(sigma, (bool, str, bytes)) and np.ndim(sigma) == 0 and np.isfinite(float(sigma)) and float(sigma) > 0.0
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError('sigma (the noise level of the robust tensor fit) must be a finite number > 0, got %r' % (sigma,))
+    return float(sigma)
+
+
 class Dti:
     """amx_dti: principal-direction estimator of one acquisition scheme (include/amico_amd.h, row f1)."""
 
-    METHODS = {'OLS': 0, 'WLS': 1, 'NLLS': 2}        # AMX_DTI_* (include/amico_amd.h)
+    METHODS = {'OLS': 0, 'WLS': 1, 'NLLS': 2, 'RESTORE': 3}        # AMX_DTI_* (include/amico_amd.h)
     # the outputs of amx_dti_fit* in ABI order: (name, values per voxel); all float64.  scalars = FA, MD, AD, RD
     OUTPUTS = (('directions', 3), ('evals', 3), ('scalars', 4))
 
-    def __init__(self, ctx, inv_design, min_signal=1e-4, design=None, method='OLS'):
+    def __init__(self, ctx, inv_design, min_signal=1e-4, design=None, method='OLS', sigma=None):
+        """sigma: the noise level of 'RESTORE', in the units of the signal (a finite number > 0); None for the other methods"""
         w = np.ascontiguousarray(inv_design, dtype=np.float64)
         if w.ndim != 2 or w.shape[0] != 7:
             raise ValueError('inv_design must be pinv(design matrix), shape [7, nS]')
         if method not in self.METHODS:
-            raise ValueError("method must be one of 'OLS', 'WLS', 'NLLS'")
+            raise ValueError("method must be one of 'OLS', 'WLS', 'NLLS', 'RESTORE'")
+        if method == 'RESTORE':
+            sigma = check_sigma(sigma)
+        elif sigma is not None:
+            raise ValueError('sigma belongs to the RESTORE method')
         if design is None:
             if method != 'OLS':
                 raise ValueError('%s needs the design matrix, shape [nS, 7]' % method)
@@ -817,9 +839,13 @@ class Dti:
             if x.shape != (w.shape[1], 7):
                 raise ValueError('design must be the design matrix, shape [nS, 7] = [%d, 7]' % w.shape[1])
         self.ctx, self.nS, self.method = ctx, w.shape[1], method
+        self.sigma = sigma
         self._h = c_vp()
-        ctx.check(lib().amx_dti_create_method(ctx._h, None if x is None else _p(x, c_dp), _p(w, c_dp), self.nS, float(min_signal),
-                                              self.METHODS[method], C.byref(self._h)))
+        if method == 'RESTORE':
+            ctx.check(lib().amx_dti_create_robust(ctx._h, _p(x, c_dp), _p(w, c_dp), self.nS, float(min_signal), sigma, C.byref(self._h)))
+        else:
+            ctx.check(lib().amx_dti_create_method(ctx._h, None if x is None else _p(x, c_dp), _p(w, c_dp), self.nS, float(min_signal),
+                                                  self.METHODS[method], C.byref(self._h)))
 
     def last_unconverged(self):
         """voxels of the last NLLS call that kept their starting parameters (waits for the call)"""
@@ -832,6 +858,13 @@ class Dti:
         a, b = C.c_int64(0), C.c_int64(0)
         self.ctx.check(lib().amx_dti_last_trips(self.ctx._h, self._h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def last_robust(self):
+        """(voxels that entered the reweighted fit, voxels refitted without their outliers, voxels at the reweighted fit's trip cap or
+        give-up, voxels left with fewer than 7 inliers) of the last RESTORE call; zeros for the other methods"""
+        out = (C.c_int64 * 4)()
+        self.ctx.check(lib().amx_dti_last_robust(self.ctx._h, self._h, out))
+        return tuple(int(v) for v in out)
 
     def close(self):
         if getattr(self, '_h', None) and getattr(self.ctx, '_h', None):
@@ -869,14 +902,28 @@ class Dti:
             raise ValueError('want must name some of %s' % ', '.join(name for name, _ in self.OUTPUTS))
         out = {name: np.zeros((y.shape[0], k)) for name, k in self.OUTPUTS if name in want}
         ptrs = [_p(out[name], c_dp) if name in out else None for name, _ in self.OUTPUTS]
-        self.ctx.check(lib().amx_dti_fit(self.ctx._h, self._h, _p(y, c_dp), y.shape[0], float(min_diffusivity), *ptrs))
+        if self.method == 'RESTORE':
+            # (the robust estimator: also 'outliers' int32 [n_vox], the samples its verdict left out -- amx_dti_fit_robust)
+            out['outliers'] = np.zeros(y.shape[0], dtype=np.int32)
+            self.ctx.check(lib().amx_dti_fit_robust(self.ctx._h, self._h, _p(y, c_dp), y.shape[0], float(min_diffusivity), *ptrs,
+                                                    _p(out['outliers'], c_i32p)))
+        else:
+            self.ctx.check(lib().amx_dti_fit(self.ctx._h, self._h, _p(y, c_dp), y.shape[0], float(min_diffusivity), *ptrs))
         return out
 
-    def fit_device(self, d_y, n_vox, min_diffusivity, d_dirs=None, d_evals=None, d_scalars=None, stream=None, f32=False):
+    def fit_device(self, d_y, n_vox, min_diffusivity, d_dirs=None, d_evals=None, d_scalars=None, stream=None, f32=False,
+                   d_outliers=None):
         """directions_device with the eigenvalues f64 [n_vox, 3] and FA, MD, AD, RD f64 [n_vox, 4]; a pointer of None (or 0) leaves that
-        output out, and with d_evals and d_scalars both None this is directions_device (amx_dti_fit_device[_f32])"""
-        fn = lib().amx_dti_fit_device_f32 if f32 else lib().amx_dti_fit_device
+        output out, and with d_evals and d_scalars both None this is directions_device (amx_dti_fit_device[_f32]).  d_outliers
+        int32 [n_vox]: a RESTORE estimator's outlier counts (amx_dti_fit_robust_device[_f32])"""
+        if d_outliers and self.method != 'RESTORE':
+            raise ValueError('d_outliers belongs to a RESTORE estimator')
         ptrs = [c_vp(p or 0) for p in (d_dirs, d_evals, d_scalars)]
+        if d_outliers:
+            fn = lib().amx_dti_fit_robust_device_f32 if f32 else lib().amx_dti_fit_robust_device
+            ptrs.append(c_vp(d_outliers))
+        else:
+            fn = lib().amx_dti_fit_device_f32 if f32 else lib().amx_dti_fit_device
         self.ctx.check(fn(self.ctx._h, self._h, c_vp(d_y), int(n_vox), float(min_diffusivity), *ptrs, c_vp(stream or 0)))
 
 

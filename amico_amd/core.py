@@ -65,6 +65,7 @@ class Evaluation:
         self.set_config('doDirectionalAverage', False)
         self.set_config('nthreads', -1)
         self.set_config('DTI_fit_method', 'OLS')
+        self.set_config('DTI_sigma', None)             # not a key of the reference: see fit()
         self.set_config('BLAS_nthreads', 1)
         self.set_config('doSaveTensorMaps', False)     # not a key of the reference: see fit()
 
@@ -254,13 +255,22 @@ class Evaluation:
             fit without the key gives, bit for bit.  NODDI, FreeWater and CylinderZeppelinBall; SANDI, several devices and an assigned
             `y` raise NotImplementedError, a bad value ValueError, before anything is uploaded.  A progress_callback sees the ticks
             of every replicate's fit.
+        DTI_sigma               (default None) the noise level of DTI_fit_method 'RT' | 'RESTORE' | 'restore', one finite number > 0 in the
+            units of the prepared signal `y` (dti.TensorDirections; the reference passes dipy none and fails there).  Unset, it is
+            1 / DWI-SNR when DWI-SNR is set, doNormalizeSignal is on and the scheme has b0 volumes (the signals are divided by their
+            b0 mean, so sigma = b0 / SNR becomes 1 / SNR); with neither the robust names raise NotImplementedError where the tensor
+            fit would run, as they always have.  A bad value raises ValueError before anything is uploaded.  With doMergeB0 the
+            one sigma applies to the merged b0 as well, as dipy would do with that table.  get_config('dti_robust') holds the four
+            counters of `TensorDirections.last_robust` after the fit; with doSaveTensorMaps RESULTS['DTI_outliers'] float32 [X, Y, Z]
+            is the number of samples left out per voxel (zero outside the mask), and Free-Water's second tensor fit on the corrected
+            rows is robust too and leaves RESULTS['DTI_outliers_corrected'].  The volume pipelines (pipeline.py) do not take it.
         doSaveTensorMaps        (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
             two kernels, the gather and then the tensor pass, for every method -- here that is the route of always; in the volume
             pipelines (pipeline.py, tensor_maps=True) it means that the OLS fit no longer rides on the fused gather.  With
             `directions` given to set_data the tensor pass runs for the maps only and `DIRs` stay the caller's.  'RT' / 'RESTORE'
-            raise NotImplementedError as they do whenever a tensor fit would run; doDirectionalAverage leaves no gradient
+            without a sigma raise NotImplementedError as they do whenever a tensor fit would run; doDirectionalAverage leaves no gradient
             directions to fit a tensor to and raises ValueError before anything is uploaded.
             Free-Water: also RESULTS['DTI_MAPs_corrected'] / ['DTI_evals_corrected'], the same fit on the free-water-corrected rows
             (results['y_corrected'], made in HBM from the fit's isotropic coefficients; doSaveCorrectedDWI need not be set;
@@ -279,6 +289,11 @@ class Evaluation:
         if self.KERNELS['model'] != self.model.id:
             raise RuntimeError('Response functions were not created with the same model')
         _dti.check_fit_method(self.get_config('DTI_fit_method'))     # core.py:419-420: before anything is uploaded
+        dti_sigma = None
+        if self.get_config('DTI_fit_method') in _dti.ROBUST_METHODS:
+            # (ValueError for a bad DTI_sigma / DWI-SNR; None leaves the refusal to where the tensor fit would run)
+            dti_sigma = _dti.resolve_sigma(self.get_config('DTI_fit_method'), self.get_config('DTI_sigma'), self.get_config('DWI-SNR'),
+                                           bool(self.get_config('doNormalizeSignal')) and self.scheme.b0_count > 0)
         if tensor_maps and len(_models.get_contexts()) > 1:
             raise NotImplementedError('doSaveTensorMaps is not built for several devices (set_devices)')
         if self.get_config('doSavePredictedSignal') and len(_models.get_contexts()) > 1:
@@ -340,9 +355,10 @@ class Evaluation:
         elif self._dirs_img is not None:
             d_dirs = torch.from_numpy(np.ascontiguousarray(self._dirs_img[sel, :], dtype=np.float64)).to(dev)
         if (d_dirs is None and not self.get_config('doDirectionalAverage')) or tensor_maps:
-            # (raises NotImplementedError for 'RT' / 'RESTORE': only here, where a tensor fit would actually run)
+            # (raises NotImplementedError for 'RT' / 'RESTORE' without a sigma: only here, where a tensor fit would actually run)
             est = _dti.TensorDirections.from_scheme(self._raw_scheme, do_merge_b0=self.get_config('doMergeB0'), ctx=ctx,
-                                                    fit_method=self.get_config('DTI_fit_method'))
+                                                    fit_method=self.get_config('DTI_fit_method'), sigma=dti_sigma)
+            robust = dti_sigma is not None
             d_fit_dirs = None
             if d_dirs is None:
                 d_fit_dirs = d_dirs = torch.empty((n, 3), dtype=torch.float64, device=dev)
@@ -350,10 +366,15 @@ class Evaluation:
                 # doSaveTensorMaps: the kernel variant that also writes what its eigen-solve has; given directions stay the caller's
                 d_tmaps = {'DTI_evals': torch.empty((n, 3), dtype=torch.float64, device=dev),
                            'DTI_MAPs': torch.empty((n, 4), dtype=torch.float64, device=dev)}
+                if robust:
+                    d_tmaps['DTI_outliers'] = torch.empty(n, dtype=torch.int32, device=dev)
                 est.fit_device(d_y.data_ptr(), n, None if d_fit_dirs is None else d_fit_dirs.data_ptr(), f32=True,
-                               d_evals=d_tmaps['DTI_evals'].data_ptr(), d_scalars=d_tmaps['DTI_MAPs'].data_ptr())
+                               d_evals=d_tmaps['DTI_evals'].data_ptr(), d_scalars=d_tmaps['DTI_MAPs'].data_ptr(),
+                               d_outliers=d_tmaps['DTI_outliers'].data_ptr() if robust else None)
             else:
                 est.fit_device(d_y.data_ptr(), n, d_fit_dirs.data_ptr(), f32=True)
+            if robust:
+                self.set_config('dti_robust', est.last_robust())
         ctx.sync()
         del d_img
         if self._prep.debias_snr is not None:
@@ -440,11 +461,19 @@ class Evaluation:
                 d_yc = _capi.freewater_corrected_device(ctx, self._dev['lut'], self._dev['y'], x_iso)
                 for key, k in (('DTI_evals', 3), ('DTI_MAPs', 4)):
                     d_tmaps[key + '_corrected'] = torch.empty((n, k), dtype=torch.float64, device=dev)
+                if 'DTI_outliers' in d_tmaps:
+                    d_tmaps['DTI_outliers_corrected'] = torch.empty(n, dtype=torch.int32, device=dev)
                 est.fit_device(d_yc.data_ptr(), n, None, d_evals=d_tmaps['DTI_evals_corrected'].data_ptr(),
-                               d_scalars=d_tmaps['DTI_MAPs_corrected'].data_ptr())
+                               d_scalars=d_tmaps['DTI_MAPs_corrected'].data_ptr(),
+                               d_outliers=d_tmaps['DTI_outliers_corrected'].data_ptr() if 'DTI_outliers' in d_tmaps else None)
             for key in ('DTI_MAPs', 'DTI_evals', 'DTI_MAPs_corrected', 'DTI_evals_corrected'):
                 if key in d_tmaps:
                     out[key] = d_tmaps[key]
+                    self.RESULTS[key] = sc(key, None)
+            for key in ('DTI_outliers', 'DTI_outliers_corrected'):
+                if key in d_tmaps:
+                    # (the scatter kernel moves floating-point rows: the counts, at most 512, are exact in them)
+                    out[key] = d_tmaps[key].to(torch.float64)
                     self.RESULTS[key] = sc(key, None)
         if self.get_config('doSavePredictedSignal'):
             # the fit left its coefficients in HBM: dictionary, x, DIRs (and mean_b0) -> the float32 volume in one kernel, one copy home;

@@ -280,9 +280,11 @@ struct amx_dti {
     int nS = 0;
     double min_signal = 0.0;
     double *wt = nullptr;          // device f64[nS][6]: transposed first six rows of pinv(design matrix)
-    int method = 0;                // AMX_DTI_OLS | AMX_DTI_WLS | AMX_DTI_NLLS
-    // WLS / NLLS only (one allocation): pinv(design)^T and the design matrix, f64[nS][7] each, in the column-scaled
-    // parametrisation; 1 / scale; counters of the last NLLS call (unconverged voxels, voxel trips, wavefront trips)
+    int method = 0;                // AMX_DTI_OLS | AMX_DTI_WLS | AMX_DTI_NLLS | AMX_DTI_RESTORE
+    double sigma = 0.0;            // RESTORE: the noise level
+    // all but OLS (one allocation): pinv(design)^T and the design matrix, f64[nS][7] each, in the column-scaled
+    // parametrisation; 1 / scale; counters of the last NLLS / RESTORE call, kDtiStats of them (unconverged voxels, voxel trips,
+    // wavefront trips, -, RESTORE: voxels in step 3, refitted, at step 3's cap, with fewer than 7 inliers)
     double *wt7 = nullptr, *xs = nullptr;
     double ics[7] = {1, 1, 1, 1, 1, 1, 1};
     unsigned long long *stats = nullptr;

@@ -1,6 +1,6 @@
 // amx_signal.hip -- the steps either side of model.fit (SURVEY section 8 f): principal directions from the
 // log-linear tensor fit (core.py:431-436, 456-458) -- streaming, HBM-bound kernels -- and from the weighted / non-linear
-// fits of DTI_fit_method 'WLS' / 'NLLS' (core.py:419-420, 436), k_dti_dirs_w.
+// fits of DTI_fit_method 'WLS' / 'NLLS' and the robust fit 'RT' / 'RESTORE' (core.py:419-420, 436), k_dti_dirs_w.
 #include "amx_host.hpp"
 #include "amx_tensor.hpp"
 
@@ -234,8 +234,11 @@ __device__ __forceinline__ bool chol_solve7(double (&A)[28], double (&b)[7], dou
 
 // one lane's share (volumes q, q + 8, ..) of the weighted normal equations, summed over the voxel's lanes:
 // G = X^T W^2 X, g = X^T W^2 log s with W = exp(X p)
+// REFIT (step 4 of RESTORE): the row holds s, not log s, and the lane's volume q + 8 j has the sample weight 0 where bit j of
+// `skip` is set and 1 elsewhere
+template <bool REFIT = false>
 __device__ __forceinline__ void wls_pass(const double *__restrict__ xl, const double *__restrict__ yr, int nS, int q,
-                                         const double (&p)[7], double (&G)[28], double (&g)[7])
+                                         const double (&p)[7], double (&G)[28], double (&g)[7], unsigned long long skip = 0)
 {
 #pragma unroll
     for (int k = 0; k < 28; k++) G[k] = 0.0;
@@ -243,10 +246,15 @@ __device__ __forceinline__ void wls_pass(const double *__restrict__ xl, const do
     for (int k = 0; k < 7; k++) g[k] = 0.0;
 #pragma unroll 1
     for (int v = q; v < nS; v += kDtiLanes) {
+        if constexpr (REFIT) {
+            const bool out = skip & 1;
+            skip >>= 1;
+            if (out) continue;
+        }
         double x[7], t = 0.0;
 #pragma unroll
         for (int k = 0; k < 7; k++) { x[k] = xl[v * 7 + k]; t = fma(x[k], p[k], t); }
-        const double w2 = exp(2.0 * t), ly = yr[v];
+        const double w2 = exp(2.0 * t), ly = REFIT ? log(yr[v]) : yr[v];
 #pragma unroll
         for (int j = 0; j < 7; j++) {
             const double wx = w2 * x[j];
@@ -268,8 +276,10 @@ __device__ __forceinline__ void wls_pass(const double *__restrict__ xl, const do
 }
 
 // the same for the non-linear cost at p: e = exp(X p), r = s - e, c = sum r^2, G = J^T J, g = J^T r with J = e (.) X
+// REFIT: the sample weights of `skip`, as in wls_pass
+template <bool REFIT = false>
 __device__ __forceinline__ void nlls_pass(const double *__restrict__ xl, const double *__restrict__ sr, int nS, int q,
-                                          const double (&p)[7], double &c, double (&G)[28], double (&g)[7])
+                                          const double (&p)[7], double &c, double (&G)[28], double (&g)[7], unsigned long long skip = 0)
 {
     c = 0.0;
 #pragma unroll
@@ -278,6 +288,11 @@ __device__ __forceinline__ void nlls_pass(const double *__restrict__ xl, const d
     for (int k = 0; k < 7; k++) g[k] = 0.0;
 #pragma unroll 1
     for (int v = q; v < nS; v += kDtiLanes) {
+        if constexpr (REFIT) {
+            const bool out = skip & 1;
+            skip >>= 1;
+            if (out) continue;
+        }
         double x[7], t = 0.0;
 #pragma unroll
         for (int k = 0; k < 7; k++) { x[k] = xl[v * 7 + k]; t = fma(x[k], p[k], t); }
@@ -311,24 +326,272 @@ __device__ __forceinline__ int wave_sum(int x)
     return x;
 }
 
+// Levenberg-Marquardt on sum (s_i - exp(X_i p))^2 from p, for the voxels with `run` set (the same on the 8 lanes of a voxel); the
+// loop is uniform over the wavefront.  sr: the voxel's signal row, gv: its kDtiNormLd doubles of LDS, ss = sum s_i^2.  Returns
+// whether the voxel failed (a non-finite cost, the trip cap, lam > 1e12): p is then the starting point again.  trips / wtrips grow
+// by the voxel's trips and by those its wavefront ran.
+template <bool REFIT>
+__device__ __forceinline__ bool nlls_fit(const double *__restrict__ xl, const double *__restrict__ sr, double *__restrict__ gv, int nS, int q,
+                                         unsigned long long skip, double ss, bool run, double (&p)[7], int &trips, int &wtrips)
+{
+    // normal equations of the accepted point: parked in LDS between trips (every lane of the voxel writes the same bits
+    // and reads its own back, so no ordering between lanes is needed); registers hold one set of 35 sums at a time
+    double c, p0[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) p0[k] = p[k];
+    {
+        double G[28], g[7];
+        nlls_pass<REFIT>(xl, sr, nS, q, p, c, G, g, skip);
+        if (run) {
+#pragma unroll
+            for (int k = 0; k < 28; k++) gv[k] = G[k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) gv[28 + k] = g[k];
+        }
+    }
+    bool failed = run && !(c < 1e300);
+    bool active = run && !failed;
+    double lam = 1e-3;
+    const double floor_c = 1e-30 * ss;         // an exact fit (7 volumes) ends at rounding noise of the signal, not at zero
+#pragma unroll 1
+    for (int trip = 0; trip < kLmTrips; trip++) {
+        if (!__any(active)) break;             // the loop is uniform over the wavefront: the shuffles see every lane
+        wtrips++;
+        double pt[7];
+        bool ok;
+        {
+            double G[28], g[7];
+#pragma unroll
+            for (int k = 0; k < 28; k++) G[k] = gv[k];
+#pragma unroll
+            for (int k = 0; k < 7; k++) g[k] = gv[28 + k];
+            ok = chol_solve7(G, g, lam);
+#pragma unroll
+            for (int k = 0; k < 7; k++) pt[k] = ok ? p[k] + g[k] : p[k];
+        }
+        double ct, Gt[28], gt[7];
+        nlls_pass<REFIT>(xl, sr, nS, q, pt, ct, Gt, gt, skip);
+        if (active) {
+            trips++;
+            const bool acc = ok && ct <= c;    // (false for a non-finite trial cost)
+            const bool flat = ok && fabs(c - ct) <= fma(1e-15, c, floor_c);
+            if (acc) {
+#pragma unroll
+                for (int k = 0; k < 7; k++) { p[k] = pt[k]; gv[28 + k] = gt[k]; }
+#pragma unroll
+                for (int k = 0; k < 28; k++) gv[k] = Gt[k];
+                c = ct;
+                lam = fmax(lam * 0.1, 1e-12);
+            } else {
+                lam *= 10.0;
+            }
+            if (flat && trip >= 2) active = false;                  // converged: the cost has stopped moving in fp64
+            else if (lam > 1e12) { active = false; failed = true; }
+        }
+    }
+    failed = failed || active;                 // trip cap
+#pragma unroll
+    for (int k = 0; k < 7; k++) p[k] = failed ? p0[k] : p[k];
+    return failed;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// RESTORE (include/amico_amd.h: steps 1-5).  Step 1 is the NLLS fit above.  What follows runs only while a voxel of the wavefront
+// has a sample beyond 3 sigma; the other voxels idle.  A voxel's residuals live in a second LDS row beside its signals, each lane
+// writing its own volumes and all eight reading the whole row (same wavefront: the fence orders the two); the outlier set is one
+// bit per volume in a register of the lane that owns the volume (64 volumes per lane: schemes of up to 512).
+constexpr int kGmTrips = 1024;                  // trip cap of step 3 (62 on average, 440 at most in a numpy emulation on 33 .. 288 volumes)
+constexpr int kDtiStats = 8;                    // counters of a call (amx_dti in amx_host.hpp)
+
+__device__ __forceinline__ double lanes_max(double x)
+{
+#pragma unroll
+    for (int m = 1; m < kDtiLanes; m <<= 1) x = fmax(x, __shfl_xor(x, m));
+    return x;
+}
+
+__device__ __forceinline__ int lanes_sum(int x)
+{
+#pragma unroll
+    for (int m = 1; m < kDtiLanes; m <<= 1) x += __shfl_xor(x, m);
+    return x;
+}
+
+__device__ __forceinline__ void row_fence()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+
+// r = s - exp(X p) at the lane's volumes: the bits of those beyond thr (a NaN residual is none); returns their count in the voxel
+__device__ __forceinline__ int restore_verdict(const double *__restrict__ xl, const double *__restrict__ sr, int nS, int q,
+                                               const double (&p)[7], double thr, unsigned long long &skip)
+{
+    skip = 0;
+    unsigned long long bit = 1;
+#pragma unroll 1
+    for (int v = q; v < nS; v += kDtiLanes, bit <<= 1) {
+        double t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) t = fma(xl[v * 7 + k], p[k], t);
+        if (fabs(sr[v] - exp(t)) > thr) skip |= bit;
+    }
+    return lanes_sum((int)__popcll(skip));
+}
+
+// numpy's median of the row (DEV: of |row - centre|) by rank counting: each lane ranks its own volumes against the whole row; the
+// value with `less <= k < less + equal` is the k-th smallest.  The mean of the two middle values for an even count.
+template <bool DEV>
+__device__ __forceinline__ double row_median(const double *rr, int nS, int q, double centre)
+{
+    const int k2 = nS >> 1, k1 = (nS & 1) ? k2 : k2 - 1;
+    double lo = -INFINITY, hi = -INFINITY;
+#pragma unroll 1
+    for (int v = q; v < nS; v += kDtiLanes) {
+        const double a = DEV ? fabs(rr[v] - centre) : rr[v];
+        int less = 0, same = 0;
+#pragma unroll 4
+        for (int j = 0; j < nS; j++) {
+            const double b = DEV ? fabs(rr[j] - centre) : rr[j];
+            less += b < a ? 1 : 0;
+            same += b == a ? 1 : 0;
+        }
+        if (less <= k1 && k1 < less + same) lo = a;
+        if (less <= k2 && k2 < less + same) hi = a;
+    }
+    return 0.5 * (lanes_max(lo) + lanes_max(hi));
+}
+
+// the Geman-McClure weight of a residual, w = wn / (r^2 + C^2) with wn = 1 / mean(1 / (r^2 + C^2))
+__device__ __forceinline__ double gm_weight(double r, double C2, double wn) { return wn / fma(r, r, C2); }
+
+// nlls_pass with the frozen weights of the residual row rr (taken at the point the weights belong to):
+// c = sum w r^2, G = J^T W J, g = J^T W r at p
+__device__ __forceinline__ void gm_pass(const double *__restrict__ xl, const double *__restrict__ sr, const double *rr,
+                                        int nS, int q, const double (&p)[7], double C2, double wn, double &c, double (&G)[28],
+                                        double (&g)[7])
+{
+    c = 0.0;
+#pragma unroll
+    for (int k = 0; k < 28; k++) G[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = 0.0;
+#pragma unroll 1
+    for (int v = q; v < nS; v += kDtiLanes) {
+        double x[7], t = 0.0;
+#pragma unroll
+        for (int k = 0; k < 7; k++) { x[k] = xl[v * 7 + k]; t = fma(x[k], p[k], t); }
+        const double e = exp(t), r = sr[v] - e, w = gm_weight(rr[v], C2, wn), we = w * e;
+        c = fma(w * r, r, c);
+#pragma unroll
+        for (int j = 0; j < 7; j++) {
+            const double ex = we * x[j];
+            g[j] = fma(ex, r, g[j]);
+#pragma unroll
+            for (int k = 0; k <= j; k++) G[tri(j, k)] = fma(ex, e * x[k], G[tri(j, k)]);
+        }
+    }
+    c = lanes_sum(c);
+#pragma unroll
+    for (int k0 = 0; k0 < 28; k0 += 7) {
+#pragma unroll
+        for (int k = k0; k < k0 + 7; k++) G[k] = lanes_sum(G[k]);
+        __builtin_amdgcn_sched_barrier(0);
+    }
+#pragma unroll
+    for (int k = 0; k < 7; k++) g[k] = lanes_sum(g[k]);
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// Step 3 for the voxels with `need` set: p1 -> p2.  Returns whether the voxel reached the trip cap or gave up.
+__device__ __forceinline__ bool restore_reweighted(const double *__restrict__ xl, const double *__restrict__ sr, double *rr,
+                                                   int nS, int q, double sigma, bool need, double (&p)[7], int &trips, int &wtrips)
+{
+    bool active = need, gave_up = false;
+    double lam = 1e-3;
+#pragma unroll 1
+    for (int trip = 0; trip < kGmTrips; trip++) {
+        if (!__any(active)) break;
+        wtrips++;
+#pragma unroll 1
+        for (int v = q; v < nS; v += kDtiLanes) {
+            double t = 0.0;
+#pragma unroll
+            for (int k = 0; k < 7; k++) t = fma(xl[v * 7 + k], p[k], t);
+            const double r = sr[v] - exp(t);
+            if (active) rr[v] = r;
+        }
+        row_fence();
+        const double med = row_median<false>(rr, nS, q, 0.0);
+        const double mad = row_median<true>(rr, nS, q, med);
+        const double C = fmax(1.4826 * mad, 1e-6 * sigma), C2 = C * C;
+        double sw = 0.0;
+#pragma unroll 1
+        for (int v = q; v < nS; v += kDtiLanes) sw += gm_weight(rr[v], C2, 1.0);
+        const double wn = (double)nS / lanes_sum(sw);
+        double c, d[7], pt[7];
+        bool ok;
+        {
+            double G[28];
+            gm_pass(xl, sr, rr, nS, q, p, C2, wn, c, G, d);
+            ok = chol_solve7(G, d, lam);
+#pragma unroll
+            for (int k = 0; k < 7; k++) pt[k] = ok ? p[k] + d[k] : p[k];
+        }
+        // the trial: the frozen-weight cost at pt and the largest move of a sample's log-signal
+        double ct = 0.0, dmax = 0.0;
+#pragma unroll 1
+        for (int v = q; v < nS; v += kDtiLanes) {
+            double t = 0.0, u = 0.0;
+#pragma unroll
+            for (int k = 0; k < 7; k++) { const double x = xl[v * 7 + k]; t = fma(x, pt[k], t); u = fma(x, d[k], u); }
+            const double r = sr[v] - exp(t);
+            ct = fma(gm_weight(rr[v], C2, wn) * r, r, ct);
+            dmax = fmax(dmax, fabs(u));
+        }
+        ct = lanes_sum(ct);
+        dmax = lanes_max(dmax);
+        row_fence();                           // the row is read to the end before the next trip rewrites it
+        if (active) {
+            trips++;
+            if (ok && ct <= c) {               // (false for a non-finite trial cost)
+#pragma unroll
+                for (int k = 0; k < 7; k++) p[k] = pt[k];
+                lam = fmax(lam * 0.1, 1e-12);
+                if (dmax <= 1e-10) active = false;
+            } else {
+                lam *= 10.0;
+                if (lam > 1e12) { active = false; gave_up = true; }
+            }
+        }
+    }
+    return gave_up || active;
+}
+
+enum { kDtiWls = AMX_DTI_WLS, kDtiNlls = AMX_DTI_NLLS, kDtiRestore = AMX_DTI_RESTORE };
+
 // y f64|f32[n][nS] -> dirs f64[n][3].  wt7 f64[nS][7]: pinv(X)^T with row k scaled by the column scale of X; xs f64[nS][7]: X
-// with its columns scaled to unit max-abs.  stats (NLLS): [0] voxels that kept their starting parameters, [1] trips of the
-// voxels, [2] trips their wavefronts made for them (a voxel waits for the slowest of the 8 in its wavefront).
+// with its columns scaled to unit max-abs.  stats (NLLS, RESTORE): [0] voxels that kept their starting parameters, [1] trips of the
+// voxels, [2] trips their wavefronts made for them (a voxel waits for the slowest of the 8 in its wavefront); RESTORE: [4] voxels
+// that entered step 3, [5] refitted in step 4, [6] at step 3's cap or give-up, [7] with fewer than 7 inliers; outliers i32[n] or null.
 // MAPS: dti_store's.
-template <typename YT, bool NLLS, bool MAPS>
-__global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const YT *__restrict__ y, const double *__restrict__ wt7,
+template <typename YT, int METHOD, bool MAPS>
+__global__ __launch_bounds__(kDtiThreads, METHOD != kDtiWls ? 1 : 2) void k_dti_dirs_w(const YT *__restrict__ y, const double *__restrict__ wt7,
                                                                         const double *__restrict__ xs, DtiScale sc,
                                                                         int nS, int ldl, int tv, long long n, double min_signal,
                                                                         double *__restrict__ dirs, unsigned long long *__restrict__ stats,
                                                                         double min_diffusivity, double *__restrict__ evals,
-                                                                        double *__restrict__ scalars)
+                                                                        double *__restrict__ scalars, double sigma,
+                                                                        int *__restrict__ outliers)
 {
+    constexpr bool NLLS = METHOD != kDtiWls;           // the non-linear fit runs (RESTORE: as its step 1)
     extern __shared__ double sm[];
     double *wl = sm;                                   // nS * 7
     double *xl = sm + nS * 7;                          // nS * 7 (odd row stride)
     double *yl = sm + ((nS * 14 + 1) & ~1);            // tv * ldl
     double *dl = yl + tv * ldl;                        // kDtiBatch * tv * 7 (6 tensor entries, odd stride)
     double *gl = dl + kDtiBatch * tv * 7;              // NLLS: tv * kDtiNormLd (normal equations of each voxel's accepted point)
+    double *rl = gl + tv * kDtiNormLd;                 // RESTORE: tv * ldl (residual rows)
     const int tid = threadIdx.x;
     for (int i = tid; i < nS * 7; i += kDtiThreads) { wl[i] = wt7[i]; xl[i] = xs[i]; }
     const long long n_tiles = (n + tv - 1) / tv;
@@ -403,66 +666,61 @@ __global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const 
                 ss = fma(sv, sv, ss);
             }
             ss = lanes_sum(ss);
-            // normal equations of the accepted point: parked in LDS between trips (every lane of the voxel writes the same bits
-            // and reads its own back, so no ordering between lanes is needed); registers hold one set of 35 sums at a time
             double *gv = gl + (live ? vox : 0) * kDtiNormLd;
-            double c, p0[7];
-#pragma unroll
-            for (int k = 0; k < 7; k++) p0[k] = p[k];
-            {
-                double G[28], g[7];
-                nlls_pass(xl, yr, nS, q, p, c, G, g);
-                if (live) {
-#pragma unroll
-                    for (int k = 0; k < 28; k++) gv[k] = G[k];
-#pragma unroll
-                    for (int k = 0; k < 7; k++) gv[28 + k] = g[k];
-                }
-            }
-            bool failed = live && !(c < 1e300);
-            bool active = live && !failed;
-            double lam = 1e-3;
-            const double floor_c = 1e-30 * ss;         // an exact fit (7 volumes) ends at rounding noise of the signal, not at zero
             int trips = 0, wtrips = 0;
-#pragma unroll 1
-            for (int trip = 0; trip < kLmTrips; trip++) {
-                if (!__any(active)) break;             // the loop is uniform over the wavefront: the shuffles see every lane
-                wtrips++;
-                double pt[7];
-                bool ok;
-                {
-                    double G[28], g[7];
+            bool failed = nlls_fit<false>(xl, yr, gv, nS, q, 0ull, ss, live, p, trips, wtrips);
+            if constexpr (METHOD == kDtiRestore) {
+                const double thr = 3.0 * sigma;
+                unsigned long long skip;
+                int n_out = restore_verdict(xl, yr, nS, q, p, thr, skip);
+                const bool need = live && n_out > 0;
+                bool capped = false, refit = false, few = false;
+                if (__any(need)) {
+                    // (lanes without a voxel go through the motions on residual row 0, as on signal row 0.  Those of other wavefronts
+                    //  than voxel 0's read it while it is rewritten: what they compute is never stored and every loop is bounded)
+                    capped = restore_reweighted(xl, yr, rl + (live ? vox : 0) * ldl, nS, q, sigma, need, p, trips, wtrips);
+                    n_out = restore_verdict(xl, yr, nS, q, p, thr, skip);
+                    few = need && n_out > 0 && nS - n_out < 7;
+                    refit = need && n_out > 0 && !few;
+                    if (__any(refit)) {
+                        // OLS (the weights of wls_pass at p = 0 are exp(0) = 1), WLS and NLLS over the samples outside O
+                        double pr[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+                        bool ok0;
+                        {
+                            double G[28], g[7];
+                            wls_pass<true>(xl, yr, nS, q, pr, G, g, skip);
+                            ok0 = chol_solve7(G, g, 0.0);
 #pragma unroll
-                    for (int k = 0; k < 28; k++) G[k] = gv[k];
+                            for (int k = 0; k < 7; k++) ok0 = ok0 && fabs(g[k]) < 1e300;
 #pragma unroll
-                    for (int k = 0; k < 7; k++) g[k] = gv[28 + k];
-                    ok = chol_solve7(G, g, lam);
+                            for (int k = 0; k < 7; k++) pr[k] = ok0 ? g[k] : 0.0;
+                            wls_pass<true>(xl, yr, nS, q, pr, G, g, skip);
+                            bool ok = chol_solve7(G, g, 0.0);
 #pragma unroll
-                    for (int k = 0; k < 7; k++) pt[k] = ok ? p[k] + g[k] : p[k];
-                }
-                double ct, Gt[28], gt[7];
-                nlls_pass(xl, yr, nS, q, pt, ct, Gt, gt);
-                if (active) {
-                    trips++;
-                    const bool acc = ok && ct <= c;    // (false for a non-finite trial cost)
-                    const bool flat = ok && fabs(c - ct) <= fma(1e-15, c, floor_c);
-                    if (acc) {
+                            for (int k = 0; k < 7; k++) ok = ok && fabs(g[k]) < 1e300;
 #pragma unroll
-                        for (int k = 0; k < 7; k++) { p[k] = pt[k]; gv[28 + k] = gt[k]; }
+                            for (int k = 0; k < 7; k++) pr[k] = ok ? g[k] : pr[k];
+                        }
+                        const bool bad = nlls_fit<true>(xl, yr, gv, nS, q, skip, ss, refit && ok0, pr, trips, wtrips);
+                        if (refit) {
 #pragma unroll
-                        for (int k = 0; k < 28; k++) gv[k] = Gt[k];
-                        c = ct;
-                        lam = fmax(lam * 0.1, 1e-12);
-                    } else {
-                        lam *= 10.0;
+                            for (int k = 0; k < 7; k++) p[k] = ok0 ? pr[k] : p[k];
+                            failed = failed || bad || !ok0;
+                        }
                     }
-                    if (flat && trip >= 2) active = false;                  // converged: the cost has stopped moving in fp64
-                    else if (lam > 1e12) { active = false; failed = true; }
+                }
+                if (!need) n_out = 0;
+                const bool head = live && q == 0;
+                if (head && outliers) outliers[v0 + vox] = n_out;
+                const int s3 = wave_sum(head && need ? 1 : 0), s4 = wave_sum(head && refit ? 1 : 0),
+                          sc3 = wave_sum(head && capped ? 1 : 0), sf = wave_sum(head && few ? 1 : 0);
+                if ((tid & 63) == 0 && s3) {
+                    atomicAdd(stats + 4, (unsigned long long)s3);
+                    if (s4) atomicAdd(stats + 5, (unsigned long long)s4);
+                    if (sc3) atomicAdd(stats + 6, (unsigned long long)sc3);
+                    if (sf) atomicAdd(stats + 7, (unsigned long long)sf);
                 }
             }
-            failed = failed || active;                 // trip cap
-#pragma unroll
-            for (int k = 0; k < 7; k++) p[k] = failed ? p0[k] : p[k];
             const bool head = live && q == 0;
             const int nf = wave_sum(head && failed ? 1 : 0), vt = wave_sum(head ? trips : 0), wt = wave_sum(head ? wtrips : 0);
             if ((tid & 63) == 0) {
@@ -495,23 +753,19 @@ __global__ __launch_bounds__(kDtiThreads, NLLS ? 1 : 2) void k_dti_dirs_w(const 
 
 }  // namespace amx
 
-extern "C" {
-
-int amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method,
-                          amx_dti **out)
+static int dti_create(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method, double sigma,
+                      amx_dti **out)
 {
     if (!ctx) return AMX_E_BADARG;
     if (!inv_design || !out || nS < 7 || nS > 2048) return amx_bad(ctx, "amx_dti_create: need inv_design f64[7][nS], 7 <= nS <= 2048");
     if (!(min_signal > 0.0)) return amx_bad(ctx, "amx_dti_create: min_signal must be positive");
-    if (method != AMX_DTI_OLS && method != AMX_DTI_WLS && method != AMX_DTI_NLLS)
-        return amx_bad(ctx, "amx_dti_create_method: method must be AMX_DTI_OLS, AMX_DTI_WLS or AMX_DTI_NLLS");
-    if (method != AMX_DTI_OLS && !design) return amx_bad(ctx, "amx_dti_create_method: WLS and NLLS need the design matrix f64[nS][7]");
+    if (method != AMX_DTI_OLS && !design) return amx_bad(ctx, "amx_dti_create_method: WLS, NLLS and RESTORE need the design matrix f64[nS][7]");
     HIPCHK(ctx, hipSetDevice(ctx->device));
     std::vector<double> wt((size_t)nS * 6);
     for (int v = 0; v < nS; v++)
         for (int k = 0; k < 6; k++) wt[(size_t)v * 6 + k] = inv_design[(size_t)k * nS + v];
     amx_dti *h = new amx_dti;
-    h->ctx = ctx; h->nS = nS; h->min_signal = min_signal; h->method = method;
+    h->ctx = ctx; h->nS = nS; h->min_signal = min_signal; h->method = method; h->sigma = sigma;
     hipError_t e = hipMalloc((void **)&h->wt, wt.size() * sizeof(double));
     if (e == hipSuccess) e = hipMemcpy(h->wt, wt.data(), wt.size() * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && method != AMX_DTI_OLS) {
@@ -527,12 +781,12 @@ int amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_
                 tab[(size_t)(nS + v) * 7 + k] = design[(size_t)v * 7 + k] / cs;
             }
         }
-        e = hipMalloc((void **)&h->wt7, tab.size() * sizeof(double) + 4 * sizeof(unsigned long long));
+        e = hipMalloc((void **)&h->wt7, tab.size() * sizeof(double) + kDtiStats * sizeof(unsigned long long));
         if (e == hipSuccess) e = hipMemcpy(h->wt7, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice);
         if (e == hipSuccess) {
             h->xs = h->wt7 + (size_t)nS * 7;
             h->stats = reinterpret_cast<unsigned long long *>(h->wt7 + (size_t)nS * 14);
-            e = hipMemset(h->stats, 0, 4 * sizeof(unsigned long long));
+            e = hipMemset(h->stats, 0, kDtiStats * sizeof(unsigned long long));
         }
     }
     if (e != hipSuccess) {
@@ -544,6 +798,26 @@ int amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_
     }
     *out = h;
     return AMX_OK;
+}
+
+extern "C" {
+
+int amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method,
+                          amx_dti **out)
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (method == AMX_DTI_RESTORE) return amx_bad(ctx, "amx_dti_create_method: RESTORE needs sigma (amx_dti_create_robust)");
+    if (method != AMX_DTI_OLS && method != AMX_DTI_WLS && method != AMX_DTI_NLLS)
+        return amx_bad(ctx, "amx_dti_create_method: method must be AMX_DTI_OLS, AMX_DTI_WLS or AMX_DTI_NLLS");
+    return dti_create(ctx, design, inv_design, nS, min_signal, method, 0.0, out);
+}
+
+int amx_dti_create_robust(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, double sigma,
+                          amx_dti **out)
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (!(sigma > 0.0) || !std::isfinite(sigma)) return amx_bad(ctx, "amx_dti_create_robust: sigma must be a finite number > 0");
+    return dti_create(ctx, design, inv_design, nS, min_signal, AMX_DTI_RESTORE, sigma, out);
 }
 
 int amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_signal, amx_dti **out)
@@ -560,12 +834,12 @@ void amx_dti_destroy(amx_dti *h)
     delete h;
 }
 
-static int dti_read_stats(amx_ctx *ctx, const amx_dti *h, unsigned long long (&st)[3])
+static int dti_read_stats(amx_ctx *ctx, const amx_dti *h, unsigned long long (&st)[kDtiStats])
 {
     if (!ctx) return AMX_E_BADARG;
     if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_last_stats: not an estimator of this ctx");
-    st[0] = st[1] = st[2] = 0;
-    if (h->method != AMX_DTI_NLLS) return AMX_OK;
+    for (int k = 0; k < kDtiStats; k++) st[k] = 0;
+    if (h->method != AMX_DTI_NLLS && h->method != AMX_DTI_RESTORE) return AMX_OK;
     HIPCHK(ctx, hipSetDevice(ctx->device));
     HIPCHK(ctx, hipStreamSynchronize(h->last_stream));
     HIPCHK(ctx, hipMemcpy(st, h->stats, sizeof st, hipMemcpyDeviceToHost));
@@ -575,7 +849,7 @@ static int dti_read_stats(amx_ctx *ctx, const amx_dti *h, unsigned long long (&s
 int amx_dti_last_unconverged(amx_ctx *ctx, const amx_dti *h, int64_t *out)
 {
     if (ctx && !out) return amx_bad(ctx, "amx_dti_last_unconverged: null output");
-    unsigned long long st[3];
+    unsigned long long st[kDtiStats];
     const int rc = dti_read_stats(ctx, h, st);
     if (rc == AMX_OK) *out = (int64_t)st[0];
     return rc;
@@ -584,33 +858,51 @@ int amx_dti_last_unconverged(amx_ctx *ctx, const amx_dti *h, int64_t *out)
 int amx_dti_last_trips(amx_ctx *ctx, const amx_dti *h, int64_t *out_voxel_trips, int64_t *out_wavefront_trips)
 {
     if (ctx && (!out_voxel_trips || !out_wavefront_trips)) return amx_bad(ctx, "amx_dti_last_trips: null output");
-    unsigned long long st[3];
+    unsigned long long st[kDtiStats];
     const int rc = dti_read_stats(ctx, h, st);
     if (rc == AMX_OK) { *out_voxel_trips = (int64_t)st[1]; *out_wavefront_trips = (int64_t)st[2]; }
     return rc;
 }
 
+int amx_dti_last_robust(amx_ctx *ctx, const amx_dti *h, int64_t out[4])
+{
+    if (ctx && !out) return amx_bad(ctx, "amx_dti_last_robust: null output");
+    unsigned long long st[kDtiStats];
+    const int rc = dti_read_stats(ctx, h, st);
+    if (rc == AMX_OK)
+        for (int k = 0; k < 4; k++) out[k] = (int64_t)st[4 + k];
+    return rc;
+}
+
 }  // extern "C"
 
-// what amx_dti_fit* adds to amx_dti_directions*
-struct DtiMapsOut { double min_diffusivity; double *evals, *scalars; };
+// what amx_dti_fit* adds to amx_dti_directions*, and amx_dti_fit_robust* to those
+struct DtiMapsOut { double min_diffusivity; double *evals, *scalars; int32_t *outliers = nullptr; };
 
-template <typename YT, bool NLLS, bool MAPS>
+template <typename YT, int METHOD, bool MAPS>
 static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double *d_dirs, hipStream_t s,
                                 const DtiMapsOut &mo)
 {
     const int nS = h->nS;
     int ldl = (nS + 3) & ~3;
     if (((ldl >> 2) & 1) == 0) ldl += 4;
+    constexpr bool NLLS = METHOD != kDtiWls, RESTORE = METHOD == kDtiRestore;
     int tv = (kDtiPre * 2 * kDtiThreads) / nS;
     tv = tv > kDtiVox ? kDtiVox : (tv & ~1);
-    // the two [nS][7] tables (scaled pinv, scaled design matrix), the signal rows, the tensors of a batch, NLLS' normal equations
-    const size_t lds = ((size_t)((nS * 14 + 1) & ~1) + (size_t)tv * ldl + (size_t)kDtiBatch * tv * 7 +
-                        (NLLS ? (size_t)tv * kDtiNormLd : 0)) * sizeof(double);
+    // the two [nS][7] tables (scaled pinv, scaled design matrix), the signal rows, the tensors of a batch, NLLS' normal equations,
+    // RESTORE's residual rows -- which make its tile the shorter one on long schemes
+    const size_t fixed = (size_t)((nS * 14 + 1) & ~1);
+    const size_t per_vox = (size_t)ldl * (RESTORE ? 2 : 1) + (size_t)kDtiBatch * 7 + (NLLS ? (size_t)kDtiNormLd : 0);
+    if (RESTORE) {
+        if (nS > 64 * kDtiLanes) return amx_bad(ctx, "amx_dti_directions: scheme too long for the LDS tile (RESTORE: at most 512 volumes)");
+        const int fit = (int)((160 * 1024 / sizeof(double) - fixed) / per_vox) & ~1;
+        tv = tv < fit ? tv : fit;
+    }
+    const size_t lds = (fixed + (size_t)tv * per_vox) * sizeof(double);
     if (tv < 2 || lds > 160 * 1024) return amx_bad(ctx, "amx_dti_directions: scheme too long for the LDS tile");
     static bool attr_set[64];
     if (!attr_set[ctx->device & 63]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs_w<YT, NLLS, MAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_dti_dirs_w<YT, METHOD, MAPS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
         attr_set[ctx->device & 63] = true;
     }
     const long long n_tiles = (n_vox + tv - 1) / tv;
@@ -619,11 +911,11 @@ static int dti_directions_w_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, i
     if (grid > n_tiles) grid = n_tiles;
     DtiScale sc;
     for (int k = 0; k < 7; k++) sc.ics[k] = h->ics[k];
-    if (NLLS) HIPCHK(ctx, hipMemsetAsync(h->stats, 0, 4 * sizeof(unsigned long long), s));
+    if (NLLS) HIPCHK(ctx, hipMemsetAsync(h->stats, 0, kDtiStats * sizeof(unsigned long long), s));
     h->last_stream = s;
     rec(ctx, 8, s);
-    hipLaunchKernelGGL((k_dti_dirs_w<YT, NLLS, MAPS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt7, h->xs, sc, nS, ldl, tv,
-                       (long long)n_vox, h->min_signal, d_dirs, h->stats, mo.min_diffusivity, mo.evals, mo.scalars);
+    hipLaunchKernelGGL((k_dti_dirs_w<YT, METHOD, MAPS>), dim3((unsigned)grid), dim3(kDtiThreads), lds, s, d_y, h->wt7, h->xs, sc, nS, ldl, tv,
+                       (long long)n_vox, h->min_signal, d_dirs, h->stats, mo.min_diffusivity, mo.evals, mo.scalars, h->sigma, mo.outliers);
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, s);
     return AMX_OK;
@@ -642,8 +934,9 @@ static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int
     if (sizeof(YT) == 8 && ((uintptr_t)d_y & 15) != 0) return amx_bad(ctx, "amx_dti_directions: y must be 16-byte aligned");
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
-    if (h->method == AMX_DTI_WLS) return dti_directions_w_dev<YT, false, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
-    if (h->method == AMX_DTI_NLLS) return dti_directions_w_dev<YT, true, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
+    if (h->method == AMX_DTI_WLS) return dti_directions_w_dev<YT, kDtiWls, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
+    if (h->method == AMX_DTI_NLLS) return dti_directions_w_dev<YT, kDtiNlls, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
+    if (h->method == AMX_DTI_RESTORE) return dti_directions_w_dev<YT, kDtiRestore, MAPS>(ctx, h, d_y, n_vox, d_dirs, s, mo);
     const int nS = h->nS;
     int ldl = (nS + 3) & ~3;                  // row stride = 4 * odd doubles: the 16 quads of a wavefront read
     if (((ldl >> 2) & 1) == 0) ldl += 4;      // conflict-free LDS rows
@@ -672,11 +965,46 @@ static int dti_directions_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int
 // the same kernel, the same launch.
 template <typename YT>
 static int dti_fit_dev(amx_ctx *ctx, const amx_dti *h, const YT *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
-                       double *d_evals, double *d_scalars, void *hip_stream)
+                       double *d_evals, double *d_scalars, void *hip_stream, int32_t *d_outliers = nullptr)
 {
-    if (!d_evals && !d_scalars)
-        return dti_directions_dev<YT, false>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{0.0, nullptr, nullptr});
-    return dti_directions_dev<YT, true>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{min_diffusivity, d_evals, d_scalars});
+    // (the outlier counts alone: the MAPS variant, whose every output may be null -- the direction kernel stores its directions unasked)
+    if (!d_evals && !d_scalars && (d_dirs || !d_outliers))
+        return dti_directions_dev<YT, false>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{0.0, nullptr, nullptr, d_outliers});
+    return dti_directions_dev<YT, true>(ctx, h, d_y, n_vox, d_dirs, hip_stream, DtiMapsOut{min_diffusivity, d_evals, d_scalars, d_outliers});
+}
+
+// amx_dti_fit_robust*: a RESTORE estimator and nothing else
+static int dti_robust_handle(amx_ctx *ctx, const amx_dti *h)
+{
+    if (!ctx) return AMX_E_BADARG;
+    if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_directions: not an estimator of this ctx");
+    if (h->method != AMX_DTI_RESTORE) return amx_bad(ctx, "amx_dti_fit_robust: not a RESTORE estimator (amx_dti_create_robust)");
+    return AMX_OK;
+}
+
+// amx_dti_fit and amx_dti_fit_robust
+static int dti_fit_host(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double min_diffusivity, double *out_dirs,
+                        double *out_evals, double *out_scalars, int32_t *out_outliers)
+{
+    if (n_vox == 0) return AMX_OK;
+    if (n_vox < 0 || !y || (!out_dirs && !out_evals && !out_scalars && !out_outliers)) return amx_bad(ctx, "amx_dti_directions: bad argument");
+    HIPCHK(ctx, hipSetDevice(ctx->device));
+    int rc;
+    // one device buffer behind y's: 3 + 3 + 4 doubles per voxel, and the outlier counts
+    const size_t yb = (size_t)n_vox * h->nS * sizeof(double), vb = (size_t)n_vox * sizeof(double);
+    if ((rc = amx_ensure(ctx, ctx->hy, yb))) return rc;
+    if ((rc = amx_ensure(ctx, ctx->hdirs, 10 * vb + (size_t)n_vox * sizeof(int32_t)))) return rc;
+    double *dd = (double *)ctx->hdirs.p, *de = dd + 3 * n_vox, *ds = dd + 6 * n_vox;
+    int32_t *dout = (int32_t *)(dd + 10 * n_vox);
+    HIPCHK(ctx, hipMemcpyAsync(ctx->hy.p, y, yb, hipMemcpyHostToDevice, nullptr));
+    if ((rc = dti_fit_dev<double>(ctx, h, (const double *)ctx->hy.p, n_vox, min_diffusivity, out_dirs ? dd : nullptr, out_evals ? de : nullptr,
+                                  out_scalars ? ds : nullptr, nullptr, out_outliers ? dout : nullptr))) return rc;
+    if (out_dirs) HIPCHK(ctx, hipMemcpyAsync(out_dirs, dd, 3 * vb, hipMemcpyDeviceToHost, nullptr));
+    if (out_evals) HIPCHK(ctx, hipMemcpyAsync(out_evals, de, 3 * vb, hipMemcpyDeviceToHost, nullptr));
+    if (out_scalars) HIPCHK(ctx, hipMemcpyAsync(out_scalars, ds, 4 * vb, hipMemcpyDeviceToHost, nullptr));
+    if (out_outliers) HIPCHK(ctx, hipMemcpyAsync(out_outliers, dout, (size_t)n_vox * sizeof(int32_t), hipMemcpyDeviceToHost, nullptr));
+    HIPCHK(ctx, hipStreamSynchronize(nullptr));
+    return AMX_OK;
 }
 
 extern "C" {
@@ -726,23 +1054,28 @@ int amx_dti_fit(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, 
 {
     if (!ctx) return AMX_E_BADARG;
     if (!h || h->ctx != ctx) return amx_bad(ctx, "amx_dti_directions: not an estimator of this ctx");
-    if (n_vox == 0) return AMX_OK;
-    if (n_vox < 0 || !y || (!out_dirs && !out_evals && !out_scalars)) return amx_bad(ctx, "amx_dti_directions: bad argument");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    // one device buffer behind y's: 3 + 3 + 4 doubles per voxel
-    const size_t yb = (size_t)n_vox * h->nS * sizeof(double), vb = (size_t)n_vox * sizeof(double);
-    if ((rc = amx_ensure(ctx, ctx->hy, yb))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hdirs, 10 * vb))) return rc;
-    double *dd = (double *)ctx->hdirs.p, *de = dd + 3 * n_vox, *ds = dd + 6 * n_vox;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hy.p, y, yb, hipMemcpyHostToDevice, nullptr));
-    if ((rc = amx_dti_fit_device(ctx, h, (const double *)ctx->hy.p, n_vox, min_diffusivity, out_dirs ? dd : nullptr,
-                                 out_evals ? de : nullptr, out_scalars ? ds : nullptr, nullptr))) return rc;
-    if (out_dirs) HIPCHK(ctx, hipMemcpyAsync(out_dirs, dd, 3 * vb, hipMemcpyDeviceToHost, nullptr));
-    if (out_evals) HIPCHK(ctx, hipMemcpyAsync(out_evals, de, 3 * vb, hipMemcpyDeviceToHost, nullptr));
-    if (out_scalars) HIPCHK(ctx, hipMemcpyAsync(out_scalars, ds, 4 * vb, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(ctx, hipStreamSynchronize(nullptr));
-    return AMX_OK;
+    return dti_fit_host(ctx, h, y, n_vox, min_diffusivity, out_dirs, out_evals, out_scalars, nullptr);
+}
+
+int amx_dti_fit_robust_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                              double *d_evals, double *d_scalars, int32_t *d_outliers, void *hip_stream)
+{
+    const int rc = dti_robust_handle(ctx, h);
+    return rc ? rc : dti_fit_dev<double>(ctx, h, d_y, n_vox, min_diffusivity, d_dirs, d_evals, d_scalars, hip_stream, d_outliers);
+}
+
+int amx_dti_fit_robust_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
+                                  double *d_evals, double *d_scalars, int32_t *d_outliers, void *hip_stream)
+{
+    const int rc = dti_robust_handle(ctx, h);
+    return rc ? rc : dti_fit_dev<float>(ctx, h, d_y, n_vox, min_diffusivity, d_dirs, d_evals, d_scalars, hip_stream, d_outliers);
+}
+
+int amx_dti_fit_robust(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double min_diffusivity, double *out_dirs,
+                       double *out_evals, double *out_scalars, int32_t *out_outliers)
+{
+    const int rc = dti_robust_handle(ctx, h);
+    return rc ? rc : dti_fit_host(ctx, h, y, n_vox, min_diffusivity, out_dirs, out_evals, out_scalars, out_outliers);
 }
 
 }  // extern "C"

@@ -391,19 +391,45 @@ int  amx_dti_create(amx_ctx *ctx, const double *inv_design, int nS, double min_s
  *        cost stops moving in fp64 -- MINPACK at dipy's default tolerances stops earlier, so the two agree to MINPACK's
  *        stopping rule, not to rounding.  A voxel that reaches the trip cap or a non-finite value keeps the WLS parameters
  *        and is counted (amx_dti_last_unconverged); no error is raised, as in the reference.
- * 'RT' / 'RESTORE' are not built: the reference's call passes no sigma and raises inside dipy for them.
+ *   RESTORE ('RT' | 'RESTORE' | 'restore'; dipy/reconst/dti.py: restore_fit_tensor; Chang, Jones & Pierpaoli 2005)  needs the
+ *        noise level sigma > 0 in the units of y, one scalar per estimator (amx_dti_create_robust): the reference's own call passes
+ *        none and raises inside dipy.  Per voxel:
+ *          1. p1 = the NLLS fit above, by the arithmetic above (dipy's 1 / sigma^2 weights do not move the minimum)
+ *          2. r = s - exp(X p1);  no |r_i| > 3 sigma: done, p = p1, 0 outliers
+ *          3. the Geman-McClure fit as a fixed point, from p1.  One trip: r at p;  C = max(1.4826 median|r - median(r)|,
+ *             1e-6 sigma) (numpy's median);  w_i = 1 / (r_i^2 + C^2) / mean(w);  ONE Levenberg-Marquardt trial on
+ *             sum w_i (s_i - exp(X_i p))^2 with w frozen (J = exp(X p) (.) X, (J'WJ + lam diag) d = J'Wr, accepted when the
+ *             frozen-weight cost does not rise; lam as in NLLS: 1e-3 at the start, x 0.1 on accept with floor 1e-12, x 10 on reject, give
+ *             up above 1e12).  Converged when an accepted step has max_i |X_i d| <= 1e-10.  At most 1024 trips; a voxel at the cap
+ *             or giving up keeps its last accepted iterate and is counted (amx_dti_last_robust).
+ *          4. r = s - exp(X p2), O = {i : |r_i| > 3 sigma}.  O empty: p = p2.  Fewer than 7 samples outside O: p = p2, counted.
+ *             Otherwise the samples outside O are fitted anew: OLS, WLS and NLLS as above over those samples.  A failed NLLS keeps
+ *             the WLS parameters of those samples, a failed OLS (a singular system) keeps p2; both are counted in
+ *             amx_dti_last_unconverged.
+ *          5. tensor -> direction (evals, scalars) as above;  outliers = |O|, 0 for a voxel that ended at step 2.
+ *        This is restore_fit_tensor in structure.  Two differences are deliberate.  Step 3 is a defined fixed point, the
+ *        iteratively reweighted fit of Chang et al.: dipy hands MINPACK a cost whose weights move under it, with a Jacobian that
+ *        ignores them.  And every fit runs to its minimum, not to MINPACK's default tolerances.  With a sigma so large that no
+ *        sample is ever an outlier the outputs are NLLS's, bit for bit.  Schemes of up to 512 volumes.
  * design f64[nS][7] (host, C-order) = dipy.reconst.dti.design_matrix(gtab), needed for WLS / NLLS (may be NULL for OLS);
  * both fits run in fp64 on the design matrix with its columns scaled to unit max-abs.  Schemes whose two [nS][7] tables and
  * signal tile exceed the 160 KB of LDS are refused by amx_dti_directions* ("scheme too long").                              */
-enum { AMX_DTI_OLS = 0, AMX_DTI_WLS = 1, AMX_DTI_NLLS = 2 };
+enum { AMX_DTI_OLS = 0, AMX_DTI_WLS = 1, AMX_DTI_NLLS = 2, AMX_DTI_RESTORE = 3 };
 int  amx_dti_create_method(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, int method,
                            amx_dti **out);
+/* the RESTORE estimator (amx_dti_create_method refuses AMX_DTI_RESTORE: it has no sigma); AMX_E_BADARG unless sigma is finite and > 0 */
+int  amx_dti_create_robust(amx_ctx *ctx, const double *design, const double *inv_design, int nS, double min_signal, double sigma,
+                           amx_dti **out);
 void amx_dti_destroy(amx_dti *h);
-/* voxels of the last NLLS call on this handle that kept their starting parameters (0 for the other methods); waits for that call */
+/* voxels of the last NLLS / RESTORE call on this handle that kept their starting parameters (0 for the other methods; RESTORE: of
+ * step 1 or of step 4); waits for that call */
 int amx_dti_last_unconverged(amx_ctx *ctx, const amx_dti *h, int64_t *out);
-/* Levenberg-Marquardt trips of the last NLLS call: summed over its voxels, and summed over the trips their wavefronts ran for
- * them (a voxel that has converged idles until the last of the 8 voxels of its wavefront has)                                */
+/* Levenberg-Marquardt trips of the last NLLS / RESTORE call: summed over its voxels, and summed over the trips their wavefronts ran
+ * for them (a voxel that has converged idles until the last of the 8 voxels of its wavefront has).  RESTORE: steps 1, 3 and 4. */
 int amx_dti_last_trips(amx_ctx *ctx, const amx_dti *h, int64_t *out_voxel_trips, int64_t *out_wavefront_trips);
+/* the last RESTORE call (zeros for the other methods): out[0] voxels that entered step 3, [1] voxels refitted in step 4, [2] voxels at
+ * the trip cap or give-up of step 3, [3] voxels left with fewer than 7 samples outside O; waits for that call */
+int amx_dti_last_robust(amx_ctx *ctx, const amx_dti *h, int64_t out[4]);
 /* y f64[n_vox][nS] -> dirs f64[n_vox][3]; host buffers (blocking) / device buffers (enqueued on hip_stream) */
 int amx_dti_directions(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double *out_dirs);
 /* (_f32: float32 signals, the dtype amx_prep_gather_device_f32 leaves them in -- same arithmetic, half the bytes)                */
@@ -430,6 +456,16 @@ int amx_dti_fit_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int
                            double *d_evals, double *d_scalars, void *hip_stream);
 int amx_dti_fit_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double min_diffusivity, double *d_dirs,
                        double *d_evals, double *d_scalars, void *hip_stream);
+/* amx_dti_fit* of a RESTORE estimator (AMX_E_BADARG for any other), and outliers int32[n_vox] = |O| of step 4 (may be NULL; the host
+ * call needs one output).  amx_dti_directions*, amx_dti_fit* and amx_prep_gather_directions_device_f32 take a RESTORE estimator too
+ * and are this call without the outlier output.  Odd samples are NLLS's: a NaN or a sample below min_signal counts as min_signal
+ * (and may then be an outlier like any sample); a +Inf sample leaves NaN parameters, no outlier and NaN evals and scalars. */
+int amx_dti_fit_robust(amx_ctx *ctx, const amx_dti *h, const double *y, int64_t n_vox, double min_diffusivity, double *out_dirs,
+                       double *out_evals, double *out_scalars, int32_t *out_outliers);
+int amx_dti_fit_robust_device_f32(amx_ctx *ctx, const amx_dti *h, const float *d_y, int64_t n_vox, double min_diffusivity,
+                                  double *d_dirs, double *d_evals, double *d_scalars, int32_t *d_outliers, void *hip_stream);
+int amx_dti_fit_robust_device(amx_ctx *ctx, const amx_dti *h, const double *d_y, int64_t n_vox, double min_diffusivity,
+                              double *d_dirs, double *d_evals, double *d_scalars, int32_t *d_outliers, void *hip_stream);
 
 /* (f2, f3) signal preparation and result scatter, fused around the masked voxel list:
  *   core.py:209-223  mean_b0s = mean(img[..., b0_idx], axis=3); norm_factor = 1 / mean_b0s, 0 where
