@@ -34,6 +34,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
+           'amx_noise_b0_rows_device', 'amx_noise_b0_rows_device_f32', 'amx_prep_noise_b0_device', 'amx_nanmedian_device',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample',
@@ -225,6 +226,10 @@ def lib():
     L.amx_prep_debias.argtypes = [c_vp, c_vp, c_fp, C.c_double]
     L.amx_prep_debias_device.argtypes = [c_vp, c_vp, c_vp, C.c_double, c_vp]
     L.amx_debias_last_unconverged.argtypes = [c_vp, C.POINTER(C.c_int64)]
+    for f_ in (L.amx_noise_b0_rows_device, L.amx_noise_b0_rows_device_f32):
+        f_.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, c_i32p, C.c_int, c_vp, c_vp, c_vp, c_vp]      # ctx, S, n, nS, b0_idx (host), n_b0, mean, sd, ratio, stream
+    L.amx_prep_noise_b0_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]                 # ctx, plan, img, mean, sd, ratio, stream
+    L.amx_nanmedian_device.argtypes = [c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]                      # ctx, v, n, out[2], count, stream
     L.amx_prep_sanitize.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
     L.amx_prep_sanitize_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp]
     L.amx_sanitize_device_f32.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_float, c_vp]
@@ -947,7 +952,8 @@ class Prep:
         gidx = np.ascontiguousarray(np.concatenate([np.asarray(g, dtype=np.int32).ravel() for g in groups]), dtype=np.int32)
         b0 = np.ascontiguousarray(b0_idx, dtype=np.int32)
         self.n_out = len(groups)
-        self.extent = 1 + sum((d - 1) * s for d, s in zip(self.shape, self.strides))
+        self.n_b0 = len(b0)
+        self.extent =1 + sum((d - 1) * s for d, s in zip(self.shape, self.strides))
         self._h = c_vp()
         ctx.check(lib().amx_prep_create(ctx._h, _p(dims, c_i64p), _p(st, c_i64p), self.shape[3], _p(rank, c_i32p),
                                         self.n_vox, _p(gptr, c_i32p), _p(gidx, c_i32p), self.n_out,
@@ -1031,6 +1037,13 @@ class Prep:
     def debias_device(self, d_img, snr, stream=None):
         """device pointer (int) of the image's element buffer, in place, enqueued on `stream`"""
         self.ctx.check(lib().amx_prep_debias_device(self.ctx._h, self._h, c_vp(d_img), float(snr), c_vp(stream or 0)))
+
+    def noise_b0_device(self, d_img, d_mean=None, d_sd=None, d_ratio=None, stream=None):
+        """device pointers (ints): the image's element buffer -> mean, sample standard deviation (ddof = 1) and mean / sd of the b0
+        repeats of the voxels with mask == 1, f64 [n_vox] each in the plan's masked order, NaN where a voxel is not eligible; any of the
+        three may be None, not all (amx_prep_noise_b0_device); enqueued on `stream`"""
+        self.ctx.check(lib().amx_prep_noise_b0_device(self.ctx._h, self._h, c_vp(d_img), c_vp(d_mean or 0), c_vp(d_sd or 0), c_vp(d_ratio or 0),
+                                                      c_vp(stream or 0)))
 
     def sanitize(self, img, replace=None):
         """host image: -> number of NaN / Inf samples; with `replace` (a finite number) they are overwritten IN PLACE with float32(replace),
@@ -1202,6 +1215,21 @@ def debias_rows(ctx, S, b0_idx, snr):
     fn = lib().amx_debias_rows_f32 if f32 else lib().amx_debias_rows
     ctx.check(fn(ctx._h, _p(S, c_fp if f32 else c_dp), S.shape[0], S.shape[1], _p(b0, c_i32p), len(b0), float(snr), _p(E, c_dp)))
     return E
+
+
+def noise_b0_rows_device(ctx, d_S, n, nS, b0_idx, d_mean=None, d_sd=None, d_ratio=None, stream=None, f32=False):
+    """device pointers (ints): rows S f64 | f32 (f32=True) [n, nS] -> mean, sd (ddof = 1) and mean / sd of the samples b0_idx (host, in
+    that order), f64 [n] each, NaN where a row is not eligible; any of the three may be None, not all (amx_noise_b0_rows_device[_f32])"""
+    b0 = np.ascontiguousarray(b0_idx, dtype=np.int32).ravel()
+    fn = lib().amx_noise_b0_rows_device_f32 if f32 else lib().amx_noise_b0_rows_device
+    ctx.check(fn(ctx._h, c_vp(d_S or 0), int(n), int(nS), _p(b0, c_i32p), len(b0), c_vp(d_mean or 0), c_vp(d_sd or 0), c_vp(d_ratio or 0),
+                 c_vp(stream or 0)))
+
+
+def nanmedian_device(ctx, d_v, n, d_out, d_count, stream=None):
+    """device pointers (ints): v f64 [n] -> out f64 [2] = the lower and upper middle of its non-NaN values, count int64 [1] = how many
+    there are (0: both NaN); numpy's nanmedian is (out[0] + out[1]) / 2 (amx_nanmedian_device); enqueued on `stream`"""
+    ctx.check(lib().amx_nanmedian_device(ctx._h, c_vp(d_v or 0), int(n), c_vp(d_out or 0), c_vp(d_count or 0), c_vp(stream or 0)))
 
 
 def lut_resample(ctx, lm, ylm_out, idx_out, nS):

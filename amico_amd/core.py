@@ -7,6 +7,7 @@ in-memory volumes, every per-voxel step on the GPU:
              NaN / Inf scan of the raw image, replacement with replace_bad_voxels (core.py:152-158)    (amx_prep_sanitize);
              CONFIG['bad_samples_raw'] = samples found; the same for ``y`` after the gather (core.py:270-276) (amx_sanitize),
              CONFIG['bad_samples_preprocessed']
+             with doEstimateNoise: SNR and sigma from the spread of the b0 repeats (amx_prep_noise_b0, amx_nanmedian; not the reference's);
              Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
@@ -27,6 +28,7 @@ from . import _capi
 from . import prep as _prep
 from . import dti as _dti
 from . import bootstrap as _bootstrap
+from . import noise as _noise
 from .synthetic import SimpleScheme
 
 
@@ -68,6 +70,9 @@ class Evaluation:
         self.set_config('DTI_sigma', None)             # not a key of the reference: see fit()
         self.set_config('BLAS_nthreads', 1)
         self.set_config('doSaveTensorMaps', False)     # not a key of the reference: see fit()
+        self.set_config('doEstimateNoise', False)      # not a key of the reference: see fit()
+        self._estimate_noise = False                   # the key as set_data() read it
+        self._debias_estimated = False                 # doDebiasSignal without DWI-SNR: fit() fills the estimate in
 
     # `niiDWI_img` (core.py:136) is the raw float32 image.  When set_data kept the image in its stored dtype the float32 array is made
     # on first read, by the numpy expression the ingest kernel is held to, and cached; fit() itself never needs it
@@ -139,10 +144,13 @@ class Evaluation:
         _prep.check_replace_bad_voxels(replace_bad_voxels)                       # before any context is made or anything uploaded
         scaling = _prep.check_scaling(scaling)
         self.set_config('replace_bad_voxels', replace_bad_voxels)               # core.py:134
+        estimate = bool(self.get_config('doEstimateNoise'))
+        if estimate:
+            _noise.check_b0_count(scheme.b0_count)                               # (RuntimeError naming the key, before anything is uploaded)
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
             debias_snr = self.get_config('DWI-SNR')
-            if debias_snr is None:
+            if debias_snr is None and not estimate:
                 raise RuntimeError('Set noise variance for debiasing (eg. ae.set_config(\'RicianNoiseSigma\', sigma))')   # core.py:205
             if scheme.b0_count == 0:
                 raise RuntimeError('No b0 volume to estimate the noise level from (doDebiasSignal)')   # preproc.py:30-31
@@ -178,6 +186,10 @@ class Evaluation:
             do_merge_b0=self.get_config('doMergeB0'), do_directional_average=self.get_config('doDirectionalAverage'),
             b0_min_signal=b0_min_signal, debias_snr=debias_snr, replace_bad_voxels=replace_bad_voxels,
             scaling=scaling if self._raw is not None else None)
+        self._estimate_noise = estimate
+        self._debias_estimated = bool(self.get_config('doDebiasSignal')) and debias_snr is None      # (only with the key: see above)
+        if self._debias_estimated:
+            self._prep._plan.set_debias_mask(self.niiMASK_img)                   # the SNR comes in fit(); the mask is known now
         # the scheme the model sees: one row per shell after the directional average (core.py:254-255)
         self.scheme = SimpleScheme(_prep.directional_average_table(scheme), scheme.b0_thr) \
             if self.get_config('doDirectionalAverage') else scheme
@@ -264,6 +276,18 @@ class Evaluation:
             counters of `TensorDirections.last_robust` after the fit; with doSaveTensorMaps RESULTS['DTI_outliers'] float32 [X, Y, Z]
             is the number of samples left out per voxel (zero outside the mask), and Free-Water's second tensor fit on the corrected
             rows is robust too and leaves RESULTS['DTI_outliers_corrected'].  The volume pipelines (pipeline.py) do not take it.
+        doEstimateNoise         (default False; read by set_data like the other preprocessing keys) the noise level from the spread of the
+            b0 repeats (amico_amd.noise), taken in HBM directly after the ingest / scan kernel and before the debias: one
+            kernel over the b0 samples of the voxels with mask == 1, two exact medians, one small wait.  It leaves
+            CONFIG['DWI-SNR_estimated'], ['noise_sigma_estimated'] (image units) and ['noise_voxels'] (eligible voxels: finite b0
+            samples, a positive mean and a spread; none is a RuntimeError) and RESULTS['NOISE_MAPs'] float32 [X, Y, Z, 2] = b0 mean and
+            b0 sample standard deviation (ddof = 1, uncorrected), zero outside the mask and where the voxel was not eligible.  The scheme
+            needs 2 to 128 b0 volumes (RuntimeError in set_data otherwise).  An explicit DWI-SNR or DTI_sigma always wins and the
+            estimate is still reported.  With DWI-SNR None, doDebiasSignal no longer raises in set_data and debiases with the estimated
+            SNR; a robust DTI_fit_method without DTI_sigma takes 1 / SNR_est on normalised signals (the rule above) and
+            noise_sigma_estimated otherwise -- `y` is in image units then, which an SNR alone cannot be turned into.  Without the key
+            every call, its order and every result and error are what they were.  The volume pipelines (pipeline.py), the host path
+            SignalPreparation.gather and models.X().fit(evaluation) do not take it.
         doSaveTensorMaps        (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
@@ -290,10 +314,13 @@ class Evaluation:
             raise RuntimeError('Response functions were not created with the same model')
         _dti.check_fit_method(self.get_config('DTI_fit_method'))     # core.py:419-420: before anything is uploaded
         dti_sigma = None
+        normalized = False
         if self.get_config('DTI_fit_method') in _dti.ROBUST_METHODS:
-            # (ValueError for a bad DTI_sigma / DWI-SNR; None leaves the refusal to where the tensor fit would run)
+            normalized = bool(self.get_config('doNormalizeSignal')) and self.scheme.b0_count > 0
+            # (ValueError for a bad DTI_sigma / DWI-SNR; None leaves the refusal to where the tensor fit would run -- or, with
+            #  doEstimateNoise, the choice to the estimate, once it is there)
             dti_sigma = _dti.resolve_sigma(self.get_config('DTI_fit_method'), self.get_config('DTI_sigma'), self.get_config('DWI-SNR'),
-                                           bool(self.get_config('doNormalizeSignal')) and self.scheme.b0_count > 0)
+                                           normalized)
         if tensor_maps and len(_models.get_contexts()) > 1:
             raise NotImplementedError('doSaveTensorMaps is not built for several devices (set_devices)')
         if self.get_config('doSavePredictedSignal') and len(_models.get_contexts()) > 1:
@@ -330,9 +357,30 @@ class Evaluation:
         self.set_config('bad_samples_raw', ctx.sanitize_last())
         d_raw = None
         _prep.refuse_or_warn(self.get_config('bad_samples_raw'), bad_value, _prep.BAD_RAW)
-        if self._prep.debias_snr is not None:
+        debias_snr = self._prep.debias_snr
+        d_noise = None
+        if self._estimate_noise:
+            # doEstimateNoise: on the raw float32 image, before the debias changes it -- one k_noise_b0 launch, two medians, and one
+            # small wait like the scan count's above.  An explicit DWI-SNR / DTI_sigma wins; the estimate is reported either way.
+            noise = _noise.estimate_device(plan, d_img.data_ptr())
+            self.set_config('DWI-SNR_estimated', noise['snr'])
+            self.set_config('noise_sigma_estimated', noise['sigma'])
+            self.set_config('noise_voxels', noise['voxels'])
+            if noise['voxels'] == 0:
+                raise RuntimeError('doEstimateNoise: no voxel of the mask has b0 repeats to estimate the noise from (finite samples, a '
+                                   'positive mean and a spread are needed)')
+            # b0 mean and sample standard deviation (ddof = 1), zero where the voxel was not eligible: scattered with the results below
+            d_noise = torch.nan_to_num(torch.stack((noise['mean'], noise['sd']), dim=1), nan=0.0).contiguous()
+            if self._debias_estimated:
+                debias_snr = noise['snr']
+            if self.get_config('DTI_fit_method') in _dti.ROBUST_METHODS and dti_sigma is None:
+                # resolve_sigma's rule with the estimate in DWI-SNR's place: 1 / SNR on normalised signals; otherwise y is in image units
+                # and the estimate has the unit an SNR lacks
+                dti_sigma = _dti.resolve_sigma(self.get_config('DTI_fit_method'), None, noise['snr'], True) if normalized \
+                    else _capi.check_sigma(noise['sigma'])
+        if debias_snr is not None:
             # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
-            self._prep._plan.debias_device(d_img.data_ptr(), self._prep.debias_snr)
+            self._prep._plan.debias_device(d_img.data_ptr(), debias_snr)
         # the prepared signals stay float32 in HBM (every value of core.py:209-268 is a float32; core.py:451-452 only widen them):
         # the tensor fit and the model fit read them in place, half the bytes of the float64 rows
         d_y = torch.empty((n, self._prep.n_out), dtype=torch.float32, device=dev)
@@ -377,7 +425,7 @@ class Evaluation:
                 self.set_config('dti_robust', est.last_robust())
         ctx.sync()
         del d_img
-        if self._prep.debias_snr is not None:
+        if debias_snr is not None:
             # samples whose root search reached its trip cap (none on any signal tried: include/amico_amd.h); reported, not hidden
             self.set_config('debias_unconverged', ctx.debias_last_unconverged())
             if self.get_config('debias_unconverged'):
@@ -423,6 +471,9 @@ class Evaluation:
         if d_dirs is not None:
             out['DIRs'] = d_dirs
             self.RESULTS['DIRs'] = sc('DIRs', None)
+        if d_noise is not None:
+            out['NOISE_MAPs'] = d_noise
+            self.RESULTS['NOISE_MAPs'] = sc('NOISE_MAPs', None)
         if self.get_config('doComputeRMSE'):
             self.RESULTS['RMSE'] = sc('rmse', results['rmse'])
         if self.get_config('doComputeNRMSE'):

@@ -105,6 +105,9 @@ struct amx_ctx : WorkSet {
     unsigned long long *san_host = nullptr;    // pinned mirror of the two counters, written by a copy enqueued behind each scan
     hipEvent_t san_ev[2] = {nullptr, nullptr};
     unsigned san_seq = 0;          // sanitize calls enqueued on this ctx so far; call k counts into san_count[k & 1]
+    // exact median (amx_noise.hip): a ring of slots (state + one histogram pair per digit pass); call k takes slot k mod kMedRing
+    DevBuf median_ws;
+    unsigned median_seq = 0;
 };
 
 // ------------------------------------------------------------------ environment switches

@@ -594,6 +594,40 @@ int amx_prep_debias_device(amx_ctx *ctx, const amx_prep *p, float *d_img, double
  * stream it was enqueued on may be gone by then) */
 int amx_debias_last_unconverged(amx_ctx *ctx, int64_t *out);
 
+/* (f0+) The noise level from the spread of the b0 repeats (Evaluation's key doEstimateNoise; no counterpart in the reference, whose
+ * debias and robust tensor fit both take a number the user has to bring).  Per voxel, k = n_b0 in 2 .. 128, samples float32 | float64,
+ * everything in fp64 and every operation rounded on its own (no fused multiply-add):
+ *     x_i   = (double) S[b0_idx[i]]                       i = 0 .. k-1, in b0_idx order
+ *     sum   = ((x_0 + x_1) + x_2) + ...                   sequential
+ *     m     = sum / k
+ *     q     = ((x_0-m)*(x_0-m) + (x_1-m)*(x_1-m)) + ...   sequential, product then add
+ *     sd    = sqrt(q / (k-1))
+ *     eligible  <=>  every x_i finite  and  m > 0  and  sd > 0  and  sd finite
+ *     mean = m, sd = sd, ratio = m / sd   when eligible; otherwise all three NaN
+ * Over the voxels, with c eligible voxels, nu = k - 1 and m_nu = 2 gammaincinv(nu / 2, 1 / 2) / nu (the median of a chi-square variable
+ * of nu degrees of freedom over its mean), the caller takes SNR = nanmedian(ratio) sqrt(m_nu), sigma = nanmedian(sd) / sqrt(m_nu)
+ * (amico_amd/noise.py): the median commutes with monotone maps, so both are median-unbiased under Gaussian noise for every k >= 2.
+ * rows form:   S [n][nS] (C order) in device memory, b0_idx int32[n_b0] in HOST memory -> f64[n] each, row by row.
+ * image form:  the float32 image of a plan in the plan's own layout (any element strides); scheme and b0 list are the plan's.  It visits
+ *              the voxels of plan rank >= 0 (mask == 1, the fit's selection: core.py:451) and writes f64[n_vox] in rank order -- the
+ *              order amx_prep_scatter_device takes.  Nothing but the k b0 samples of those voxels is read and the image is not written.
+ * Any of the three output pointers may be NULL, at least one must be given.  n_b0 < 2, n_b0 > 128 or an index outside 0 .. nS-1 is
+ * AMX_E_BADARG; n == 0 (a plan without masked voxels) is a no-op.  Enqueued on `hip_stream`; waits for nothing.                   */
+int amx_noise_b0_rows_device(amx_ctx *ctx, const double *d_S, int64_t n, int nS, const int32_t *b0_idx, int n_b0,
+                             double *d_mean, double *d_sd, double *d_ratio, void *hip_stream);
+int amx_noise_b0_rows_device_f32(amx_ctx *ctx, const float *d_S, int64_t n, int nS, const int32_t *b0_idx, int n_b0,
+                                 double *d_mean, double *d_sd, double *d_ratio, void *hip_stream);
+int amx_prep_noise_b0_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, double *d_mean, double *d_sd, double *d_ratio,
+                             void *hip_stream);
+/* The exact median of the non-NaN values of d_v f64[n] (device): d_out[0] / d_out[1] = the lower / upper middle order statistic (ranks
+ * (c-1)/2 and c/2 of the c non-NaN values; equal for an odd c; numpy's nanmedian is (d_out[0] + d_out[1]) / 2), *d_count = c; all three
+ * in device memory.  n == 0 or nothing but NaNs: c = 0 and NaN in both.  +-Inf are ordinary values; -0.0 sorts before +0.0.  A radix
+ * select on the order-preserving 64-bit key of the value (sign bit set -> all bits flipped; otherwise the sign bit flipped), eleven
+ * bits a pass (six passes): integer counts only, so the result does not depend on the launch shape or on the order of the atomics.  No host round trip
+ * between the passes, nothing synchronises; the workspace is the ctx's, a ring of four slots: at most four calls of a ctx in flight on
+ * different streams.                                                                                                               */
+int amx_nanmedian_device(amx_ctx *ctx, const double *d_v, int64_t n, double *d_out, int64_t *d_count, void *hip_stream);
+
 /* (f0') NaN / Inf samples, load_data(..., replace_bad_voxels): core.py:152-158 on the raw image and core.py:270-276 on the
  * pre-processed one --
  *     if np.isnan(img).any() or np.isinf(img).any():
