@@ -37,7 +37,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_noise_b0_rows_device', 'amx_noise_b0_rows_device_f32', 'amx_prep_noise_b0_device', 'amx_nanmedian_device',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
-           'amx_lut_resample', 'amx_lut_rotate_resample',
+           'amx_lut_resample', 'amx_lut_rotate_resample', 'amx_lut_route',
            'amx_dict_upload', 'amx_dict_destroy', 'amx_nnls_batched', 'amx_lasso_batched', 'amx_nnls_batched_device', 'amx_lasso_batched_device',
            'amx_dict_set_dense', 'amx_batched_last_dense',
            'amx_bootstrap_resample_device', 'amx_bootstrap_resample_device_f32', 'amx_bootstrap_accumulate_device', 'amx_bootstrap_std_device']
@@ -241,6 +241,7 @@ def lib():
     L.amx_prep_ingest.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_double, C.c_double, C.c_int, C.c_float, c_fp, C.POINTER(C.c_int64)]
     L.amx_lut_resample.argtypes = [c_vp, c_fp, C.c_int64, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
     L.amx_lut_rotate_resample.argtypes = [c_vp, c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, c_fp, c_i32p, C.c_int, C.c_int, c_fp]
+    L.amx_lut_route.argtypes = [C.c_int] * 3 + [c_i64p]
     _lib = L
     return L
 
@@ -1244,6 +1245,18 @@ def lut_resample(ctx, lm, ylm_out, idx_out, nS):
     ctx.check(lib().amx_lut_resample(ctx._h, _p(lm, c_fp), rows, lm.shape[-1], _p(y, c_fp), _p(idx, c_i32p),
                                      y.shape[0], int(nS), _p(out, c_fp)))
     return out
+
+
+LUT_ROUTES = ('refused', 'tile', 'lds', 'generic')      # LUT_ROUTE_* (csrc/amx_lut_route.hpp)
+
+
+def lut_route(n_sh, n_out, fused=False):
+    """which kernel the resampling GEMM launches for K = n_sh reduction indices and n_out volumes (fused: lut_rotate_resample), without a
+    device (amx_lut_route) -> {'route': one of LUT_ROUTES, 'kh2': compile-time half-length 23 / 46 / 64, 'lds': dynamic LDS bytes}"""
+    out = np.zeros(3, dtype=np.int64)
+    if lib().amx_lut_route(int(n_sh), int(n_out), int(bool(fused)), _p(out, c_i64p)) != 0:
+        raise ValueError('amx_lut_route: bad sizes')
+    return {'route': LUT_ROUTES[int(out[0])], 'kh2': int(out[1]), 'lds': int(out[2])}
 
 
 def lut_rotate_resample(ctx, zonal, ylm_rot, ylm_out, idx_out, nS):

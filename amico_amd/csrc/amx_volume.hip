@@ -5,6 +5,7 @@
 #include "amx_host.hpp"
 #include "amx_tensor.hpp"
 #include "amx_prep_route.hpp"
+#include "amx_lut_route.hpp"
 
 using namespace amx;
 
@@ -958,7 +959,7 @@ __global__ void k_fill_ones(float *out, long long n)
 // The order of a sum does not matter to the GEMM.  Measured for 72 000 x 182 x 90 (profiles/): 0.093 ms = 25 TFLOP/s, 16 %
 // of the f32 matrix peak (0.35 ms before); variants that did NOT help: the rows of L through a coalesced per-wavefront
 // LDS tile (0.13 ms at one workgroup per CU), three independent accumulators (0.10 ms, one wavefront per SIMD).
-constexpr int kLutKhMax = 64;
+// (kLutKhMax and the arithmetic that picks one of the three kernels: amx_lut_route.hpp)
 
 // Fused mode (Z != nullptr, amx_lut_rotate_resample): row (atom, orientation) of L is never materialised --
 // L[atom * ndirs + dir][k] = Z[atom][k] * R[dir][k mod n_sh]  (rotate_kernel, lut.pyx:262-264: const * Klm[idx_m0] * Ylm_rot).
@@ -1088,13 +1089,18 @@ __global__ __launch_bounds__(256) void k_lut_resample_tile(const float *__restri
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        // A repeating lane still writes at ITS OWN LDS position (destination = base + 16 * lane).  With N * K / 2 odd the copy ends
+        // 8 bytes into a lane's slot: that lane has put bytes [ybytes - 16, ybytes - 8) where the last two floats belong.  They are
+        // read again with an ordinary load (nothing is read beyond the operator's end).
+        if ((ybytes & 8) && threadIdx.x == 0)
+            *reinterpret_cast<float2 *>(Ys + ybytes / 4 - 2) = *reinterpret_cast<const float2 *>(Y + ybytes / 4 - 2);
         // behind the last row of the operator: zeros (the over-read of row N - 1 and the rows N .. of the last column block)
         for (long long pos = ybytes / 4 + threadIdx.x; pos < yzone / 4; pos += blockDim.x) Ys[pos] = 0.0f;
         __syncthreads();
     }
     LPH_ADD(0, t0);
     // the tile of rows m0 .. m0 + 31 -> this wavefront's LDS block (whole 1 KB pieces; the tail lanes of the last piece repeat
-    // its last 16 bytes, which land in the slack behind the tile)
+    // its last 16 bytes, which land behind the tile's rows -- but for the one lane that straddles their end: process() below)
     auto load_tile = [&](long long m0) {
         const long long rows = (M - m0) < 32 ? (M - m0) : 32;
         const long long bytes = rows * K * 4;
@@ -1115,6 +1121,12 @@ __global__ __launch_bounds__(256) void k_lut_resample_tile(const float *__restri
         unsigned long long t1 = LPH_T();
         load_tile(m0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (also: the previous tile's stores are out)
+        // a last tile with an odd number of rows and K / 2 odd ends 8 bytes into a lane's 16-byte slot: as for the operator above, the
+        // repeating lane has shifted the last two floats of the last row; an ordinary load puts them right (wavefront-uniform test)
+        if (M - m0 < 32 && (((M - m0) * K) & 2)) {
+            const long long last = (M - m0) * K - 2;
+            if (lane == 0) *reinterpret_cast<float2 *>(Lt + last) = *reinterpret_cast<const float2 *>(L + m0 * K + last);
+        }
         LPH_ADD(1, t1);
         const float2 *arow = reinterpret_cast<const float2 *>(Lt + (size_t)l32 * K + 2 * half * KH2);
         for (int c = c_begin; c < c_end; c++) {
@@ -1212,19 +1224,18 @@ static int lut_gemm(amx_ctx *ctx, const float *d_lm, const float *d_z, const flo
 {
     int rc = AMX_OK;
     hipLaunchKernelGGL(amx::k_fill_ones, dim3(2048), dim3(256), 0, nullptr, (float *)ctx->hextra.p, (long long)n_rows * nS);
-    const int kh2 = (n_sh + 3) / 4;
-    const int kh2t = kh2 <= 23 ? 23 : (kh2 <= 46 ? 46 : 64);         // compile-time reduction lengths: 1 / 2 shells of lmax 12, <= 256
-    const size_t lds = (size_t)((n_out + 31) & ~31) * (4 * kh2t + 2) * sizeof(float);
-    // both operands in LDS: plain input, even K, operator zone + four row tiles within the 160 KB of a CU
-    const size_t yzone = ((((size_t)n_out * n_sh * 4) + 1023) & ~(size_t)1023) + 2048;
-    const size_t lds_tile = yzone + 4 * ((((size_t)32 * n_sh * 4) + 1023) & ~(size_t)1023);
-    if (d_lm && (n_sh & 1) == 0 && n_sh <= 4 * amx::kLutKhMax && 4 * kh2t - n_sh <= 4 && lds_tile <= 160 * 1024) {
+    const amx::LutRoute rt = amx::lut_route(n_sh, n_out, d_lm == nullptr);      // (amx_lut_route.hpp: the one place that decides)
+    const int kh2t = rt.kh2;
+    const size_t lds = rt.lds;
+    if (rt.route == amx::LUT_ROUTE_REFUSED)
+        return amx_bad(ctx, "amx_lut_rotate_resample: shape beyond the fused kernel (K <= 256, operator <= 80 KB)");
+    if (rt.route == amx::LUT_ROUTE_TILE) {                           // both operands in LDS
         auto launch = [&](auto kern) -> int {
-            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile));
+            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             long long blocks = (n_rows + 127) / 128;
             if (blocks > ctx->n_cu) blocks = ctx->n_cu;              // persistent, one workgroup per CU: the operator is staged once
             rec(ctx, 8, nullptr);
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds_tile, nullptr, d_lm, d_ylm, d_idx, (long long)n_rows, n_sh,
+            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, nullptr, d_lm, d_ylm, d_idx, (long long)n_rows, n_sh,
                                n_out, nS, (float *)ctx->hextra.p);
             return AMX_OK;
         };
@@ -1232,9 +1243,7 @@ static int lut_gemm(amx_ctx *ctx, const float *d_lm, const float *d_z, const flo
         else if (kh2t == 46) rc = launch(amx::k_lut_resample_tile<46>);
         else rc = launch(amx::k_lut_resample_tile<64>);
         if (rc) return rc;
-    } else
-    if (n_sh > 4 * amx::kLutKhMax || lds > 80 * 1024) {              // generic shapes: operands from L2
-        if (!d_lm) return amx_bad(ctx, "amx_lut_rotate_resample: shape beyond the fused kernel (K <= 256, operator <= 80 KB)");
+    } else if (rt.route == amx::LUT_ROUTE_GENERIC) {                 // operands from L2
         rec(ctx, 8, nullptr);
         hipLaunchKernelGGL(amx::k_lut_resample_generic, dim3((unsigned)((n_rows + 127) / 128)), dim3(256), 0, nullptr, d_lm, d_ylm,
                            d_idx, (long long)n_rows, n_sh, n_out, nS, (float *)ctx->hextra.p);
@@ -1256,6 +1265,14 @@ static int lut_gemm(amx_ctx *ctx, const float *d_lm, const float *d_z, const flo
     }
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, nullptr);
+    return AMX_OK;
+}
+
+extern "C" int amx_lut_route(int n_sh, int n_out, int fused, int64_t out[3])
+{
+    if (n_sh < 1 || n_out < 1 || !out) return AMX_E_BADARG;
+    const amx::LutRoute rt = amx::lut_route(n_sh, n_out, fused != 0);
+    out[0] = rt.route; out[1] = rt.kh2; out[2] = (int64_t)rt.lds;
     return AMX_OK;
 }
 

@@ -703,6 +703,14 @@ int amx_lut_rotate_resample(amx_ctx *ctx, const float *zonal, int n_atoms, const
                             int n_sh_shell, int n_shells, const float *ylm_out, const int32_t *idx_out, int n_out,
                             int nS, float *out);
 
+/* Which of the GEMM's three kernels a shape gets, without a device (the arithmetic both calls above launch by, csrc/amx_lut_route.hpp):
+ * n_sh = K reduction indices (for the fused call n_sh_shell * n_shells), n_out DWI volumes, fused = 1 for amx_lut_rotate_resample.
+ * out = {route (0 refused: a fused shape beyond K <= 256 / an operator of 80 KB, AMX_E_BADARG from the call; 1 tile: both operands in
+ * LDS, plain input with K in 88 90 92 180 182 184 252 254 256 while operator + four row tiles fit 160 KB; 2 lds: the operator in at
+ * most 80 KB of LDS, K <= 256, the only fused kernel; 3 generic: operands from L2), compile-time half-length 23 / 46 / 64, dynamic LDS
+ * bytes per workgroup}.                                                                                                              */
+int amx_lut_route(int n_sh, int n_out, int fused, int64_t out[3]);
+
 /* ---- measurement hooks (bench.py): HIP-event time of the solver kernels of the LAST
  * *_fit_device call on this ctx, measured on the stream they were launched on.
  * which: 0 = all kernels of the call, 1..3 = solver stage kernels (NODDI: the wavefront-per-voxel kernels of NNLS-1, LASSO,
