@@ -30,7 +30,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_dti_create', 'amx_dti_create_method', 'amx_dti_create_robust', 'amx_dti_last_unconverged', 'amx_dti_last_trips', 'amx_dti_last_robust', 'amx_dti_destroy', 'amx_dti_directions', 'amx_dti_directions_device', 'amx_dti_directions_device_f32',
            'amx_dti_fit', 'amx_dti_fit_device', 'amx_dti_fit_device_f32', 'amx_dti_fit_robust', 'amx_dti_fit_robust_device', 'amx_dti_fit_robust_device_f32', 'amx_prep_gather_device_f32',
            'amx_prep_create', 'amx_prep_destroy', 'amx_prep_gather', 'amx_prep_gather_device',
-           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_noddi_route', 'amx_prep_last_launch',
+           'amx_prep_gather_directions_device', 'amx_prep_gather_directions_device_f32', 'amx_prep_route', 'amx_noddi_route', 'amx_small_route', 'amx_prep_last_launch',
            'amx_prep_mean_b0', 'amx_prep_mean_b0_device', 'amx_prep_scatter', 'amx_prep_scatter_device',
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
@@ -173,6 +173,7 @@ def lib():
     L.amx_last_path.argtypes = [c_vp, C.c_char_p, C.c_int]
     L.amx_prep_route.argtypes = [C.c_int] * 7 + [c_i64p]
     L.amx_noddi_route.argtypes = [C.c_int] * 5 + [C.c_int64] * 2 + [C.c_double] * 2 + [C.c_char_p, C.c_int, c_i64p]
+    L.amx_small_route.argtypes = [C.c_int] * 4 + [C.c_int64] + [C.c_double] * 2 + [C.c_uint, C.c_int, C.c_uint, C.c_char_p, C.c_int, c_i64p]
     L.amx_prep_last_launch.argtypes = [c_vp, C.c_char_p, C.c_int, c_i64p]
     L.amx_host_pool_info.argtypes = [c_vp, C.POINTER(C.c_int)]
     L.amx_set_call_voxels.argtypes = [c_vp, C.c_int64]
@@ -1175,6 +1176,36 @@ def noddi_route(nS, n_wm, n_dwi, ndirs, is_exvivo, n_vox, call_vox=0, lambda1=0.
     names = rt['path'].split(' -> ')
     w = out[len(NODDI_ROUTE_WORDS):len(NODDI_ROUTE_WORDS) + 3 * rt['n_launch']].reshape(-1, 3)
     rt['launches'] = [(names[i], int(w[i, 0]), int(w[i, 1]), int(w[i, 2])) for i in range(rt['n_launch'])]
+    return rt
+
+
+# SmallFamily, SmallTables, SmallRefusal (csrc/amx_small_route.hpp); the switches of switches_mask, bit 0 first
+SMALL_FAMILIES = ('none', 'fw_fused', 'fw_refill', 'lane', 'wave', 'sandi_rows', 'sandi_long_lane', 'sandi_long_wave', 'czb_fast', 'czb_gram', 'czb_qr',
+                  'enet_big')
+SMALL_TABLES = ('none', 'fw', 'sandi', 'sandi_long', 'czb')
+SMALL_REFUSALS = ('none', 'sandi_long_ridge', 'pair_tile', 'lane_tile', 'sandi_long_operand', 'big_no_gram', 'big_vectors')
+SMALL_SWITCHES = ('AMX_WAVE_PER_VOXEL', 'AMX_NO_REFILL', 'AMX_SANDI_ATOM_SPACE', 'AMX_FW_NO_FUSE')
+SMALL_ROUTE_WORDS = ('family', 'N', 'NR', 'mfma', 'widen', 'chunk', 'blocks_chunk', 'tables', 'in_order', 'nSp', 'waves', 'lds', 'lds_list', 'refusal',
+                     'n_launch')
+
+
+def small_route(model, nS, n_atoms, ndirs, n_vox, lambda1=0.0, lambda2=1e-3, flags=0, f32=False, switches_mask=0):
+    """which kernels a FreeWater (model 2), SANDI (3) or CylinderZeppelinBall (4) fit of n_vox voxels launches on a dictionary of this shape,
+    without a device (amx_small_route) -> the words of SMALL_ROUTE_WORDS ('family', 'tables', 'refusal' as names of SMALL_FAMILIES /
+    SMALL_TABLES / SMALL_REFUSALS, flags as bool), 'path' in the format of Context.last_path(), 'launches' (its kernels), 'status' (AMX_OK, or
+    AMX_E_BADARG for a shape the fit refuses) and 'error' (the refusal's text)"""
+    out = np.zeros(len(SMALL_ROUTE_WORDS), dtype=np.int64)
+    buf = C.create_string_buffer(1024)
+    if lib().amx_small_route(int(model), int(nS), int(n_atoms), int(ndirs), int(n_vox), float(lambda1), float(lambda2), int(flags), int(bool(f32)),
+                             int(switches_mask), buf, 1024, _p(out, c_i64p)) != 0:
+        raise ValueError('amx_small_route: bad arguments')
+    rt = {k: int(v) for k, v in zip(SMALL_ROUTE_WORDS, out)}
+    for k in ('mfma', 'widen', 'in_order'):
+        rt[k] = bool(rt[k])
+    rt['family'], rt['tables'], rt['refusal'] = SMALL_FAMILIES[rt['family']], SMALL_TABLES[rt['tables']], SMALL_REFUSALS[rt['refusal']]
+    rt['path'], _, rt['error'] = buf.value.decode().partition('\n')
+    rt['launches'] = rt['path'].split(' -> ') if rt['path'] else []
+    rt['status'] = AMX_E_BADARG if rt['refusal'] != 'none' else AMX_OK
     return rt
 
 

@@ -402,6 +402,26 @@ int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64
     return AMX_OK;
 }
 
+// the route of a FreeWater, SANDI or CylinderZeppelinBall fit (amx_small_route.hpp) for a dictionary of this shape, as the model's upload would build it
+int amx_small_route(int model, int nS, int n_atoms, int ndirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, int f32,
+                    unsigned switches_mask, char *note_buf, int cap, int64_t out[AMX_SMALL_ROUTE_WORDS])
+{
+    if (!note_buf || cap <= 0 || !out || model < 2 || model > 4 || nS < 1 || nS > 512 || n_atoms < 1 || n_atoms > amx::kBigMaxAtoms || ndirs < 1 ||
+        (model == 3 && ndirs != 1) || n_vox < 1 || n_vox > INT_MAX / 4 || !(lambda1 >= 0.0) || !(lambda2 >= 0.0) || switches_mask > 15u) return AMX_E_BADARG;
+    // (ldA: new_lut's; Gram tables: amx_lut_upload_czb's, and amx_build_big_gram for every dictionary of more than 64 atoms)
+    const amx::SmallShape sh{model, nS, (n_atoms & 1) ? n_atoms : n_atoms + 1, n_atoms, ndirs, model == 4 || n_atoms > amx::kSmallMaxAtoms};
+    const amx::SmallRoute r = amx::small_route(sh, {n_vox, lambda1, lambda2, flags, f32 != 0},
+                                               {(switches_mask & 1u) != 0, (switches_mask & 2u) != 0, (switches_mask & 4u) != 0, (switches_mask & 8u) != 0});
+    const int64_t words[AMX_SMALL_ROUTE_WORDS] = {r.family, r.N, r.NR, r.mfma, r.widen, r.chunk, r.blocks_chunk, r.tables, r.in_order, r.nSp, r.waves,
+                                                  (int64_t)r.lds, (int64_t)r.lds_list, r.refusal, r.n_launch};
+    for (int k = 0; k < AMX_SMALL_ROUTE_WORDS; k++) out[k] = words[k];
+    std::string p;
+    for (int l = 0; l < r.n_launch; l++) { p += (l ? " -> " : ""); p += r.launch[l]; }
+    if (r.refusal) { p += "\n"; p += r.error; }
+    snprintf(note_buf, (size_t)cap, "%s", p.c_str());
+    return AMX_OK;
+}
+
 int amx_last_seed_stats(amx_ctx *ctx, int64_t out[8])
 {
     if (!ctx || !out) return AMX_E_BADARG;

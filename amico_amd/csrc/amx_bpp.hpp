@@ -22,7 +22,6 @@
 namespace amx {
 namespace bpp {
 
-constexpr int kThreads = 256;
 constexpr int kStart = 32, kBackup = 3, kRefine = 3;
 constexpr double kTol = 1e-12, kTolP = 1e-11, kPiv = 1e-13;
 // ASPACE (k_enet_big): a pivot of the single exchanges below kSmall H_jj is evaluated again in A-space, and dropped at kPivA H_jj only.
@@ -255,13 +254,7 @@ struct Work {
     double *Ll;       // packed lower triangle, <= lcap atoms
 };
 
-__host__ __device__ inline size_t vec_bytes(int m, int n)
-{
-    const size_t mp = (size_t)((m + 1) & ~1), npd = (size_t)((n + 1) & ~1), n4 = (size_t)((n + 3) & ~3);
-    size_t bytes = (2 * mp + 9 * npd + kThreads + 2) * sizeof(double) + (5 * n4 + 16) * sizeof(int);
-    return (bytes + 15) & ~(size_t)15;
-}
-
+// (kThreads, vec_bytes: amx_sizes.hpp)
 __device__ __forceinline__ Work carve(unsigned char *smem, int m, int n)
 {
     const int mp = (m + 1) & ~1, npd = (n + 1) & ~1, n4 = (n + 3) & ~3;

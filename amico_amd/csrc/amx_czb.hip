@@ -3,31 +3,26 @@
 using namespace amx;
 
 template <int NR>
-static int go(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)
+static int go(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
-    constexpr int NQ = 1, MP = 32, MB = 64;      // 26 atoms by default: the main kernel's passive set holds them all
+    constexpr int NQ = 1, MP = 32, MB = 64;      // 26 atoms by default: the main kernel's passive set holds them all (small_route sizes the LDS with the same three)
     constexpr int NW = 8;
-    return launch_pair<NW>(ctx, a, pl, s, k_czb<NR, NQ, MP, NW, false>, k_czb<NR, NQ, MB, 1, true>,
-                           [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MP, true) + ((size_t)a.c.n_atoms * a.ldG + (size_t)(MP + 1) * (MP + 2) + MP + 1) * sizeof(double) + 16; },
-                           fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB, true), 0, 2, NR == 2 ? "k_czb<2>" : (NR == 4 ? "k_czb<4>" : "k_czb<8>"));
+    return launch_pair<NW>(ctx, a, pl, s, k_czb<NR, NQ, MP, NW, false>, k_czb<NR, NQ, MB, 1, true>, route_lds(rt.waves, rt.lds), rt.lds_list, 0, 2, rt.launch[0]);
 }
 
 // lambda2 below what the Gram form can take: thin QR in A-space (the other models route small ridges there too)
 template <int NR>
-static int go_qr(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)
+static int go_qr(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
     constexpr int NQ = 1, MP = 32, MB = 64;
     constexpr int NW = 4;
-    return launch_pair<NW>(ctx, a, pl, s, k_czb_qr<NR, NQ, MP, NW, false>, k_czb_qr<NR, NQ, MB, 1, true>,
-                           [&](int nw) { return fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, nw, MP); }, fit_lds_bytes<float>(a.c.nS, a.c.ldA, NR, NQ, 1, MB), 0, 2,
-                           NR == 2 ? "k_czb_qr<2>" : (NR == 4 ? "k_czb_qr<4>" : "k_czb_qr<8>"));
+    return launch_pair<NW>(ctx, a, pl, s, k_czb_qr<NR, NQ, MP, NW, false>, k_czb_qr<NR, NQ, MB, 1, true>, route_lds(rt.waves, rt.lds), rt.lds_list, 0, 2, rt.launch[0]);
 }
 
-int amx_launch_czb(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s)
+int amx_launch_czb(amx_ctx *ctx, CzbArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
-    // (8 rows per lane: protocols of up to 512 volumes -- the <= 64-atom tile still fits the LDS: 512 x 65 float32 = 133 KB)
-    if (a.c.lam2 < 1e-6) return a.c.nS <= 128 ? go_qr<2>(ctx, a, pl, s) : (a.c.nS <= 256 ? go_qr<4>(ctx, a, pl, s) : go_qr<8>(ctx, a, pl, s));
-    return a.c.nS <= 128 ? go<2>(ctx, a, pl, s) : (a.c.nS <= 256 ? go<4>(ctx, a, pl, s) : go<8>(ctx, a, pl, s));
+    if (rt.family == SF_CZB_QR) return rt.NR == 2 ? go_qr<2>(ctx, a, pl, s, rt) : (rt.NR == 4 ? go_qr<4>(ctx, a, pl, s, rt) : go_qr<8>(ctx, a, pl, s, rt));
+    return rt.NR == 2 ? go<2>(ctx, a, pl, s, rt) : (rt.NR == 4 ? go<4>(ctx, a, pl, s, rt) : go<8>(ctx, a, pl, s, rt));
 }
 
 // ================================================================== the default problem, fast: complementary form, one voxel per lane
@@ -391,12 +386,12 @@ __global__ void __launch_bounds__(256, 1) k_czb_lane(const CzbFastArgs a)
     }
 }
 
-size_t amx_czb_table_stride(int nS) { const int nSp = nS <= 100 ? 100 : 160; return (size_t)2 * kCzbN * kCzbLd + kCzbN + (size_t)2 * kCzbN * nSp; }
+size_t amx_czb_table_stride(int nS) { return (size_t)2 * kCzbN * kCzbLd + kCzbN + (size_t)2 * kCzbN * czb_padded_nS(nS); }
 
 // tables of the fast path, cached in the dictionary handle for one lambda2
-int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s)
+int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s, const SmallRoute &rt)
 {
-    const int nSp = lut->nS <= 100 ? 100 : 160;
+    const int nSp = rt.nSp;
     const size_t stride = amx_czb_table_stride(lut->nS);
     if (lut->czb_lam2 != lam2 || !lut->czb_prep) {
         if (lut->czb_prep) HIPCHK(ctx, hipDeviceSynchronize());            // (a fit with the old tables may still run)
@@ -412,19 +407,19 @@ int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s
     return AMX_OK;
 }
 
-int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, CzbArgs &a, const Plan &pl, hipStream_t s)
+int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, CzbArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
     CzbFastArgs f;
     memset(&f, 0, sizeof f);
     f.y = a.c.y; f.y32 = a.c.y32; f.perm = pl.perm; f.schunks = pl.schunks; f.n_schunks = pl.n_chunks + 1;
-    f.tables = lut->czb_prep; f.table_stride = (int)amx_czb_table_stride(lut->nS); f.nSp = lut->nS <= 100 ? 100 : 160;
+    f.tables = lut->czb_prep; f.table_stride = (int)amx_czb_table_stride(lut->nS); f.nSp = rt.nSp;
     f.nS = lut->nS; f.n_atoms = lut->n_atoms; f.n_rs = lut->n_rs; f.n_perp = lut->n_perp; f.Rs = lut->Rs; f.lam1 = a.c.lam1;
     f.Zb = (double *)ctx->cgemm.p; f.est = a.est; f.xdbg = a.c.xdbg; f.status = a.c.status;
     f.ovf_count = pl.ovf_count; f.ovf_list = pl.ovf_list;
     const dim3 grid(((pl.max_schunks + 7) / 8) * 8);
     int rc;
     rec(ctx, 2, s);
-    if (lut->nS <= 100) {
+    if (rt.N == 25) {
         const size_t lds = ((size_t)4 * 25 * 64 + kCzbN) * sizeof(double);
         if ((rc = set_lds(ctx, k_czb_project<25>, lds))) return rc;
         hipLaunchKernelGGL(k_czb_project<25>, grid, dim3(512), lds, s, f);
@@ -433,26 +428,24 @@ int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, CzbArgs &a, const Plan
         if ((rc = set_lds(ctx, k_czb_project<40>, lds))) return rc;
         hipLaunchKernelGGL(k_czb_project<40>, grid, dim3(512), lds, s, f);
     }
-    amx_note(ctx, lut->nS <= 100 ? "k_czb_project<25>" : "k_czb_project<40>");
+    amx_note(ctx, rt.launch[0]);
     AMX_TRACE(ctx, s, "z0 = M A'y on the matrix cores");
     const size_t lds2 = ((size_t)2 * kCzbN * kCzbLd + 2 + (size_t)4 * 2 * kCzbN * 64) * sizeof(double);
     if ((rc = set_lds(ctx, k_czb_lane, lds2))) return rc;
     hipLaunchKernelGGL(k_czb_lane, grid, dim3(256), lds2, s, f);
-    amx_note(ctx, "k_czb_lane");
+    amx_note(ctx, rt.launch[1]);
     AMX_TRACE(ctx, s, "complementary-form pivoting, one voxel per lane");
     // voxels with more clamped atoms than a lane holds: the wavefront-per-voxel kernel, one wavefront per workgroup
     {
         CzbArgs b = a;
         b.c.ovf_count = pl.ovf_count + 8; b.c.ovf_list = pl.ovf_list + 3 * pl.n;
         b.c.list = pl.ovf_list; b.c.list_count = pl.ovf_count;
-        const size_t lds_list = fit_lds_bytes<float>(a.c.nS, a.c.ldA, 2, 1, 1, 64, true);
-        if (a.c.nS <= 128) {
-            if ((rc = set_lds(ctx, (k_czb<2, 1, 64, 1, true>), lds_list))) return rc;
-            hipLaunchKernelGGL((k_czb<2, 1, 64, 1, true>), dim3(kListGrid), dim3(64), lds_list, s, b);
+        if (rt.NR == 2) {
+            if ((rc = set_lds(ctx, (k_czb<2, 1, 64, 1, true>), rt.lds_list))) return rc;
+            hipLaunchKernelGGL((k_czb<2, 1, 64, 1, true>), dim3(kListGrid), dim3(64), rt.lds_list, s, b);
         } else {
-            const size_t l4 = fit_lds_bytes<float>(a.c.nS, a.c.ldA, 4, 1, 1, 64, true);
-            if ((rc = set_lds(ctx, (k_czb<4, 1, 64, 1, true>), l4))) return rc;
-            hipLaunchKernelGGL((k_czb<4, 1, 64, 1, true>), dim3(kListGrid), dim3(64), l4, s, b);
+            if ((rc = set_lds(ctx, (k_czb<4, 1, 64, 1, true>), rt.lds_list))) return rc;
+            hipLaunchKernelGGL((k_czb<4, 1, 64, 1, true>), dim3(kListGrid), dim3(64), rt.lds_list, s, b);
         }
     }
     rec(ctx, 3, s);

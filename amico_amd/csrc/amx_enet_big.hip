@@ -178,14 +178,12 @@ __global__ void __launch_bounds__(kEbThreads) k_enet_big(const EnetBigArgs b)
 }
 
 template <typename AT, int MODEL>
-int launch_enet_big(amx_ctx *ctx, const amx_lut *lut, EnetBigArgs &b, hipStream_t s, const char *name)
+int launch_enet_big(amx_ctx *ctx, const amx_lut *lut, EnetBigArgs &b, hipStream_t s, const SmallRoute &rt)
 {
     const int m = b.c.nS, n = b.c.n_atoms;
-    if (!lut->gram || n > kBigMaxAtoms) { ctx->err = "k_enet_big: the dictionary has no Gram table"; return AMX_E_BADARG; }
     b.gram = lut->gram; b.ldG = lut->ldG; b.ndirs = lut->ndirs;
     b.full_start = (b.c.lam1 == 0.0 && b.c.lam2 >= 1e-2) ? 1 : 0;
-    const size_t vec = bpp::vec_bytes(m, n);
-    if (vec > kLdsPerCU) { ctx->err = "k_enet_big: the dictionary's vectors do not fit the LDS"; return AMX_E_BADARG; }
+    const size_t vec = bpp::vec_bytes(m, n);      // (the route has seen that they fit, and that the dictionary has its Gram table)
     int lcap = 0;
     while (lcap < n && vec + ((size_t)(lcap + 1) * (lcap + 2) / 2) * sizeof(double) <= kLdsPerCU) lcap++;
     b.lcap = lcap;
@@ -204,7 +202,7 @@ int launch_enet_big(amx_ctx *ctx, const amx_lut *lut, EnetBigArgs &b, hipStream_
     }
     rec(ctx, 4, s);
     if ((rc = launch_lds(ctx, k_enet_big<AT, MODEL>, dim3((unsigned)grid), dim3(kEbThreads), lds, s, b))) return rc;
-    amx_note(ctx, name);
+    amx_note(ctx, rt.launch[0]);
     AMX_TRACE(ctx, s, "dictionaries of 65 .. 256 atoms (block principal pivoting, workgroup per voxel)");
     rec(ctx, 5, s);
     HIPCHK(ctx, hipGetLastError());
@@ -222,32 +220,32 @@ void common_args(EnetBigArgs &b, const FitCommon &c, const Plan *pl, int ndirs, 
 
 }  // namespace
 
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const FwArgs &a, const Plan &pl, int64_t n, hipStream_t s)
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const FwArgs &a, const Plan &pl, int64_t n, hipStream_t s, const SmallRoute &rt)
 {
     EnetBigArgs b;
     common_args(b, a.c, &pl, lut->ndirs, n);
     b.est = a.est; b.rmse = a.rmse; b.nrmse = a.nrmse; b.n_maps = a.n_maps;
     b.n_a = a.n_perp; b.n_iso = a.n_iso; b.is_mouse = a.is_mouse; b.ycorr = a.ycorr; b.xiso = a.xiso;
-    return launch_enet_big<float, 2>(ctx, lut, b, s, "k_enet_big<FreeWater> (65 .. 256 atoms)");
+    return launch_enet_big<float, 2>(ctx, lut, b, s, rt);
 }
 
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const SandiArgs &a, int64_t n, hipStream_t s)
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const SandiArgs &a, int64_t n, hipStream_t s, const SmallRoute &rt)
 {
     EnetBigArgs b;
     common_args(b, a.c, nullptr, 1, n);                           // (one dictionary: the voxels in order)
     b.est = a.est; b.rmse = a.rmse; b.nrmse = a.nrmse; b.n_maps = 6;
     b.n_a = a.n_rs; b.n_b = a.n_in; b.n_iso = a.n_iso;
     b.norms = a.norms; b.Rs = a.Rs; b.d_in = a.d_in; b.d_isos = a.d_isos;
-    return launch_enet_big<double, 3>(ctx, lut, b, s, "k_enet_big<SANDI> (65 .. 256 atoms)");
+    return launch_enet_big<double, 3>(ctx, lut, b, s, rt);
 }
 
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s)
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s, const SmallRoute &rt)
 {
     EnetBigArgs b;
     common_args(b, a.c, &pl, lut->ndirs, n);
     b.est = a.est; b.rmse = a.rmse; b.nrmse = a.nrmse; b.n_maps = 3;
     b.n_a = a.n_rs; b.n_b = a.n_perp; b.Rs = a.Rs;
-    return launch_enet_big<float, 4>(ctx, lut, b, s, "k_enet_big<CylinderZeppelinBall> (65 .. 256 atoms)");
+    return launch_enet_big<float, 4>(ctx, lut, b, s, rt);
 }
 
 // G_d of every orientation of a dictionary of more than 64 atoms into lut->gram, on the null stream (the upload's)

@@ -1,5 +1,5 @@
 // amx_fit_dev.hip -- the four model fits on device pointers.  One checked, prepared call (fit_check, fit_open, fit_args, fit_close) around
-// what is a model's own: NODDI's chain of three stages, FreeWater's refill decision, SANDI's row-space branch, CylinderZeppelinBall's fast route.
+// what is a model's own: NODDI's chain of three stages; FreeWater, SANDI and CylinderZeppelinBall as their route says (amx_small_route.hpp).
 #include "amx_host.hpp"
 
 using namespace amx;
@@ -252,24 +252,21 @@ int noddi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     return fit_close(ctx, c, rc);
 }
 
-// ------------------------------------------------------------------ FreeWater
-int freewater_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+// ------------------------------------------------------------------ FreeWater, SANDI, CylinderZeppelinBall: each follows its route (amx_small_route.hpp)
+int freewater_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c, const SmallRoute &rt)
 {
     const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
     if ((rc = make_plan(ctx, c.n, lut->ndirs, pl))) return rc;
-    const bool refill = amx_use_lane_solver(ctx, lut->n_atoms, c.lam2) && amx_fw_use_refill(ctx, lut->n_atoms, lut->nS, c.flags, c.lam2);
     FwArgs a;
     // AMX_F_FW_ISO: the isotropic coefficients of every voxel, at the voxel's index in the caller's buffer (fit_check has seen the buffer)
     double *xiso = (c.flags & AMX_F_FW_ISO) ? ctx->fw_iso + (size_t)c.batch.base * lut->n_iso : nullptr;
-    if ((rc = fit_open(ctx, m, c, pl, refill ? amx_refill_chunk(c.n) : kChunk, xiso, lut->n_iso)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
+    if ((rc = fit_open(ctx, m, c, pl, rt.chunk, xiso, lut->n_iso)) || (rc = fit_args(ctx, m, c, pl, a, &FwArgs::ycorr))) return rc;
     a.n_perp = lut->n_perp; a.n_iso = lut->n_iso; a.is_mouse = c.is_mouse; a.n_maps = fit_maps(m, c); a.xiso = xiso;
-    if (refill && (rc = amx_fw_prepare(ctx, lut, a, s))) return rc;
-    // (more than 64 atoms: the dense route, amx_enet_big.hip -- the dictionary's shape alone decides)
-    return fit_close(ctx, c, amx_big_dictionary(lut) ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s) : amx_launch_fw(ctx, a, pl, s));
+    if (rt.tables == SMT_FW && (rc = amx_fw_prepare(ctx, lut, a, s, rt))) return rc;
+    return fit_close(ctx, c, rt.family == SF_ENET_BIG ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s, rt) : amx_launch_fw(ctx, a, pl, s, rt));
 }
 
-// ------------------------------------------------------------------ SANDI
-int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c, const SmallRoute &rt)
 {
     const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
     if ((rc = make_plan(ctx, c.n, 1, pl))) return rc;
@@ -277,64 +274,58 @@ int sandi_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;      // (one dictionary: no bucketing)
     a.norms = lut->norms; a.Rs = lut->Rs; a.d_in = lut->d_in; a.d_isos = lut->d_isos;
     a.n_rs = lut->n_rs; a.n_in = lut->n_in; a.n_iso = lut->n_isos;
-    // protocols without the directional average need the ridge: an isotropic dictionary has rank <= shells + 1 < n_atoms, so without it the optimum
-    // is not unique and A'A alone is singular
-    if (lut->nS > kSandiShortNS && c.lam2 < 1e-9) return fit_bad(ctx, m, ": protocols of more than 128 volumes need lambda2 >= 1e-9 (Gram-space solver)");
-    // more than 64 atoms: the dense route, whatever the protocol (amx_enet_big.hip; the voxels in order, no per-call counters)
-    if (amx_big_dictionary(lut)) return fit_close(ctx, c, amx_launch_enet_big(ctx, lut, a, c.n, s), false);
-    if (lut->nS > kSandiShortNS) {
-        // c = A'y on the matrix cores, then the Gram-space solvers (amx_sandi_long.hip)
-        if ((rc = amx_sandi_long_prepare(ctx, lut, c.lam2, s))) return rc;
-        return fit_close(ctx, c, amx_launch_sandi_long(ctx, lut, a, c.n, s), false);      // (the voxels in order, no per-call counters)
+    if (rt.tables == SMT_SANDI && (rc = amx_sandi_prepare(ctx, lut, a, s))) return rc;
+    if (rt.tables == SMT_SANDI_LONG && (rc = amx_sandi_long_prepare(ctx, lut, c.lam2, s))) return rc;
+    // the voxels in order (k_enet_big, the long protocols' kernels, the row-space kernel): they count straight into the status words;
+    // the other SANDI kernels walk the (trivial) plan and use the per-call counters
+    if (rt.family == SF_SANDI_ROWS) a.n_lin = (int)c.n;
+    if (!rt.in_order && (rc = enqueue_linear_plan(ctx, c.n, pl, s))) return rc;
+    switch (rt.family) {
+    case SF_ENET_BIG: rc = amx_launch_enet_big(ctx, lut, a, c.n, s, rt); break;
+    case SF_SANDI_LONG_LANE: case SF_SANDI_LONG_WAVE: rc = amx_launch_sandi_long(ctx, lut, a, c.n, s, rt); break;
+    default: rc = amx_launch_sandi(ctx, a, pl, s, rt);
     }
-    if ((rc = amx_sandi_prepare(ctx, lut, a, s))) return rc;
-    // the row-space kernel (default protocol) takes the voxels in order and counts straight into the status words: one launch
-    // per fit; the other SANDI kernels walk the (trivial) plan and use the per-call counters
-    const bool rows = a.tables && amx_use_lane_solver(ctx, a.c.n_atoms, a.c.lam2) && !ctx->opt_sandi_atom_space;
-    if (rows) a.n_lin = (int)c.n;
-    else if ((rc = enqueue_linear_plan(ctx, c.n, pl, s))) return rc;
-    return fit_close(ctx, c, amx_launch_sandi(ctx, a, pl, s), !rows);
+    return fit_close(ctx, c, rc, !rt.in_order);
 }
 
-// ------------------------------------------------------------------ CylinderZeppelinBall
-int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c)
+int czb_fit_dev(amx_ctx *ctx, const FitSpec &m, const FitCall &c, const SmallRoute &rt)
 {
     const amx_lut *lut = c.lut; hipStream_t s = c.stream; Plan pl; int rc;
-    // the default problem (strong ridge, <= 32 atoms, maps only): complementary form, one voxel per lane (amx_czb.hip)
-    const bool fast = lut->n_atoms <= 32 && c.lam2 >= 1e-2 && !(c.flags & (AMX_F_RMSE | AMX_F_NRMSE)) &&
-                      !ctx->opt_wave_per_voxel && lut->nS <= 160 && lut->gram != nullptr;
-    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl, nullptr, 64, fast ? 2048 : 0))) return rc;
+    if ((rc = make_plan(ctx, c.n, lut->ndirs, pl, nullptr, 64, rt.blocks_chunk))) return rc;
     CzbArgs a;
     if ((rc = fit_open(ctx, m, c, pl)) || (rc = fit_args(ctx, m, c, pl, a))) return rc;
     a.n_rs = lut->n_rs; a.n_perp = lut->n_perp; a.Rs = lut->Rs; a.gram = lut->gram; a.ldG = lut->ldG;
-    if (fast) { if (!(rc = amx_czb_prepare(ctx, lut, c.lam2, s))) rc = amx_launch_czb_fast(ctx, lut, a, pl, s); }
-    else rc = amx_big_dictionary(lut) ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s) : amx_launch_czb(ctx, a, pl, s);
+    if (rt.family == SF_CZB_FAST) { if (!(rc = amx_czb_prepare(ctx, lut, c.lam2, s, rt))) rc = amx_launch_czb_fast(ctx, lut, a, pl, s, rt); }
+    else rc = rt.family == SF_ENET_BIG ? amx_launch_enet_big(ctx, lut, a, pl, c.n, s, rt) : amx_launch_czb(ctx, a, pl, s, rt);
     return fit_close(ctx, c, rc);
 }
 
 }  // namespace
 
-// float32 signals in HBM (the image's dtype, core.py:136; lossless) are read in place by the NODDI kernels, by every wavefront-per-voxel
-// kernel, by FreeWater's matrix-core projection and by SANDI's (k_sandi_project); the other lane kernels get a float64 copy made on the device first.
+// The argument checks, then -- for the three small models -- the fit's route, once: a shape it refuses leaves here before anything is enqueued
+// (with the launches the fit had noted when it used to find out); float32 signals in HBM (the image's dtype, core.py:136; lossless) get a
+// float64 copy made on the device first where the route's kernels read float64 only.  (The NODDI kernels read either: noddi_fit_dev.)
 int amx_fit_dev(amx_ctx *ctx, const FitSpec &m, FitCall c)
 {
     int rc;
-    const bool f32 = ctx && c.lut && c.lut->model == m.model && c.y32 && c.n > 0;      // (else: fit_check says what is wrong)
-    if (f32 && ((m.model == 2 && !amx_fw_native_f32(ctx, c.lut->n_atoms, c.lut->nS, c.flags, c.lam2)) ||
-                (m.model == 3 && c.lut->nS <= kSandiShortNS && amx_use_lane_solver(ctx, c.lut->n_atoms, c.lam2)))) {      // (longer protocols: k_sandi_project reads either)
+    if ((rc = fit_check(ctx, m, c)) || c.n == 0) return rc;
+    if (m.model == 1) return noddi_fit_dev(ctx, m, c);
+    const SmallRoute rt = small_route(small_shape(c.lut), {c.n, c.lam1, c.lam2, c.flags, c.y32 != nullptr}, small_switches(ctx));
+    if (rt.refusal) {
+        for (int l = 0; l < rt.n_launch; l++) amx_note(ctx, rt.launch[l]);
+        return amx_bad(ctx, rt.error);
+    }
+    if (rt.widen) {
         const size_t nel = (size_t)c.n * c.lut->nS;
-        HIPCHK(ctx, hipSetDevice(ctx->device));
         if ((rc = amx_ensure(ctx, ctx->wy, nel * sizeof(double)))) return rc;
         widen_on_device(c.y32, (double *)ctx->wy.p, nel, c.stream);
         HIPCHK(ctx, hipGetLastError());
         c.y = (const double *)ctx->wy.p; c.y32 = nullptr;
     }
-    if ((rc = fit_check(ctx, m, c)) || c.n == 0) return rc;
     switch (m.model) {
-    case 1: return noddi_fit_dev(ctx, m, c);
-    case 2: return freewater_fit_dev(ctx, m, c);
-    case 3: return sandi_fit_dev(ctx, m, c);
-    default: return czb_fit_dev(ctx, m, c);
+    case 2: return freewater_fit_dev(ctx, m, c, rt);
+    case 3: return sandi_fit_dev(ctx, m, c, rt);
+    default: return czb_fit_dev(ctx, m, c, rt);
     }
 }
 

@@ -96,8 +96,7 @@ __device__ unsigned long long g_fw_ph[8], g_fw_pp[8];
 #define FWPH_T() 0ull
 #define FWPH_ADD(k, t0) (void)(t0)
 #endif
-constexpr int kTileRows = 16;          // signal values per voxel and transposition pass
-constexpr int kTileLd = 65;            // odd leading dimension (doubles) of the transposition tile [row][voxel]
+// (kTileRows, kTileLd, kProjKS -- what sizes the projection kernels' LDS and gates the route: amx_sizes.hpp)
 
 // per orientation, once per (dictionary, lambda2): the fp64 dictionary A [nS][NP], H^-1 [N][NP] and H = A'A + lambda2 I
 // [N][N] (NP = N rounded up to even).  One wavefront per orientation.
@@ -265,7 +264,6 @@ __global__ void __launch_bounds__(256, kFwProjOcc) k_fw_project(const FwArgs a)
 //   * the values of a voxel end up in four lanes (l & 15 equal): the passive-set bits are OR-ed across them.
 // Rows beyond the last full tile of 16 (nS = 65: one row) go through ordinary loads, zero-padded to a K-step.
 typedef double v4d __attribute__((ext_vector_type(4)));
-constexpr int kProjKS = 24;                // K-steps of dictionary registers: nS <= 96
 
 // F32: the signals are float32 in HBM (amx_freewater_fit_device_f32; 260 instead of 520 bytes per voxel): a tile of 16 values
 // of 64 voxels is 4 KB, four lanes fetch the 64 bytes of a voxel, pieces XOR-swizzled by (voxel >> 2) & 3, converted at the
@@ -535,7 +533,7 @@ __global__ void __launch_bounds__(256, 2) k_freewater_refill(const FwArgs a)
         // KKT point is reached in 2.9 solves per voxel from P0 (3.2 for block removals followed by Lawson-Hanson steps; the
         // longest voxel needs 7 instead of 14), and no coefficient vector has to survive from one trip to the next.
         // (The kernel is only launched with the warm start: for lambda2 < 1e-5, where H may be nearly singular, and for
-        // flag bit 31 (cold start) the fit goes to k_freewater_lane's Lawson-Hanson loop -- amx_fw_use_refill.)
+        // flag bit 31 (cold start) the fit goes to k_freewater_lane's Lawson-Hanson loop -- small_route.)
         bool done = false;
         if (active && !(c[0] == c[0])) done = true;             // non-finite signal: NaN maps, never iterate
         const bool slv = active && !done;
@@ -1047,29 +1045,23 @@ __global__ void __launch_bounds__(64 * (kFuseConsumers + 1), 2) k_freewater_fuse
 }
 
 static size_t refill_lds_bytes(int N, int nw) { return (size_t)nw * (2 * (128 * ((N * N + 127) / 128) + 2) + 2 + 2 * (64 * ((N + 1) & ~1) + 64)) * sizeof(double); }
-static size_t project_lds_bytes(int nS, int N, int nw)
-{
-    const int NP = (N + 1) & ~1;
-    return ((size_t)(nS + N) * NP + (size_t)nw * (kTileRows * kTileLd + 32)) * sizeof(double);
-}
 
 }  // namespace
 
 typedef void (*FwKernel)(const FwArgs);
 static int launch_refill(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s, FwKernel proj, FwKernel pmfma, FwKernel pmfma32, FwKernel kern, int N,
-                         FwKernel fused, FwKernel fused32, size_t fused_lds)
+                         FwKernel fused, FwKernel fused32, size_t fused_lds, const SmallRoute &rt)
 {
     int rc;
-    // one kernel (k_freewater_fused) when the protocol fits its pipeline: four or more full tiles of 16 values per voxel, dictionary
-    // operand in registers (AMX_FW_NO_FUSE=1: the projection + solver pair, for A/B)
-    if (a.c.nS >= 64 && a.c.nS <= 4 * kProjKS && !ctx->opt_fw_no_fuse) {
+    // one kernel (k_freewater_fused) when the protocol fits its pipeline (AMX_FW_NO_FUSE=1: the projection + solver pair, for A/B)
+    if (rt.family == SF_FW_FUSED) {
         FwKernel k = a.c.y32 != nullptr ? fused32 : fused;
         if ((rc = set_lds(ctx, k, fused_lds))) return rc;
         a.queue = pl.n_chunks + 60;                            // (misc word 60: zeroed with the plan counters)
-        a.sub_per_chunk = (amx_refill_chunk((long long)pl.n) + kFuseSub - 1) / kFuseSub;
+        a.sub_per_chunk = (rt.chunk + kFuseSub - 1) / kFuseSub;
         rec(ctx, 2, s);
         hipLaunchKernelGGL(k, dim3(2 * ctx->n_cu), dim3(64 * (kFuseConsumers + 1)), fused_lds, s, a);
-        amx_note(ctx, N == 11 ? "k_freewater_fused<11>" : "k_freewater_fused<12>");
+        amx_note(ctx, rt.launch[0]);
         AMX_TRACE(ctx, s, "FreeWater: projection (producer wavefront) + lane-per-voxel solver (consumers), one kernel");
         rec(ctx, 3, s);
         HIPCHK(ctx, hipGetLastError());
@@ -1081,21 +1073,20 @@ static int launch_refill(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s,
     if ((rc = amx_ensure(ctx, ctx->cproj, cbytes + (size_t)a.ldC * sizeof(unsigned)))) return rc;
     a.cproj = (double *)ctx->cproj.p;
     a.p0 = (unsigned *)((char *)ctx->cproj.p + cbytes);
-    const bool mfma = a.c.nS <= 4 * kProjKS;
-    const size_t lds_p = mfma ? (size_t)4 * (2 * 64 * 16 + 32) * sizeof(double) : project_lds_bytes(a.c.nS, N, 4), lds = refill_lds_bytes(N, 4);
+    const bool mfma = rt.mfma;      // (which is what reads float32 signals: a route without it has widened them)
+    const size_t lds_p = mfma ? (size_t)4 * (2 * 64 * 16 + 32) * sizeof(double) : fw_project_lds_bytes(a.c.nS, N, 4), lds = refill_lds_bytes(N, 4);
     if ((rc = set_lds(ctx, proj, lds_p)) || (rc = set_lds(ctx, pmfma, lds_p)) || (rc = set_lds(ctx, pmfma32, lds_p)) || (rc = set_lds(ctx, kern, lds))) return rc;
-    if (a.c.y32 != nullptr && !mfma) { ctx->err = "float32 signals need the matrix-core projection (amx_fw_native_f32)"; return AMX_E_BADARG; }
     const dim3 grid(((pl.max_chunks + 7) / 8) * 8);
     a.queue = pl.n_chunks + 60;                            // (misc word 60: zeroed with the plan counters)
-    a.sub_per_chunk = (amx_refill_chunk((long long)pl.n) + kSubChunk - 1) / kSubChunk;
+    a.sub_per_chunk = (rt.chunk + kSubChunk - 1) / kSubChunk;
     rec(ctx, 2, s);
     if (mfma && a.c.y32 != nullptr) hipLaunchKernelGGL(pmfma32, grid, dim3(256), lds_p, s, a);
     else if (mfma) hipLaunchKernelGGL(pmfma, grid, dim3(256), lds_p, s, a);
     else hipLaunchKernelGGL(proj, grid, dim3(256), lds_p, s, a);
-    amx_note(ctx, mfma ? "k_fw_project_mfma" : "k_fw_project");
+    amx_note(ctx, rt.launch[0]);
     AMX_TRACE(ctx, s, "A'y of every voxel");
     hipLaunchKernelGGL(kern, dim3(2 * ctx->n_cu), dim3(256), lds, s, a);
-    amx_note(ctx, "k_freewater_refill");
+    amx_note(ctx, rt.launch[1]);
     AMX_TRACE(ctx, s, "lane-per-voxel solver with refill");
     rec(ctx, 3, s);
     HIPCHK(ctx, hipGetLastError());
@@ -1132,24 +1123,23 @@ static int fw_prepare_n(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t
 // doubles per orientation of the cached tables (amx_debug_fetch)
 size_t amx_fw_table_words(const amx_lut *lut) { return lut->fw_N == 11 ? (size_t)fw_prep_words<11>(lut->nS) : (size_t)fw_prep_words<12>(lut->nS); }
 
-int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t s)
+int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, FwArgs &a, hipStream_t s, const SmallRoute &rt)
 {
-    return lut->n_atoms <= 11 ? fw_prepare_n<11>(ctx, lut, a, s) : fw_prepare_n<12>(ctx, lut, a, s);
+    return rt.N == 11 ? fw_prepare_n<11>(ctx, lut, a, s) : fw_prepare_n<12>(ctx, lut, a, s);
 }
 
-int amx_launch_fw_small(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s)
+int amx_launch_fw_small(amx_ctx *ctx, FwArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
-    // compile-time dictionary sizes: the reference's defaults (11 Human, 12 Mouse) exactly, 16 otherwise
-    const int n = a.c.n_atoms;
-    if (amx_fw_use_refill(ctx, n, a.c.nS, a.c.flags, a.c.lam2)) {
-        if (n <= 11) return launch_refill(ctx, a, pl, s, k_fw_project<11>, k_fw_project_mfma<11, false>, k_fw_project_mfma<11, true>, k_freewater_refill<11>, 11,
-                                          k_freewater_fused<11, false>, k_freewater_fused<11, true>, fuse_lds_bytes<11>(a.c.nS & 15));
+    // compile-time dictionary sizes (rt.N): the reference's defaults (11 Human, 12 Mouse) exactly, 16 otherwise
+    if (rt.family != SF_LANE) {
+        if (rt.N == 11) return launch_refill(ctx, a, pl, s, k_fw_project<11>, k_fw_project_mfma<11, false>, k_fw_project_mfma<11, true>, k_freewater_refill<11>, 11,
+                                             k_freewater_fused<11, false>, k_freewater_fused<11, true>, fuse_lds_bytes<11>(a.c.nS & 15), rt);
         return launch_refill(ctx, a, pl, s, k_fw_project<12>, k_fw_project_mfma<12, false>, k_fw_project_mfma<12, true>, k_freewater_refill<12>, 12,
-                             k_freewater_fused<12, false>, k_freewater_fused<12, true>, fuse_lds_bytes<12>(a.c.nS & 15));
+                             k_freewater_fused<12, false>, k_freewater_fused<12, true>, fuse_lds_bytes<12>(a.c.nS & 15), rt);
     }
-    if (n <= 11) return launch_lane(ctx, a, pl, s, k_freewater_lane<11>, sizeof(float), 11);
-    if (n == 12) return launch_lane(ctx, a, pl, s, k_freewater_lane<12>, sizeof(float), 12);
-    return launch_lane(ctx, a, pl, s, k_freewater_lane<16>, sizeof(float), 16);
+    if (rt.N == 11) return launch_lane(ctx, a, pl, s, k_freewater_lane<11>, rt);
+    if (rt.N == 12) return launch_lane(ctx, a, pl, s, k_freewater_lane<12>, rt);
+    return launch_lane(ctx, a, pl, s, k_freewater_lane<16>, rt);
 }
 
 #ifdef AMX_FW_PHASES

@@ -3,6 +3,7 @@
 #include "../../include/amico_amd.h"
 #include "amx_kernels.hpp"
 #include "amx_noddi_route.hpp"
+#include "amx_small_route.hpp"
 #include "amx_stage.hpp"
 #include <climits>
 #include <cstdio>
@@ -12,7 +13,6 @@
 #include <utility>
 #include <vector>
 
-constexpr int kChunk = 256;        // voxels of one orientation per workgroup
 constexpr int kListGrid = 512;     // workgroups of the large-MAXP re-run pass
 constexpr int kEv = 20;           // event pairs: 0 whole call, 1-3 NODDI stage kernels, 4 small-model solver, 5-7 NODDI GEMM + seed + certificate kernels of stages 1 / 2 / 3, 8 k_nnls_seed<1> alone, 9 k_lasso_seed alone
 
@@ -421,73 +421,38 @@ int amx_launch_noddi_big(amx_ctx *ctx, const amx::NoddiArgs &a, const Plan &pl, 
 int amx_launch_noddi_s1(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
 int amx_launch_noddi_s2(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
 int amx_launch_noddi_s3(amx_ctx *ctx, amx::NoddiArgs &a, const Plan &pl, hipStream_t s, const amx::NoddiKernel &k);
-int amx_launch_fw(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_sandi(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
-int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
+// FreeWater, SANDI and CylinderZeppelinBall follow the fit's route too (amx_small_route.hpp: amx_fit_dev computes it once)
+inline amx::SmallShape small_shape(const amx_lut *l) { return {l->model, l->nS, l->ldA, l->n_atoms, l->ndirs, l->gram != nullptr}; }
+inline amx::SmallSwitches small_switches(const amx_ctx *c) { return {c->opt_wave_per_voxel, c->opt_no_refill, c->opt_sandi_atom_space, c->opt_fw_no_fuse}; }
+int amx_launch_fw(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
+int amx_launch_sandi(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
+int amx_launch_czb(amx_ctx *ctx, amx::CzbArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
 int amx_launch_batched(amx_ctx *ctx, amx::BatchedArgs &a, const Plan &pl, hipStream_t s, bool ridge, bool dense = false);
 int amx_launch_batched_big(amx_ctx *ctx, const amx::BatchedArgs &a, const amx_dict *dict, const Plan &pl, hipStream_t s);   // amx_batched_big.hip: a dense dictionary's voxels beyond 48 atoms
 int amx_build_dict_gram(amx_ctx *ctx, const amx_dict *dict);                                                              // ... and its Gram tables
 // FreeWater, SANDI and CylinderZeppelinBall on dictionaries of kSmallMaxAtoms + 1 .. kBigMaxAtoms atoms (amx_enet_big.hip): the Gram tables made at
-// the upload, and k_enet_big -- a workgroup per voxel, in bucket order (SANDI: the voxels in order).  The route is chosen from the dictionary's shape alone.
-constexpr int kSmallMaxAtoms = 64;     // what the wavefront-per-voxel kernels of these models hold (a lane per atom)
-constexpr int kBigMaxAtoms = 256;      // a thread per atom
-static inline bool amx_big_dictionary(const amx_lut *lut) { return lut->n_atoms > kSmallMaxAtoms; }
+// the upload, and k_enet_big -- a workgroup per voxel, in bucket order (SANDI: the voxels in order)
+static inline bool amx_big_dictionary(const amx_lut *lut) { return lut->n_atoms > amx::kSmallMaxAtoms; }      // (the upload's question; a fit asks its route)
 int amx_build_big_gram(amx_ctx *ctx, amx_lut *lut);
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::FwArgs &a, const Plan &pl, int64_t n, hipStream_t s);
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s);
-int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s);
-int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
-// doubles of the per-lambda2 tables cached in a dictionary handle (per orientation where the model has orientations): amx_debug_fetch
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::FwArgs &a, const Plan &pl, int64_t n, hipStream_t s, const amx::SmallRoute &rt);
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s, const amx::SmallRoute &rt);
+int amx_launch_enet_big(amx_ctx *ctx, const amx_lut *lut, const amx::CzbArgs &a, const Plan &pl, int64_t n, hipStream_t s, const amx::SmallRoute &rt);
+// the per-dictionary tables a route names (SmallRoute::tables), cached in the dictionary handle for one lambda2 (SANDI's row-space tables: lambda1 too)
+int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, amx::FwArgs &a, hipStream_t s, const amx::SmallRoute &rt);
+int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, amx::SandiArgs &a, hipStream_t s);
+int amx_sandi_long_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
+int amx_czb_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s, const amx::SmallRoute &rt);
+// doubles of those tables (per orientation where the model has orientations): amx_debug_fetch
 size_t amx_czb_table_stride(int nS);
 size_t amx_fw_table_words(const amx_lut *lut);
 size_t amx_sandi_table_words();
 size_t amx_sandi_long_table_words(const amx_lut *lut);
-int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s);
+int amx_launch_czb_fast(amx_ctx *ctx, const amx_lut *lut, amx::CzbArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
 // lane-per-voxel variants for dictionaries of <= 16 atoms (amx_fw_lane.hip, amx_sandi_lane.hip)
-int amx_launch_fw_small(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s);
-int amx_fw_prepare(amx_ctx *ctx, const amx_lut *lut, amx::FwArgs &a, hipStream_t s);
-int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, amx::SandiArgs &a, hipStream_t s);   // before amx_launch_fw when the refill path runs
-int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s);
+int amx_launch_fw_small(amx_ctx *ctx, amx::FwArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
+int amx_launch_sandi_small(amx_ctx *ctx, amx::SandiArgs &a, const Plan &pl, hipStream_t s, const amx::SmallRoute &rt);
 // SANDI, protocols of more than kSandiShortNS volumes (amx_sandi_long.hip): projection on the matrix cores, then a Gram-space solver
-constexpr int kSandiShortNS = 128;     // up to here a wavefront's lanes hold the signal rows (k_sandi<2>) / a lane walks its own row (k_sandi_lane)
-int amx_sandi_long_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStream_t s);
-int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s);
-// Lane-per-voxel solvers: start the active set from ALL atoms and drop the non-positive ones in blocks (unique optimum
-// with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
-// the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.
-__host__ __device__ static inline bool amx_warm_start(double lam2, unsigned flags) { return lam2 >= 1e-5 && !(flags & 0x80000000u); }
-// FreeWater with lanes that never idle (k_freewater_refill, amx_fw_lane.hip): maps only (the error maps / AMX_F_CORRECTED
-// need the signal again and stay with k_freewater_lane; AMX_F_FW_ISO needs only x and selects nothing), <= 12 atoms; chunks of up to 4096 voxels per workgroup
-// voxels of one orientation per workgroup of the refill kernel: large enough to keep the lanes fed (the buffer needs a
-// pool to draw from), small enough for ~3 rounds of workgroups over the chip (measured on 2 M voxels: 512 -> 1.83 ms,
-// 1024 -> 1.79, 2048 -> 1.93, 4096 -> 2.54)
-static inline int amx_refill_chunk(long long n_vox)
-{
-    const long long c = n_vox / 1536;
-    return (int)(c < 512 ? 512 : (c > 2048 ? 2048 : c));
-}
-// (the projection + block-pivoting kernels assume the warm start: with lambda2 < 1e-5 the fit goes to the
-//  Lawson-Hanson lane kernels -- single exchanges from the empty set, which is all block pivoting could do there, ran into
-//  the iteration cap on 15 % of the voxels at lambda2 = 1e-6)
-static inline bool amx_fw_use_refill(const amx_ctx *ctx, int n_atoms, int nS, unsigned flags, double lam2)
-{
-    if (!amx_warm_start(lam2, flags)) return false;
-    if (ctx->opt_no_refill || ctx->opt_wave_per_voxel) return false;
-    return n_atoms <= 12 && (flags & (AMX_F_RMSE | AMX_F_NRMSE | AMX_F_CORRECTED)) == 0 &&
-           ((size_t)nS * 12 + 144 + 4 * (16 * 65 + 12 * 64 + 32)) * sizeof(double) + 16 <= 80 * 1024;
-}
-// float32 signals in HBM are read natively by the NODDI kernels, by the wavefront-per-voxel kernels of every model (load_rows) and by
-// FreeWater's matrix-core projection; the other lane kernels get a float64 copy made on the device first (k_widen)
-static inline bool amx_fw_native_f32(const amx_ctx *ctx, int n_atoms, int nS, unsigned flags, double lam2);
-// lane-per-voxel solvers work on H = A'A + lambda2 I (Gram space): they need the ridge to bound cond(H); with
-// lambda2 (nearly) 0 the problem goes to the QR solver in A-space (wavefront per voxel), like the reference's lasso,
-// which accepts any lambda2 >= 0
-static inline bool amx_use_lane_solver(const amx_ctx *ctx, int n_atoms, double lam2) { return n_atoms <= 16 && lam2 >= 1e-9 && !ctx->opt_wave_per_voxel; }
-static inline bool amx_fw_native_f32(const amx_ctx *ctx, int n_atoms, int nS, unsigned flags, double lam2)
-{
-    if (!amx_use_lane_solver(ctx, n_atoms, lam2)) return true;                     // wavefront per voxel: load_rows
-    return amx_fw_use_refill(ctx, n_atoms, nS, flags, lam2) && nS <= 96;
-}
+int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const amx::SandiArgs &a, int64_t n, hipStream_t s, const amx::SmallRoute &rt);
 
 // ------------------------------------------------------------------ what the entry-point units share (library-internal: not exported)
 #pragma GCC visibility push(hidden)

@@ -239,16 +239,16 @@ __device__ __forceinline__ double lane_rss(const AT *As, const double *__restric
     AT *As = reinterpret_cast<AT *>(smem_s);                                                     \
     double *Hs = reinterpret_cast<double *>(smem_s + (((size_t)words * sizeof(AT) + 15) & ~(size_t)15));
 
+// (the LDS -- lane_lds_bytes, amx_sizes.hpp -- and the note are the route's)
 template <typename Args, typename K>
-int launch_lane(amx_ctx *ctx, Args &a, const Plan &pl, hipStream_t s, K kern, size_t elem, int N)
+int launch_lane(amx_ctx *ctx, Args &a, const Plan &pl, hipStream_t s, K kern, const amx::SmallRoute &rt)
 {
-    const size_t lds = (((size_t)a.c.nS * a.c.ldA * elem + 15) & ~(size_t)15) + (size_t)N * N * sizeof(double);
-    if (lds > 160 * 1024) { ctx->err = "dictionary tile does not fit the 160 KB LDS of a CU"; return AMX_E_BADARG; }
+    const size_t lds = rt.lds;
     int rc;
     if ((rc = set_lds(ctx, kern, lds))) return rc;
     rec(ctx, 2, s);
     hipLaunchKernelGGL(kern, dim3(((pl.max_chunks + 7) / 8) * 8), dim3(256), lds, s, a);
-    amx_note(ctx, "lane-per-voxel solver (k_freewater_lane / k_sandi_lane)");
+    amx_note(ctx, rt.launch[0]);
     AMX_TRACE(ctx, s, "lane-per-voxel solver");
     rec(ctx, 3, s);
     HIPCHK(ctx, hipGetLastError());

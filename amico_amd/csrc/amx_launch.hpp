@@ -24,13 +24,15 @@ static int launch_lds(amx_ctx *ctx, K kern, dim3 grid, dim3 block, size_t lds, h
 // main pass over the orientation chunks + re-run of the voxels whose passive set overflowed
 using amx::kLdsPerCU;
 
-// launch_pair's LDSF for a NODDI stage kernel, whose wavefront count and LDS the route has fixed.  launch_pair halves nw while LDSF(nw) does
-// not fit: this one REPORTS every count above the route's as too large (kLdsPerCU + 1, not a real size), so that the loop stops at the
-// route's count with the route's LDS; a route that does not fit is still refused by launch_pair's own check.
-static inline auto route_lds(const amx::NoddiKernel &k)
+// launch_pair's LDSF for a kernel whose wavefront count and LDS its route has fixed (a NODDI stage kernel, a small model's wavefront-per-voxel
+// kernel).  launch_pair halves nw while LDSF(nw) does not fit: this one REPORTS every count above the route's as too large (kLdsPerCU + 1,
+// not a real size), so that the loop stops at the route's count with the route's LDS; a NODDI route that does not fit is still refused by
+// launch_pair's own check (a small model's was refused by amx_fit_dev).
+static inline auto route_lds(int waves, size_t lds)
 {
-    return [waves = k.waves, lds = k.lds](int nw) { return nw > waves ? kLdsPerCU + 1 : lds; };
+    return [waves, lds](int nw) { return nw > waves ? kLdsPerCU + 1 : lds; };
 }
+static inline auto route_lds(const amx::NoddiKernel &k) { return route_lds(k.waves, k.lds); }
 
 // LDSF(nw) -> dynamic LDS bytes of the main kernel with nw wavefronts per workgroup
 template <int NW, typename Args, typename KM, typename KL, typename LDSF>

@@ -191,7 +191,7 @@ int amx_lut_upload_czb(amx_ctx *ctx, const float *wmr, const float *wmh, const f
         *out = lut;
         return AMX_OK;
     }
-    lut->ldG = 64;
+    lut->ldG = kCzbLdG;
     const size_t gbytes = (size_t)ndirs * n_atoms * lut->ldG * sizeof(double);
     const size_t lds = (size_t)nS * lut->ldA * sizeof(float);
     if (hipMalloc((void **)&lut->gram, gbytes) != hipSuccess) { amx_lut_destroy(lut); return amx_bad(ctx, "amx_lut_upload_czb: out of device memory"); }

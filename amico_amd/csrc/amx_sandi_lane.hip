@@ -352,8 +352,6 @@ size_t amx_sandi_table_words() { return (size_t)kSandiTableWords; }      // (amx
 // tables of the row-space solver, cached in the dictionary handle for one (lambda1, lambda2)
 int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, SandiArgs &a, hipStream_t s)
 {
-    a.tables = nullptr;
-    if (!(lut->nS == 6 && lut->n_atoms == 15 && amx_warm_start(a.c.lam2, a.c.flags))) return AMX_OK;   // other shapes / cold start: atom-space kernels
     if (lut->sandi_lam1 != a.c.lam1 || lut->sandi_lam2 != a.c.lam2 || !lut->sandi_prep) {
         if (lut->sandi_prep) HIPCHK(ctx, hipDeviceSynchronize());                              // (a fit with the old tables may still run)
         if (!lut->sandi_prep) HIPCHK(ctx, hipMalloc((void **)&lut->sandi_prep, kSandiTableWords * sizeof(double)));
@@ -369,24 +367,22 @@ int amx_sandi_prepare(amx_ctx *ctx, const amx_lut *lut, SandiArgs &a, hipStream_
     return AMX_OK;
 }
 
-int amx_launch_sandi_small(amx_ctx *ctx, SandiArgs &a, const Plan &pl, hipStream_t s)
+int amx_launch_sandi_small(amx_ctx *ctx, SandiArgs &a, const Plan &pl, hipStream_t s, const SmallRoute &rt)
 {
-    const int n = a.c.n_atoms;                // SANDI default: 5 + 5 + 5 = 15 atoms
-    // the default protocol after the directional average (b0 + 5 shells = 6 values, 15 atoms): row-space solver
+    // the default protocol after the directional average (b0 + 5 shells = 6 values, 15 atoms: SANDI's default 5 + 5 + 5): row-space solver
     // (a refill variant of this kernel -- lanes drawing the next voxel from a global counter -- was measured SLOWER,
     //  2.65 vs 2.29 ms per 1 M voxels: SANDI's optimum is dense, 12 of 15 atoms, so the lanes of a wavefront need
     //  nearly the same number of steps and there is no idle time to win back)
-    if (a.c.nS == 6 && n == 15 && amx_warm_start(a.c.lam2, a.c.flags) && !ctx->opt_sandi_atom_space) {
-        if (!a.tables) { ctx->err = "amx_launch_sandi_small: dictionary tables missing (amx_sandi_prepare)"; return AMX_E_BADARG; }
+    if (rt.family == SF_SANDI_ROWS) {
         rec(ctx, 2, s);
         hipLaunchKernelGGL((k_sandi_rows<6, 15>), dim3(a.n_lin > 0 ? (a.n_lin + 255) / 256 : ((pl.max_chunks + 7) / 8) * 8), dim3(256), 0, s, a);
-        amx_note(ctx, "k_sandi_rows<6,15>");
+        amx_note(ctx, rt.launch[0]);
         AMX_TRACE(ctx, s, "row-space SANDI solver");
         rec(ctx, 3, s);
         HIPCHK(ctx, hipGetLastError());
         return AMX_OK;
     }
-    if (n <= 12) return launch_lane(ctx, a, pl, s, k_sandi_lane<12>, sizeof(double), 12);
-    if (n <= 15) return launch_lane(ctx, a, pl, s, k_sandi_lane<15>, sizeof(double), 15);
-    return launch_lane(ctx, a, pl, s, k_sandi_lane<16>, sizeof(double), 16);
+    if (rt.N == 12) return launch_lane(ctx, a, pl, s, k_sandi_lane<12>, rt);
+    if (rt.N == 15) return launch_lane(ctx, a, pl, s, k_sandi_lane<15>, rt);
+    return launch_lane(ctx, a, pl, s, k_sandi_lane<16>, rt);
 }

@@ -358,9 +358,7 @@ __global__ void __launch_bounds__(64) k_sandi_gram_wave(const SandiLongArgs a)
     }
 }
 
-int sl_ksteps(int nS) { return 4 * ((nS + 15) / 16); }
-int sl_padded_atoms(int n_atoms) { return ((n_atoms + 15) / 16) * 16; }
-
+// (sl_ksteps, sl_padded_atoms: amx_small_route.hpp)
 template <int N>
 void launch_gram_lane(const SandiLongArgs &f, hipStream_t s) { hipLaunchKernelGGL(k_sandi_gram_lane<N>, dim3((f.n + 255) / 256), dim3(256), 0, s, f); }
 
@@ -392,9 +390,8 @@ int amx_sandi_long_prepare(amx_ctx *ctx, const amx_lut *lut, double lam2, hipStr
 }
 
 // the voxels in order (one dictionary: no plan); counts straight into the status words
-int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const SandiArgs &a, int64_t n, hipStream_t s)
+int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const SandiArgs &a, int64_t n, hipStream_t s, const SmallRoute &rt)
 {
-    if (!lut->sandi_long_prep) { ctx->err = "amx_launch_sandi_long: dictionary tables missing (amx_sandi_long_prepare)"; return AMX_E_BADARG; }
     SandiLongArgs f;
     memset(&f, 0, sizeof f);
     f.y = a.c.y; f.y32 = a.c.y32; f.n = (int)n; f.nS = lut->nS; f.n_atoms = lut->n_atoms; f.n_rs = a.n_rs; f.n_in = a.n_in;
@@ -407,28 +404,27 @@ int amx_launch_sandi_long(amx_ctx *ctx, const amx_lut *lut, const SandiArgs &a, 
     int rc;
     if ((rc = amx_ensure(ctx, ctx->cgemm, (size_t)n_blk * f.rows * 64 * sizeof(double)))) return rc;
     f.Cb = (double *)ctx->cgemm.p;
-    const size_t lds = (size_t)f.ksteps * 64 * sizeof(double);
-    if (lds > kLdsPerCU) { ctx->err = "k_sandi_project: the A' operand of one atom tile does not fit the 160 KB LDS of a CU"; return AMX_E_BADARG; }
+    const size_t lds = rt.lds;              // (the A' operand of one atom tile: ksteps x 64 doubles)
     const int per_cu = (int)(kLdsPerCU / lds) < 8 ? (int)(kLdsPerCU / lds) : 8;      // (8 workgroups of 4 wavefronts fill a CU)
     const int grid = n_blk < ctx->n_cu * per_cu ? n_blk : ctx->n_cu * per_cu;
     rec(ctx, 4, s);                          // (amx_last_kernel_ms: 2 = the projection, 1 = the solver)
     if (f.y32) rc = launch_lds(ctx, k_sandi_project<float>, dim3(grid), dim3(256), lds, s, f);
     else rc = launch_lds(ctx, k_sandi_project<double>, dim3(grid), dim3(256), lds, s, f);
     if (rc) return rc;
-    amx_note(ctx, f.y32 ? "k_sandi_project<float>" : "k_sandi_project<double>");
+    amx_note(ctx, rt.launch[0]);
     AMX_TRACE(ctx, s, "c = A'y, y'y on the matrix cores");
     rec(ctx, 5, s);
     rec(ctx, 2, s);
-    if (amx_use_lane_solver(ctx, f.n_atoms, f.lam2)) {
-        if (f.n_atoms <= 12) launch_gram_lane<12>(f, s);
-        else if (f.n_atoms <= 15) launch_gram_lane<15>(f, s);
+    if (rt.family == SF_SANDI_LONG_LANE) {
+        if (rt.N == 12) launch_gram_lane<12>(f, s);
+        else if (rt.N == 15) launch_gram_lane<15>(f, s);
         else launch_gram_lane<16>(f, s);
-        amx_note(ctx, f.n_atoms <= 12 ? "k_sandi_gram_lane<12>" : (f.n_atoms <= 15 ? "k_sandi_gram_lane<15>" : "k_sandi_gram_lane<16>"));
+        amx_note(ctx, rt.launch[1]);
         AMX_TRACE(ctx, s, "Gram-space solver, one voxel per lane");
     } else {
         const int64_t cap = (int64_t)ctx->n_cu * 16;
         hipLaunchKernelGGL(k_sandi_gram_wave, dim3((unsigned)(n < cap ? n : cap)), dim3(64), 0, s, f);
-        amx_note(ctx, "k_sandi_gram_wave");
+        amx_note(ctx, rt.launch[1]);
         AMX_TRACE(ctx, s, "Gram-space solver, one wavefront per voxel");
     }
     rec(ctx, 3, s);

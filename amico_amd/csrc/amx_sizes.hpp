@@ -57,4 +57,33 @@ inline size_t gemm_lds(int n_cols, int rows, int ks)
 inline int gemm_passes(int nS) { return (nS + 159) / 160; }
 inline int gemm_window(int nS) { const int np = gemm_passes(nS); return ((nS + np - 1) / np + 3) & ~3; }   // samples per window, a multiple of 4
 
+// ------------------------------------------------------------------ FreeWater, SANDI, CylinderZeppelinBall (routed by amx_small_route.hpp)
+// dynamic LDS of a lane-per-voxel kernel (amx_lane_qp.hpp: AMX_SMALL_LDS): the tile in elements of `elem` bytes, then H [N][N]
+inline size_t lane_lds_bytes(size_t elem, int nS, int ldA, int N) { return (((size_t)nS * ldA * elem + 15) & ~(size_t)15) + (size_t)N * N * sizeof(double); }
+// FreeWater's projection kernels (amx_fw_lane.hip)
+constexpr int kTileRows = 16;          // signal values per voxel and transposition pass
+constexpr int kTileLd = 65;            // odd leading dimension (doubles) of the transposition tile [row][voxel]
+constexpr int kProjKS = 24;            // K-steps of dictionary registers of the matrix-core projection: nS <= 4 kProjKS = 96
+// k_fw_project: Ad f64 [nS][NP] | Hi f64 [N][NP] | per wavefront: Tt [kTileRows][kTileLd], Vb int[64]
+inline size_t fw_project_lds_bytes(int nS, int N, int nw)
+{
+    const int NP = (N + 1) & ~1;
+    return ((size_t)(nS + N) * NP + (size_t)nw * (kTileRows * kTileLd + 32)) * sizeof(double);
+}
+// k_enet_big (amx_bpp.hpp: Work): the workgroup's vectors in LDS, one block of vec_bytes(m, n) bytes
+namespace bpp {
+constexpr int kThreads = 256;
+constexpr size_t vec_bytes(int m, int n)
+{
+    const size_t mp = (size_t)((m + 1) & ~1), npd = (size_t)((n + 1) & ~1), n4 = (size_t)((n + 3) & ~3);
+    return ((2 * mp + 9 * npd + kThreads + 2) * sizeof(double) + (5 * n4 + 16) * sizeof(int) + 15) & ~(size_t)15;
+}
+}  // namespace bpp
+
 }  // namespace amx
+
+constexpr int kChunk = 256;        // voxels of one orientation per workgroup
+// Lane-per-voxel solvers: start the active set from ALL atoms and drop the non-positive ones in blocks (unique optimum
+// with lambda2 > 0, so the path is free; dense optima are reached in 3-4 factorisations).  Flag bit 31 asks for the Lawson-Hanson start from
+// the empty set instead (a retired A/B switch set it; no caller does).  Needs a ridge that keeps the full system well conditioned.
+constexpr bool amx_warm_start(double lam2, unsigned flags) { return lam2 >= 1e-5 && !(flags & 0x80000000u); }

@@ -524,6 +524,17 @@ int amx_prep_route(int nS, int n_out, int n_b0, int n_gidx, int identity, int di
 #define AMX_ROUTE_WORDS 96
 int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64_t n_vox, int64_t call_vox, double lambda1, double lambda2,
                     char *path, int cap, int64_t out[AMX_ROUTE_WORDS]);
+/* The same for the FreeWater (model 2), SANDI (3) and CylinderZeppelinBall (4) fits (csrc/amx_small_route.hpp): the route of a fit of n_vox
+ * voxels on a dictionary of nS volumes and n_atoms atoms, as the model's upload builds it.  flags: the fit's AMX_F_*; f32: the signals are
+ * float32 in HBM; switches_mask: bit 0 AMX_WAVE_PER_VOXEL, 1 AMX_NO_REFILL, 2 AMX_SANDI_ATOM_SPACE, 3 AMX_FW_NO_FUSE (0: the product path).
+ * note_buf: the launches in the format of amx_last_path; for a shape the fit refuses (out[12] != 0: it returns AMX_E_BADARG before
+ * anything is enqueued) a newline and the text of amx_last_error follow.  out: family (SmallFamily), build N, signal rows per lane, projection
+ * on the matrix cores, float32 signals widened first, voxels per bucketing chunk (0: no bucketing), per chunk of the second plan (0: none),
+ * tables to prepare (SmallTables), voxels in order (no plan, no per-call counters), padded volumes of the CylinderZeppelinBall tables,
+ * wavefronts per workgroup, LDS bytes, LDS bytes of the re-run pass, refusal (SmallRefusal), number of launches.                              */
+#define AMX_SMALL_ROUTE_WORDS 15
+int amx_small_route(int model, int nS, int n_atoms, int ndirs, int64_t n_vox, double lambda1, double lambda2, unsigned flags, int f32,
+                    unsigned switches_mask, char *note_buf, int cap, int64_t out[AMX_SMALL_ROUTE_WORDS]);
 /* What the plan's last gather launched (read-only): the kernel's name into buf, out = {workgroups, threads per workgroup, LDS bytes} */
 int amx_prep_last_launch(const amx_prep *p, char *buf, int cap, int64_t out[3]);
 /* The gather with the tensor fit taken along (round 5): y AND the principal directions of core.py:431-436, 456-458 in ONE pass over

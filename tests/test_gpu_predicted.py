@@ -208,8 +208,8 @@ def _czb_signals(n, seed):
 
 # name: (model, voxels, rmse asked of the device, lambdas, what ctx.last_path() must name (None: whatever it takes), what it must not)
 # Every fit runs with return_x and rmse=True and keeps its default fast path -- the NODDI chain and k_sandi_rows are not gated on the
-# flag.  Free-Water's and CylinderZeppelinBall's fast kernels are the maps-only ones (amx_fw_use_refill and the `fast` test of
-# czb_fit_dev exclude AMX_F_RMSE): for them the fast path is run without the error map, and a second case runs WITH it on whatever
+# flag.  Free-Water's and CylinderZeppelinBall's fast kernels are the maps-only ones (small_route, csrc/amx_small_route.hpp: the refill
+# and the fast route exclude AMX_F_RMSE): for them the fast path is run without the error map, and a second case runs WITH it on whatever
 # kernels that takes -- doComputeRMSE beside doSavePredictedSignal is what a user looking at residuals sets --, same bounds.
 FITS = {
     'noddi seeded chain': ('noddi', 24000, True, (0.5, 1e-3), 'k_nnls_seed<1', None),         # (the threshold is 22 528 voxels)
