@@ -1153,13 +1153,14 @@ def prep_route(nS, n_out, n_b0, n_gidx, identity, direct, inplace):
 NODDI_BUILDS = ('none', 'small', 'f32_8', 'f64_12', 'f64_nw', 'f32_nw', 'global', 'gram', 'gram_left', 'qr', 'big_all')      # NoddiBuild (csrc/amx_noddi_route.hpp)
 NODDI_ROUTE_WORDS = ('seeds', 'global', 'gemm_ks', 'gemm_passes', 'gemm_window', 'gcert', 'repair', 'rescue', 'tile_in_lds', 'seeds2', 'gcert2', 'wide',
                      'third', 'min_items', 'seed2_max_atoms', 'seed2_trip_add', 'left2_second_half', 'left2_count', 'seed_occ2', 'seed2_occ2',
-                     'seed_chunk', 'seed_waves', 'seed1_waves', 'seed2_waves', 's1', 's2', 's2_gram', 's3', 'n_launch')
+                     'seed_chunk', 'seed_waves', 'seed1_waves', 'seed2_waves', 's1', 's2', 's2_gram', 's3', 'n_launch', 'gemm', 'NR')
+NODDI_GEMMS = ('none', 'windows', '25_9', '25', '40')      # NoddiGemm
 
 
 def noddi_route(nS, n_wm, n_dwi, ndirs, is_exvivo, n_vox, call_vox=0, lambda1=0.5, lambda2=1e-3):
     """which kernels a NODDI fit of n_vox voxels (a batch of a call of call_vox voxels; 0: the call itself) launches on a dictionary of this
     shape, every switch at its default, without a device (amx_noddi_route) -> the words of NODDI_ROUTE_WORDS (flags as bool, s1 / s2 / s3 as
-    names of NODDI_BUILDS), 'path' in the format of Context.last_path() and 'launches': [(kernel, wavefronts, LDS bytes, LDS bytes of its
+    names of NODDI_BUILDS, gemm of NODDI_GEMMS), 'path' in the format of Context.last_path() and 'launches': [(kernel, wavefronts, LDS bytes, LDS bytes of its
     re-run pass)] in launch order"""
     out = np.zeros(96, dtype=np.int64)
     buf = C.create_string_buffer(2048)
@@ -1172,6 +1173,7 @@ def noddi_route(nS, n_wm, n_dwi, ndirs, is_exvivo, n_vox, call_vox=0, lambda1=0.
         rt[k] = bool(rt[k])
     for k in ('s1', 's2', 's3'):
         rt[k] = NODDI_BUILDS[rt[k]]
+    rt['gemm'] = NODDI_GEMMS[rt['gemm']]
     rt['path'] = buf.value.decode()
     names = rt['path'].split(' -> ')
     w = out[len(NODDI_ROUTE_WORDS):len(NODDI_ROUTE_WORDS) + 3 * rt['n_launch']].reshape(-1, 3)

@@ -519,8 +519,8 @@ int amx_prep_route(int nS, int n_out, int n_b0, int n_gidx, int identity, int di
  * launches in the format of amx_last_path.  out: seeds, global tile, gemm K-steps, gemm passes, gemm window, gcert, repair, rescue, rescue tile
  * in LDS, seeds2, gcert2, wide, third, third-pass min_items, seed-2 max_atoms, seed-2 trip-cap increment, LASSO left-overs in the second half,
  * their count array, seed occ2, seed-2 occ2, seed chunk, wavefronts of the lane kernels / of k_nnls_seed<1> / of k_lasso_seed, build of the
- * stage-1 / stage-2 kernel (NoddiBuild, csrc/amx_noddi_route.hpp), stage 2 in Gram space, build of the stage-3 kernel, number of launches;
- * then per launch {wavefronts per workgroup, LDS bytes, LDS bytes of its re-run pass}.                                                      */
+ * stage-1 / stage-2 kernel (NoddiBuild, csrc/amx_noddi_route.hpp), stage 2 in Gram space, build of the stage-3 kernel, number of launches,
+ * build of the table kernel (NoddiGemm), signal rows per lane of the projection kernels; then per launch {wavefronts per workgroup, LDS bytes, LDS bytes of its re-run pass}.                                                      */
 #define AMX_ROUTE_WORDS 96
 int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64_t n_vox, int64_t call_vox, double lambda1, double lambda2,
                     char *path, int cap, int64_t out[AMX_ROUTE_WORDS]);
