@@ -35,6 +35,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
            'amx_noise_b0_rows_device', 'amx_noise_b0_rows_device_f32', 'amx_prep_noise_b0_device', 'amx_nanmedian_device',
+           'amx_prep_noise_mppca_device', 'amx_mppca_route',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample', 'amx_lut_route',
@@ -231,6 +232,8 @@ def lib():
         f_.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, c_i32p, C.c_int, c_vp, c_vp, c_vp, c_vp]      # ctx, S, n, nS, b0_idx (host), n_b0, mean, sd, ratio, stream
     L.amx_prep_noise_b0_device.argtypes = [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]                 # ctx, plan, img, mean, sd, ratio, stream
     L.amx_nanmedian_device.argtypes = [c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]                      # ctx, v, n, out[2], count, stream
+    L.amx_prep_noise_mppca_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]   # ctx, plan, img, patch, sigma, n_signal, mean, ratio, eig, stream
+    L.amx_mppca_route.argtypes = [C.c_int, C.c_int, C.c_int, c_i64p, c_i64p]                         # nS, patch, n_cols, dims[3], out[10]
     L.amx_prep_sanitize.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
     L.amx_prep_sanitize_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp]
     L.amx_sanitize_device_f32.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_float, c_vp]
@@ -1047,6 +1050,14 @@ class Prep:
         self.ctx.check(lib().amx_prep_noise_b0_device(self.ctx._h, self._h, c_vp(d_img), c_vp(d_mean or 0), c_vp(d_sd or 0), c_vp(d_ratio or 0),
                                                       c_vp(stream or 0)))
 
+    def noise_mppca_device(self, d_img, patch=5, d_sigma=None, d_nsignal=None, d_mean=None, d_ratio=None, d_eig=None, stream=None):
+        """device pointers (ints): the image's element buffer -> per voxel of mask == 1 the Marchenko-Pastur noise level of its patch of
+        edge `patch` (3 | 5), the number of signal components, the b0 mean and mean / sigma, f64 [n_vox] each in the plan's masked order, and
+        the Gram matrix' eigenvalues f64 [n_vox, 125] (ascending, then NaN); NaN where a voxel is not eligible; any may be None, not all
+        (amx_prep_noise_mppca_device); enqueued on `stream`"""
+        self.ctx.check(lib().amx_prep_noise_mppca_device(self.ctx._h, self._h, c_vp(d_img), int(patch), c_vp(d_sigma or 0), c_vp(d_nsignal or 0),
+                                                         c_vp(d_mean or 0), c_vp(d_ratio or 0), c_vp(d_eig or 0), c_vp(stream or 0)))
+
     def sanitize(self, img, replace=None):
         """host image: -> number of NaN / Inf samples; with `replace` (a finite number) they are overwritten IN PLACE with float32(replace),
         np.nan_to_num(img, copy=False, nan=r, posinf=r, neginf=r) of core.py:156 (amx_prep_sanitize)"""
@@ -1148,6 +1159,22 @@ def prep_route(nS, n_out, n_b0, n_gidx, identity, direct, inplace):
                             _p(out, c_i64p)) != 0:
         raise ValueError('amx_prep_route: bad sizes')
     return {'route': PREP_ROUTES[int(out[0])], 'waves': int(out[1]), 'lds': int(out[2]), 'per_wave': int(out[3])}
+
+
+MPPCA_SIDES = ('volumes', 'patch')             # amx_mppca_route: out[3]
+
+
+def mppca_route(nS, patch, n_cols, dims):
+    """the Marchenko-Pastur kernel's launch for a patch of n_cols masked columns in a volume of extents dims, without a device
+    (amx_mppca_route; ValueError for a shape it refuses: patch not 3 or 5, nS > 512, an axis shorter than the patch)
+    -> {'r', 'q', 'side': one of MPPCA_SIDES (what the Gram matrix is over), 'gram': its order, 'chunk': samples per staged chunk,
+        'waves': wavefronts per patch, 'patches': per workgroup, 'lds': bytes per workgroup, 'eligible': 2 n_cols >= patch^3}"""
+    out = np.zeros(10, dtype=np.int64)
+    d = np.ascontiguousarray(dims, dtype=np.int64)
+    if d.shape != (3,) or lib().amx_mppca_route(int(nS), int(patch), int(n_cols), _p(d, c_i64p), _p(out, c_i64p)) != 0:
+        raise ValueError('amx_mppca_route: refused (patch 3 or 5, at most 512 volumes, no axis shorter than the patch)')
+    return {'r': int(out[1]), 'q': int(out[2]), 'side': MPPCA_SIDES[int(out[3])], 'gram': int(out[4]), 'chunk': int(out[5]),
+            'waves': int(out[6]), 'patches': int(out[7]), 'lds': int(out[8]), 'eligible': bool(out[9])}
 
 
 NODDI_BUILDS = ('none', 'small', 'f32_8', 'f64_12', 'f64_nw', 'f32_nw', 'global', 'gram', 'gram_left', 'qr', 'big_all')      # NoddiBuild (csrc/amx_noddi_route.hpp)

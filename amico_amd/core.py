@@ -7,7 +7,8 @@ in-memory volumes, every per-voxel step on the GPU:
              NaN / Inf scan of the raw image, replacement with replace_bad_voxels (core.py:152-158)    (amx_prep_sanitize);
              CONFIG['bad_samples_raw'] = samples found; the same for ``y`` after the gather (core.py:270-276) (amx_sanitize),
              CONFIG['bad_samples_preprocessed']
-             with doEstimateNoise: SNR and sigma from the spread of the b0 repeats (amx_prep_noise_b0, amx_nanmedian; not the reference's);
+             with doEstimateNoise: SNR and sigma from the spread of the b0 repeats (amx_prep_noise_b0, amx_nanmedian; not the reference's),
+             or with doEstimateNoise = 'MPPCA' a sigma per voxel from its local patch (amx_prep_noise_mppca);
              Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
@@ -71,7 +72,9 @@ class Evaluation:
         self.set_config('BLAS_nthreads', 1)
         self.set_config('doSaveTensorMaps', False)     # not a key of the reference: see fit()
         self.set_config('doEstimateNoise', False)      # not a key of the reference: see fit()
+        self.set_config('noise_patch', 5)              # edge of the patch of doEstimateNoise = 'MPPCA': 3 | 5
         self._estimate_noise = False                   # the key as set_data() read it
+        self._noise_patch = None                       # 'MPPCA': the patch edge as set_data() read it; None: the b0 repeats
         self._debias_estimated = False                 # doDebiasSignal without DWI-SNR: fit() fills the estimate in
 
     # `niiDWI_img` (core.py:136) is the raw float32 image.  When set_data kept the image in its stored dtype the float32 array is made
@@ -145,7 +148,10 @@ class Evaluation:
         scaling = _prep.check_scaling(scaling)
         self.set_config('replace_bad_voxels', replace_bad_voxels)               # core.py:134
         estimate = bool(self.get_config('doEstimateNoise'))
-        if estimate:
+        noise_patch = None
+        if _noise.is_mppca(self.get_config('doEstimateNoise')):
+            noise_patch = _noise.check_patch(self.get_config('noise_patch'))     # (ValueError; Marchenko-Pastur needs no b0 repeat)
+        elif estimate:
             _noise.check_b0_count(scheme.b0_count)                               # (RuntimeError naming the key, before anything is uploaded)
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
@@ -171,6 +177,8 @@ class Evaluation:
         self.set_config('b0_min_signal', b0_min_signal)
         if scheme.nS != img.shape[3]:
             raise ValueError('Scheme does not match with DWI data')
+        if noise_patch is not None:
+            _noise.check_patch_fits(img.shape[:3], noise_patch)                  # (RuntimeError naming the key, before anything is uploaded)
         self.niiMASK_img = np.ones(img.shape[:3], dtype=np.uint8) if mask is None \
             else np.asarray(mask, dtype=np.uint8)
         if self.niiMASK_img.shape != img.shape[:3]:
@@ -187,6 +195,7 @@ class Evaluation:
             b0_min_signal=b0_min_signal, debias_snr=debias_snr, replace_bad_voxels=replace_bad_voxels,
             scaling=scaling if self._raw is not None else None)
         self._estimate_noise = estimate
+        self._noise_patch = noise_patch
         self._debias_estimated = bool(self.get_config('doDebiasSignal')) and debias_snr is None      # (only with the key: see above)
         if self._debias_estimated:
             self._prep._plan.set_debias_mask(self.niiMASK_img)                   # the SNR comes in fit(); the mask is known now
@@ -288,7 +297,16 @@ class Evaluation:
             noise_sigma_estimated otherwise -- `y` is in image units then, which an SNR alone cannot be turned into.  Without the key
             every call, its order and every result and error are what they were.  The volume pipelines (pipeline.py), the host path
             SignalPreparation.gather and models.X().fit(evaluation) do not take it.
-        doSaveTensorMaps        (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
+            'MPPCA' (any letter case) selects a second estimator in the same place: a sigma per voxel by Marchenko-Pastur PCA of the voxel's
+            patch of edge noise_patch (3 | 5, default 5; anything else is a ValueError in set_data) over all volumes (amico_amd.noise,
+            DESIGN 7n).  It needs no b0 repeat -- set_data drops the 2-b0 minimum and instead raises RuntimeError when an axis of the
+            volume is shorter than the patch; doDebiasSignal still needs a b0 volume, by its own check.  noise_sigma_estimated is the median
+            of the sigma map and DWI-SNR_estimated the median of b0 mean / sigma over the eligible voxels (half of the patch inside the
+            mask, finite samples; no chi-square factor), CONFIG['noise_method'] = 'MPPCA', and RESULTS['NOISE_MAPs'] is float32
+            [X, Y, Z, 3] = b0 mean, sigma, number of signal components.  The estimates feed the debias and the robust fit by the rules
+            above; where one of them needs the SNR and there is none (no voxel with a positive b0 mean) fit() raises before the debias.
+            sigma is a few percent low on small patches.  Every other value of the key behaves as it always has.
+        doSaveTensorMaps       (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
             two kernels, the gather and then the tensor pass, for every method -- here that is the route of always; in the volume
@@ -359,18 +377,34 @@ class Evaluation:
         _prep.refuse_or_warn(self.get_config('bad_samples_raw'), bad_value, _prep.BAD_RAW)
         debias_snr = self._prep.debias_snr
         d_noise = None
+        self.CONFIG.pop('noise_method', None)                     # (set below by 'MPPCA' only: an earlier fit()'s does not linger)
         if self._estimate_noise:
             # doEstimateNoise: on the raw float32 image, before the debias changes it -- one k_noise_b0 launch, two medians, and one
             # small wait like the scan count's above.  An explicit DWI-SNR / DTI_sigma wins; the estimate is reported either way.
-            noise = _noise.estimate_device(plan, d_img.data_ptr())
+            # 'MPPCA': one k_mppca launch in the place of k_noise_b0 -- a sigma per voxel from its patch, all volumes, no b0 repeat needed
+            mppca = self._noise_patch is not None
+            noise = _noise.estimate_mppca_device(plan, d_img.data_ptr(), self._noise_patch) if mppca \
+                else _noise.estimate_device(plan, d_img.data_ptr())
             self.set_config('DWI-SNR_estimated', noise['snr'])
             self.set_config('noise_sigma_estimated', noise['sigma'])
             self.set_config('noise_voxels', noise['voxels'])
+            if mppca:
+                self.set_config('noise_method', _noise.MPPCA)
+            if noise['voxels'] == 0 and mppca:
+                raise RuntimeError(f'doEstimateNoise: no voxel of the mask has a patch to estimate the noise from (at least half of the '
+                                   f'{self._noise_patch}^3 voxels around it inside the mask and finite samples are needed)')
             if noise['voxels'] == 0:
                 raise RuntimeError('doEstimateNoise: no voxel of the mask has b0 repeats to estimate the noise from (finite samples, a '
                                    'positive mean and a spread are needed)')
             # b0 mean and sample standard deviation (ddof = 1), zero where the voxel was not eligible: scattered with the results below
-            d_noise = torch.nan_to_num(torch.stack((noise['mean'], noise['sd']), dim=1), nan=0.0).contiguous()
+            # ('MPPCA': b0 mean, sigma, signal components)
+            maps = (noise['mean'], noise['sd'], noise['signal']) if mppca else (noise['mean'], noise['sd'])
+            d_noise = torch.nan_to_num(torch.stack(maps, dim=1), nan=0.0).contiguous()
+            needs_snr = self._debias_estimated or (self.get_config('DTI_fit_method') in _dti.ROBUST_METHODS and dti_sigma is None
+                                                   and normalized)
+            if mppca and needs_snr and not np.isfinite(noise['snr']):
+                raise RuntimeError("doEstimateNoise: 'MPPCA' found a sigma but no DWI-SNR (no voxel with a positive b0 mean): set DWI-SNR "
+                                   '/ DTI_sigma')
             if self._debias_estimated:
                 debias_snr = noise['snr']
             if self.get_config('DTI_fit_method') in _dti.ROBUST_METHODS and dti_sigma is None:

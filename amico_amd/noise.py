@@ -10,6 +10,9 @@ With Gaussian noise of one SNR for the whole image (sigma_v = b0_v / SNR: the re
 sd^2 nu / sigma^2 is chi-square_nu, and the median commutes with monotone maps: both estimates are median-unbiased for every k >= 2.
 The magnitude image's noise is Rician; at b0 SNR >= 10 the Gaussian statement holds to better than 1 %.
 Both medians are exact and taken on the GPU (`amx_nanmedian_device`).  There is no CPU fallback.
+
+A second estimator needs no b0 repeat (doEstimateNoise = 'MPPCA'): `estimate_mppca_device` / `estimate_mppca` take a sigma per voxel
+from the Marchenko-Pastur edge of the eigenvalues of its local patch over all volumes (`amx_prep_noise_mppca_device`), and the same two medians.
 """
 import numpy as np
 from scipy import special
@@ -70,6 +73,86 @@ def estimate_device(plan, d_img, stream=None):
     _medians(plan.ctx, buf[2], buf[1], words, stream)
     snr, sigma, c = _finish(plan.n_b0, words.cpu().numpy())            # (the copy on the null stream waits for the kernels)
     return {'snr': snr, 'sigma': sigma, 'voxels': c, 'mean': buf[0], 'sd': buf[1]}
+
+
+MPPCA = 'MPPCA'               # the value of doEstimateNoise that selects the estimator below (any letter case)
+MPPCA_PATCHES = (3, 5)
+
+
+def is_mppca(value):
+    """doEstimateNoise names the Marchenko-Pastur estimator"""
+    return isinstance(value, str) and value.upper() == MPPCA
+
+
+def check_patch(patch):
+    """noise_patch: 3 or 5 (ValueError otherwise), as an int"""
+    if isinstance(patch, bool) or not isinstance(patch, (int, np.integer)) or int(patch) not in MPPCA_PATCHES:
+        raise ValueError('noise_patch (the edge of the Marchenko-Pastur patch) must be 3 or 5, got %r' % (patch,))
+    return int(patch)
+
+
+def check_patch_fits(shape3, patch):
+    """the sentence Evaluation.set_data raises for a volume the patch does not fit into"""
+    if min(int(d) for d in shape3) < patch:
+        raise RuntimeError(f"doEstimateNoise: 'MPPCA' with noise_patch {patch} needs a volume of at least {patch} voxels along every axis; "
+                           f'the image is {tuple(int(d) for d in shape3)}')
+
+
+def estimate_mppca_device(plan, d_img, patch=5, stream=None):
+    """The noise level per voxel by Marchenko-Pastur PCA of its patch of edge `patch` (include/amico_amd.h fixes the arithmetic).
+    plan: a `_capi.Prep`; d_img: device pointer (int) of the float32 image's element buffer in the plan's layout.
+    -> {'snr', 'sigma', 'voxels', 'mean', 'sd', 'signal'}: nanmedian(mean / sigma) (NaN without a b0 volume) and nanmedian(sigma) over the
+    eligible voxels (no chi-square factor: sigma is no sample standard deviation), their number, and per voxel the b0 mean, sigma (under
+    'sd', the key the b0 estimator's callers read) and the number of signal components as float64 device tensors [n_vox] in the plan's
+    masked order, NaN where not eligible.  One k_mppca launch, two medians, one small copy home.  On small patches sigma is a few percent
+    low (its finite-size property); the Rician caveat of the b0 estimator holds here as well."""
+    import torch
+    patch = check_patch(patch)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    buf = torch.empty((4, plan.n_vox), dtype=torch.float64, device=dev)          # sigma, signal components, mean, ratio
+    words = torch.empty(6, dtype=torch.float64, device=dev)
+    plan.noise_mppca_device(d_img, patch, buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), buf[3].data_ptr(), None, stream)
+    base = words.data_ptr()
+    _capi.nanmedian_device(plan.ctx, buf[3].data_ptr(), plan.n_vox, base, base + 32, stream)           # ratio: count in word 4
+    _capi.nanmedian_device(plan.ctx, buf[0].data_ptr(), plan.n_vox, base + 16, base + 40, stream)      # sigma: count in word 5
+    w = words.cpu().numpy()                                                      # (the copy on the null stream waits for the kernels)
+    c_ratio, c_sigma = (int(v) for v in w[4:6].view(np.int64))
+    with np.errstate(over='ignore'):
+        snr = float((w[0] + w[1]) / 2.0) if c_ratio else float('nan')
+        sigma = float((w[2] + w[3]) / 2.0) if c_sigma else float('nan')
+    return {'snr': snr, 'sigma': sigma, 'voxels': c_sigma, 'mean': buf[2], 'sd': buf[0], 'signal': buf[1]}
+
+
+def estimate_mppca(img, mask, b0_idx, patch=5, ctx=None):
+    """img float32 [X, Y, Z, nS] (numpy, C or Fortran order; anything else is copied to C-order float32), mask [X, Y, Z] (voxels == 1 are
+    taken; None: all), b0_idx: the b0 volumes (may be empty) -> the dict of `estimate_mppca_device` with 'mean' / 'sd' / 'signal' as float64
+    numpy [n_vox] in the mask's C order.  Uploads, one wait, numpy out."""
+    import torch
+    from .models import get_context
+    patch = check_patch(patch)
+    img = np.asarray(img)
+    if img.ndim != 4:
+        raise ValueError('img must be [X, Y, Z, nS]')
+    if img.dtype != np.float32 or not (img.flags.c_contiguous or img.flags.f_contiguous):
+        img = np.ascontiguousarray(img, dtype=np.float32)
+    sel = np.ones(img.shape[:3], dtype=bool) if mask is None else np.asarray(mask) == 1
+    if sel.shape != img.shape[:3]:
+        raise ValueError('mask geometry does not match the image')
+    check_patch_fits(img.shape[:3], patch)
+    rank = np.full(sel.shape, -1, dtype=np.int32)
+    rank[sel] = np.arange(int(sel.sum()), dtype=np.int32)
+    ctx = ctx if ctx is not None else get_context()
+    plan = _capi.Prep(ctx, img.shape, tuple(s // 4 for s in img.strides), rank, [[i] for i in range(img.shape[3])],
+                      np.asarray(b0_idx, dtype=np.int32).ravel())
+    try:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        d_img = torch.from_numpy(plan._img_buffer(img)).to(dev)
+        res = estimate_mppca_device(plan, d_img.data_ptr(), patch)
+        for k in ('mean', 'sd', 'signal'):
+            res[k] = res[k].cpu().numpy()
+    finally:
+        plan.close()
+    return res
 
 
 def estimate_from_rows(y, b0_idx, ctx=None):

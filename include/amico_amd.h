@@ -639,6 +639,37 @@ int amx_prep_noise_b0_device(amx_ctx *ctx, const amx_prep *p, const float *d_img
  * different streams.                                                                                                               */
 int amx_nanmedian_device(amx_ctx *ctx, const double *d_v, int64_t n, double *d_out, int64_t *d_count, void *hip_stream);
 
+/* (f0++) The noise level per voxel by Marchenko-Pastur PCA of its local patch (doEstimateNoise = 'MPPCA'; Veraart et al., NeuroImage 2016,
+ * with the degrees-of-freedom correction of Cordero-Grande et al. 2019; no counterpart in the reference).  It needs no b0 repeat and uses
+ * all nS volumes.  Input: the float32 image of a plan in the plan's layout; patch edge w in {3, 5}, h = (w-1)/2.
+ *   cube of a masked centre voxel c:  per axis a of length D_a the voxels s_a .. s_a + w - 1, s_a = clamp(c_a - h, 0, D_a - w) (at the
+ *            volume's border the cube shifts inward);
+ *   columns: the cube's voxels of plan rank >= 0 (mask == 1), n of them; rows: the m = nS volumes; values float32 widened to fp64; no mean
+ *            is removed;
+ *   eligible <=> 2 n >= w^3 and all m n samples finite and the rule below finds a p; otherwise every output of the voxel is NaN;
+ *   r = min(m, n), q = max(m, n);  G = X X^T (m <= n) or X^T X (m > n), r x r, accumulated in fp64 (the products of two float32 values
+ *            are exact in fp64, only the summation rounds);  eigenvalues ascending lambda_0 <= .. <= lambda_{r-1}, l_i = max(lambda_i, 0) / q;
+ *   rule:    for p = 0 .. r-1 with S_p = l_0 + .. + l_p:  gamma_p = (p+1) / (q - (r-p-1)),  s1 = S_p / (p+1),
+ *            s2 = (l_p - l_0) / (4 sqrt(gamma_p));  whenever s2 < s1: sigma^2 = s1, cut = p + 1 (the last such p wins);
+ *            sigma = sqrt(sigma^2), n_signal = r - cut;
+ *   mean   = the fp64 mean of the centre voxel's b0 samples with the arithmetic of amx_noise_b0_* above (sequential sum in b0_idx order,
+ *            one division); NaN without a b0 volume or with a mean <= 0;  ratio = mean / sigma.
+ * The eigenvalues come from a Householder tridiagonalisation and Sturm-count bisection (56 halvings of the Gershgorin interval); every
+ * threshold in them is a power-of-two fraction of the matrix' own Gershgorin bound, so the outputs of 2^k img are 2^k times those of
+ * img, bit for bit.  Over the image the caller takes sigma_est = nanmedian(sigma), SNR_est = nanmedian(ratio) (amx_nanmedian_device; no
+ * chi-square factor: sigma is no sample standard deviation).  On small patches the estimate is a few percent low.
+ * Outputs fp64 [n_vox] in the plan's masked order, d_eig fp64 [n_vox][125]: the r eigenvalues ascending, then NaN (it exists for the
+ * tests).  Every output is optional, at least one must be given, and they may not overlap.  patch not 3 or 5, nS > 512, an axis shorter
+ * than the patch, a plan without masked voxels: AMX_E_BADARG.  Enqueued on `hip_stream`; waits for nothing.                          */
+int amx_prep_noise_mppca_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, int patch, double *d_sigma, double *d_nsignal,
+                                double *d_mean, double *d_ratio, double *d_eig, void *hip_stream);
+/* The arithmetic of that kernel's launch without a device, for a patch of n_cols masked columns in a volume of extents dims:
+ * out = {1 (0 and AMX_E_BADARG: refused -- patch not 3 or 5, nS < 1 or > 512, an axis shorter than the patch, n_cols outside 0 .. w^3),
+ * r, q, side of the Gram matrix (0: the volumes, G = X X^T; 1: the patch, G = X^T X), its order, samples per staged chunk, wavefronts per
+ * patch, patches per workgroup, LDS bytes per workgroup, 2 n_cols >= w^3}.                                                           */
+#define AMX_MPPCA_ROUTE_WORDS 10
+int amx_mppca_route(int nS, int patch, int n_cols, const int64_t dims[3], int64_t out[AMX_MPPCA_ROUTE_WORDS]);
+
 /* (f0') NaN / Inf samples, load_data(..., replace_bad_voxels): core.py:152-158 on the raw image and core.py:270-276 on the
  * pre-processed one --
  *     if np.isnan(img).any() or np.isinf(img).any():
