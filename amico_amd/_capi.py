@@ -35,7 +35,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_debias_rows', 'amx_debias_rows_f32', 'amx_debias_rows_device', 'amx_debias_rows_device_f32',
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
            'amx_noise_b0_rows_device', 'amx_noise_b0_rows_device_f32', 'amx_prep_noise_b0_device', 'amx_nanmedian_device',
-           'amx_prep_noise_mppca_device', 'amx_mppca_route',
+           'amx_prep_noise_mppca_device', 'amx_mppca_route', 'amx_prep_noise_mppca_denoise_device', 'amx_mppca_denoise_route',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample', 'amx_lut_route',
@@ -234,6 +234,8 @@ def lib():
     L.amx_nanmedian_device.argtypes = [c_vp, c_vp, C.c_int64, c_vp, c_vp, c_vp]                      # ctx, v, n, out[2], count, stream
     L.amx_prep_noise_mppca_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]   # ctx, plan, img, patch, sigma, n_signal, mean, ratio, eig, stream
     L.amx_mppca_route.argtypes = [C.c_int, C.c_int, C.c_int, c_i64p, c_i64p]                         # nS, patch, n_cols, dims[3], out[10]
+    L.amx_prep_noise_mppca_denoise_device.argtypes = [c_vp, c_vp, c_vp, C.c_int] + [c_vp] * 8      # ctx, plan, img, patch, out, sigma, n_signal, mean, ratio, status, rows64, stream
+    L.amx_mppca_denoise_route.argtypes = [C.c_int, C.c_int, C.c_int, c_i64p, c_i64p]                 # nS, patch, n_cols, dims[3], out[11]
     L.amx_prep_sanitize.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
     L.amx_prep_sanitize_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp]
     L.amx_sanitize_device_f32.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_float, c_vp]
@@ -1058,6 +1060,17 @@ class Prep:
         self.ctx.check(lib().amx_prep_noise_mppca_device(self.ctx._h, self._h, c_vp(d_img), int(patch), c_vp(d_sigma or 0), c_vp(d_nsignal or 0),
                                                          c_vp(d_mean or 0), c_vp(d_ratio or 0), c_vp(d_eig or 0), c_vp(stream or 0)))
 
+    def noise_mppca_denoise_device(self, d_img, patch, d_out, d_sigma=None, d_nsignal=None, d_mean=None, d_ratio=None, d_status=None,
+                                   d_rows64=None, stream=None):
+        """device pointers (ints): the image's element buffer -> d_out, float32 in the image's layout and extent (no part of d_img): per
+        voxel of mask == 1 that is eligible the centre's column of its patch's best approximation of rank n_signal, every other sample
+        the image's; sigma, n_signal, mean, ratio as `noise_mppca_device` writes them; d_status int32 [n_vox] (0 denoised, 1 not eligible,
+        2 over a route's cap); d_rows64 f64 [n_vox, nS], the denoised rows before the float32 rounding, NaN where status != 0
+        (amx_prep_noise_mppca_denoise_device); enqueued on `stream`"""
+        self.ctx.check(lib().amx_prep_noise_mppca_denoise_device(self.ctx._h, self._h, c_vp(d_img), int(patch), c_vp(d_out or 0), c_vp(d_sigma or 0),
+                                                                 c_vp(d_nsignal or 0), c_vp(d_mean or 0), c_vp(d_ratio or 0), c_vp(d_status or 0),
+                                                                 c_vp(d_rows64 or 0), c_vp(stream or 0)))
+
     def sanitize(self, img, replace=None):
         """host image: -> number of NaN / Inf samples; with `replace` (a finite number) they are overwritten IN PLACE with float32(replace),
         np.nan_to_num(img, copy=False, nan=r, posinf=r, neginf=r) of core.py:156 (amx_prep_sanitize)"""
@@ -1175,6 +1188,19 @@ def mppca_route(nS, patch, n_cols, dims):
         raise ValueError('amx_mppca_route: refused (patch 3 or 5, at most 512 volumes, no axis shorter than the patch)')
     return {'r': int(out[1]), 'q': int(out[2]), 'side': MPPCA_SIDES[int(out[3])], 'gram': int(out[4]), 'chunk': int(out[5]),
             'waves': int(out[6]), 'patches': int(out[7]), 'lds': int(out[8]), 'eligible': bool(out[9])}
+
+
+def mppca_denoise_route(nS, patch, n_cols, dims):
+    """the Marchenko-Pastur denoising kernel's launch for a patch of n_cols masked columns, without a device (amx_mppca_denoise_route;
+    ValueError for what `mppca_route` refuses) -> {'r', 'q', 'side', 'waves', 'patches', 'per_patch': LDS bytes of a patch, 'lds': bytes per
+    workgroup, 'capacity': eigenvectors of length r the kernel holds, 'cap': the most min(n_signal, r - n_signal) may be (0: no cap),
+    'eligible'}"""
+    out = np.zeros(11, dtype=np.int64)
+    d = np.ascontiguousarray(dims, dtype=np.int64)
+    if d.shape != (3,) or lib().amx_mppca_denoise_route(int(nS), int(patch), int(n_cols), _p(d, c_i64p), _p(out, c_i64p)) != 0:
+        raise ValueError('amx_mppca_denoise_route: refused (patch 3 or 5, at most 512 volumes, no axis shorter than the patch)')
+    return {'r': int(out[1]), 'q': int(out[2]), 'side': MPPCA_SIDES[int(out[3])], 'waves': int(out[4]), 'patches': int(out[5]),
+            'per_patch': int(out[6]), 'lds': int(out[7]), 'capacity': int(out[8]), 'cap': int(out[9]), 'eligible': bool(out[10])}
 
 
 NODDI_BUILDS = ('none', 'small', 'f32_8', 'f64_12', 'f64_nw', 'f32_nw', 'global', 'gram', 'gram_left', 'qr', 'big_all')      # NoddiBuild (csrc/amx_noddi_route.hpp)

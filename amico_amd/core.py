@@ -9,6 +9,7 @@ in-memory volumes, every per-voxel step on the GPU:
              CONFIG['bad_samples_preprocessed']
              with doEstimateNoise: SNR and sigma from the spread of the b0 repeats (amx_prep_noise_b0, amx_nanmedian; not the reference's),
              or with doEstimateNoise = 'MPPCA' a sigma per voxel from its local patch (amx_prep_noise_mppca);
+             with doDenoise the image denoised by that patch PCA, which everything below then reads (amx_prep_noise_mppca_denoise);
              Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
@@ -75,6 +76,10 @@ class Evaluation:
         self.set_config('noise_patch', 5)              # edge of the patch of doEstimateNoise = 'MPPCA': 3 | 5
         self._estimate_noise = False                   # the key as set_data() read it
         self._noise_patch = None                       # 'MPPCA': the patch edge as set_data() read it; None: the b0 repeats
+        self.set_config('doDenoise', False)            # not a key of the reference: see fit()
+        self.set_config('doSaveDenoisedDWI', False)
+        self._denoise_patch = None                     # doDenoise: the patch edge as set_data() read it; None: no denoising
+        self._b0_estimate = False                      # doEstimateNoise asks for the b0 estimator (with doDenoise: it runs first)
         self._debias_estimated = False                 # doDebiasSignal without DWI-SNR: fit() fills the estimate in
 
     # `niiDWI_img` (core.py:136) is the raw float32 image.  When set_data kept the image in its stored dtype the float32 array is made
@@ -153,6 +158,11 @@ class Evaluation:
             noise_patch = _noise.check_patch(self.get_config('noise_patch'))     # (ValueError; Marchenko-Pastur needs no b0 repeat)
         elif estimate:
             _noise.check_b0_count(scheme.b0_count)                               # (RuntimeError naming the key, before anything is uploaded)
+        b0_estimate = estimate and noise_patch is None
+        denoise_patch = None
+        if _noise.is_denoise(self.get_config('doDenoise')):                      # (ValueError for anything but 'MPPCA' / True / False)
+            denoise_patch = _noise.check_patch(self.get_config('noise_patch'))
+            estimate = True                                                      # the denoising launch delivers an estimate as well
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
             debias_snr = self.get_config('DWI-SNR')
@@ -177,8 +187,9 @@ class Evaluation:
         self.set_config('b0_min_signal', b0_min_signal)
         if scheme.nS != img.shape[3]:
             raise ValueError('Scheme does not match with DWI data')
-        if noise_patch is not None:
-            _noise.check_patch_fits(img.shape[:3], noise_patch)                  # (RuntimeError naming the key, before anything is uploaded)
+        if noise_patch is not None or denoise_patch is not None:
+            # (RuntimeError naming the key, before anything is uploaded)
+            _noise.check_patch_fits(img.shape[:3], noise_patch if noise_patch is not None else denoise_patch)
         self.niiMASK_img = np.ones(img.shape[:3], dtype=np.uint8) if mask is None \
             else np.asarray(mask, dtype=np.uint8)
         if self.niiMASK_img.shape != img.shape[:3]:
@@ -196,6 +207,8 @@ class Evaluation:
             scaling=scaling if self._raw is not None else None)
         self._estimate_noise = estimate
         self._noise_patch = noise_patch
+        self._denoise_patch = denoise_patch
+        self._b0_estimate = b0_estimate
         self._debias_estimated = bool(self.get_config('doDebiasSignal')) and debias_snr is None      # (only with the key: see above)
         if self._debias_estimated:
             self._prep._plan.set_debias_mask(self.niiMASK_img)                   # the SNR comes in fit(); the mask is known now
@@ -306,6 +319,18 @@ class Evaluation:
             [X, Y, Z, 3] = b0 mean, sigma, number of signal components.  The estimates feed the debias and the robust fit by the rules
             above; where one of them needs the SNR and there is none (no voxel with a positive b0 mean) fit() raises before the debias.
             sigma is a few percent low on small patches.  Every other value of the key behaves as it always has.
+        doDenoise               (default False; 'MPPCA' in any letter case or True; anything else is a ValueError in set_data) the image
+            denoised by that Marchenko-Pastur PCA (amico_amd.noise.denoise_mppca_device): one k_mppca_denoise launch where the
+            estimators run -- after the ingest / scan kernel, before the debias -- gives every voxel of the mask that has a patch the
+            centre column of its patch's best approximation of rank n_signal; a voxel without one is passed through.  Debias, mean_b0,
+            gather, directions, fit, corrected and predicted DWI all read the denoised image; `niiDWI_img` keeps the RAW one.  noise_patch
+            is the estimator's key (an axis shorter than it: the same RuntimeError in set_data).  The launch delivers the 'MPPCA' estimate
+            too, bit for bit: with doEstimateNoise unset or 'MPPCA' the CONFIG keys and RESULTS['NOISE_MAPs'] above are set and feed the
+            debias and the robust fit by the rules above, with no second launch; with doEstimateNoise = True the b0 estimator runs on the
+            raw image first.  It leaves CONFIG['denoise_voxels'] / ['denoise_passed_through'], and with doSaveDenoisedDWI
+            RESULTS['DWI_denoised'] float32 [X, Y, Z, nS] in image units (before the debias).  No voxel with a patch at all is the
+            RuntimeError of 'MPPCA'.  The volume pipelines (pipeline.py), SignalPreparation.gather and models.X().fit(evaluation) do not
+            take it.
         doSaveTensorMaps       (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
@@ -378,13 +403,22 @@ class Evaluation:
         debias_snr = self._prep.debias_snr
         d_noise = None
         self.CONFIG.pop('noise_method', None)                     # (set below by 'MPPCA' only: an earlier fit()'s does not linger)
+        self.CONFIG.pop('denoise_voxels', None)                   # (doDenoise only)
+        self.CONFIG.pop('denoise_passed_through', None)
+        den = None
+        # doDenoise with doEstimateNoise = True: the b0 estimator below on the raw image as always, the denoising launch after it
+        b0_estimate = self._b0_estimate
         if self._estimate_noise:
             # doEstimateNoise: on the raw float32 image, before the debias changes it -- one k_noise_b0 launch, two medians, and one
             # small wait like the scan count's above.  An explicit DWI-SNR / DTI_sigma wins; the estimate is reported either way.
             # 'MPPCA': one k_mppca launch in the place of k_noise_b0 -- a sigma per voxel from its patch, all volumes, no b0 repeat needed
-            mppca = self._noise_patch is not None
-            noise = _noise.estimate_mppca_device(plan, d_img.data_ptr(), self._noise_patch) if mppca \
-                else _noise.estimate_device(plan, d_img.data_ptr())
+            # doDenoise: one k_mppca_denoise launch in that place delivers the same estimate, bit for bit, and the denoised image
+            mppca = self._noise_patch is not None or (self._denoise_patch is not None and not b0_estimate)
+            if self._denoise_patch is not None and not b0_estimate:
+                noise = den = _noise.denoise_mppca_device(plan, d_img.data_ptr(), self._denoise_patch)
+            else:
+                noise = _noise.estimate_mppca_device(plan, d_img.data_ptr(), self._noise_patch) if mppca \
+                    else _noise.estimate_device(plan, d_img.data_ptr())
             self.set_config('DWI-SNR_estimated', noise['snr'])
             self.set_config('noise_sigma_estimated', noise['sigma'])
             self.set_config('noise_voxels', noise['voxels'])
@@ -392,7 +426,7 @@ class Evaluation:
                 self.set_config('noise_method', _noise.MPPCA)
             if noise['voxels'] == 0 and mppca:
                 raise RuntimeError(f'doEstimateNoise: no voxel of the mask has a patch to estimate the noise from (at least half of the '
-                                   f'{self._noise_patch}^3 voxels around it inside the mask and finite samples are needed)')
+                                   f'{self._noise_patch or self._denoise_patch}^3 voxels around it inside the mask and finite samples are needed)')
             if noise['voxels'] == 0:
                 raise RuntimeError('doEstimateNoise: no voxel of the mask has b0 repeats to estimate the noise from (finite samples, a '
                                    'positive mean and a spread are needed)')
@@ -412,6 +446,21 @@ class Evaluation:
                 # and the estimate has the unit an SNR lacks
                 dti_sigma = _dti.resolve_sigma(self.get_config('DTI_fit_method'), None, noise['snr'], True) if normalized \
                     else _capi.check_sigma(noise['sigma'])
+        d_denoised = None
+        if self._denoise_patch is not None:
+            # doDenoise: every eligible voxel of the mask becomes the centre column of its patch's best approximation of rank n_signal;
+            # everything below -- debias, mean_b0, gather, directions, fit, corrected and predicted DWI -- reads the denoised image
+            if den is None:
+                den = _noise.denoise_mppca_device(plan, d_img.data_ptr(), self._denoise_patch)
+            if den['denoised'] == 0:
+                raise RuntimeError(f'doEstimateNoise: no voxel of the mask has a patch to estimate the noise from (at least half of the '
+                                   f'{self._denoise_patch}^3 voxels around it inside the mask and finite samples are needed)')
+            self.set_config('denoise_voxels', den['denoised'])
+            self.set_config('denoise_passed_through', den['passed_through'])
+            d_img = den['image']
+            if self.get_config('doSaveDenoisedDWI'):
+                d_denoised = d_img.clone() if debias_snr is not None else d_img      # (the debias works in place)
+            den = None
         if debias_snr is not None:
             # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
             self._prep._plan.debias_device(d_img.data_ptr(), debias_snr)
@@ -508,6 +557,11 @@ class Evaluation:
         if d_noise is not None:
             out['NOISE_MAPs'] = d_noise
             self.RESULTS['NOISE_MAPs'] = sc('NOISE_MAPs', None)
+        if d_denoised is not None:
+            # image units, the shape and memory order of the image given to set_data
+            self.RESULTS['DWI_denoised'] = np.lib.stride_tricks.as_strided(d_denoised.cpu().numpy(), shape=plan.shape,
+                                                                           strides=tuple(4 * st for st in plan.strides))
+            d_denoised = None
         if self.get_config('doComputeRMSE'):
             self.RESULTS['RMSE'] = sc('rmse', results['rmse'])
         if self.get_config('doComputeNRMSE'):

@@ -55,4 +55,34 @@ inline MppcaRoute mppca_route(int nS, int w, int n, long long d0, long long d1, 
     return rt;
 }
 
+// k_mppca_denoise: k_mppca's team shapes and LDS, and one more [rp] vector (the reflectors' tau2).  The eigenvectors live in what the
+// tridiagonalisation leaves dead of G (its lower triangle with the diagonal): (r - 1) / 2 + 1 vectors of r words, and the smaller of the
+// signal and the noise set never has more than r / 2 -- so no route has a cap.
+struct MppcaDenoiseRoute {
+    int ok;             // 0: refused (what mppca_route refuses)
+    int r, q, side;     // as MppcaRoute
+    int waves, patches; // as MppcaRoute
+    int eligible;       // 2 n >= w^3
+    int capacity;       // eigenvectors of length r the dead triangle of G holds
+    int cap;            // the most min(n_signal, r - n_signal) may be; 0: no cap (a voxel above a cap would be passed through, status 2)
+    size_t per_patch;   // LDS bytes of one patch's team
+    size_t lds;         // LDS bytes per workgroup
+};
+
+inline MppcaDenoiseRoute mppca_denoise_route(int nS, int w, int n, long long d0, long long d1, long long d2)
+{
+    MppcaDenoiseRoute rt = {};
+    const MppcaRoute base = mppca_route(nS, w, n, d0, d1, d2);
+    if (!base.ok) return rt;
+    const int w3 = w * w * w, rmax = nS < w3 ? nS : w3, rp = (rmax + 15) / 16 * 16;
+    rt.ok = 1;
+    rt.r = base.r; rt.q = base.q; rt.side = base.side; rt.waves = base.waves; rt.patches = base.patches; rt.eligible = base.eligible;
+    rt.capacity = rt.r > 0 ? (rt.r - 1) / 2 + 1 : 0;
+    rt.cap = 0;
+    rt.per_patch = base.per_patch + (size_t)rp * 8;
+    rt.lds = rt.per_patch * rt.patches;
+    if (rt.lds > kMppcaLdsMax) rt.ok = 0;
+    return rt;
+}
+
 }  // namespace amx

@@ -13,6 +13,8 @@ Both medians are exact and taken on the GPU (`amx_nanmedian_device`).  There is 
 
 A second estimator needs no b0 repeat (doEstimateNoise = 'MPPCA'): `estimate_mppca_device` / `estimate_mppca` take a sigma per voxel
 from the Marchenko-Pastur edge of the eigenvalues of its local patch over all volumes (`amx_prep_noise_mppca_device`), and the same two medians.
+`denoise_mppca_device` / `denoise_mppca` go on from there to the denoised image (`Evaluation`'s key doDenoise): every eligible
+voxel becomes the centre column of its patch's best approximation of rank n_signal (`amx_prep_noise_mppca_denoise_device`).
 """
 import numpy as np
 from scipy import special
@@ -110,8 +112,15 @@ def estimate_mppca_device(plan, d_img, patch=5, stream=None):
     patch = check_patch(patch)
     dev = torch.device('cuda', torch.cuda.current_device())
     buf = torch.empty((4, plan.n_vox), dtype=torch.float64, device=dev)          # sigma, signal components, mean, ratio
-    words = torch.empty(6, dtype=torch.float64, device=dev)
     plan.noise_mppca_device(d_img, patch, buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), buf[3].data_ptr(), None, stream)
+    return _mppca_result(plan, buf, stream)
+
+
+def _mppca_result(plan, buf, stream=None):
+    """buf f64 [4, n_vox] as a Marchenko-Pastur launch left it (sigma, signal components, mean, ratio) -> the dict of
+    `estimate_mppca_device`: two medians, one small copy home"""
+    import torch
+    words = torch.empty(6, dtype=torch.float64, device=buf.device)
     base = words.data_ptr()
     _capi.nanmedian_device(plan.ctx, buf[3].data_ptr(), plan.n_vox, base, base + 32, stream)           # ratio: count in word 4
     _capi.nanmedian_device(plan.ctx, buf[0].data_ptr(), plan.n_vox, base + 16, base + 40, stream)      # sigma: count in word 5
@@ -150,6 +159,72 @@ def estimate_mppca(img, mask, b0_idx, patch=5, ctx=None):
         res = estimate_mppca_device(plan, d_img.data_ptr(), patch)
         for k in ('mean', 'sd', 'signal'):
             res[k] = res[k].cpu().numpy()
+    finally:
+        plan.close()
+    return res
+
+
+DENOISE_STATUS = ('denoised', 'not eligible', 'over the cap')      # d_status of amx_prep_noise_mppca_denoise_device
+
+
+def is_denoise(value):
+    """doDenoise: 'MPPCA' in any letter case or True -> True; False / None -> False; anything else is a ValueError"""
+    if value is None or value is False:
+        return False
+    if value is True or is_mppca(value):
+        return True
+    raise ValueError("doDenoise must be 'MPPCA', True or False, got %r" % (value,))
+
+
+def denoise_mppca_device(plan, d_img, patch=5, stream=None):
+    """The image denoised by Marchenko-Pastur PCA of local patches (include/amico_amd.h fixes the arithmetic): every eligible
+    voxel of the mask gets the centre column of its patch's best approximation of rank n_signal; every other sample is the image's.
+    plan: a `_capi.Prep`; d_img: device pointer (int) of the float32 image's element buffer in the plan's layout (left as it is).
+    -> the dict of `estimate_mppca_device` -- the same bits: the launch delivers the estimate as well -- and 'image': a float32 device
+    tensor of plan.extent elements in the image's layout; 'status': int32 device tensor [n_vox] (the index into DENOISE_STATUS);
+    'denoised' / 'passed_through': the number of voxels with status 0 / any other.  One k_mppca_denoise launch behind a device copy,
+    two medians, two small copies home."""
+    import torch
+    patch = check_patch(patch)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    buf = torch.empty((4, plan.n_vox), dtype=torch.float64, device=dev)
+    out = torch.empty(plan.extent, dtype=torch.float32, device=dev)
+    status = torch.empty(plan.n_vox, dtype=torch.int32, device=dev)
+    plan.noise_mppca_denoise_device(d_img, patch, out.data_ptr(), buf[0].data_ptr(), buf[1].data_ptr(), buf[2].data_ptr(), buf[3].data_ptr(),
+                                    status.data_ptr(), None, stream)
+    res = _mppca_result(plan, buf, stream)
+    done = int((status == 0).sum().item())
+    res.update(image=out, status=status, denoised=done, passed_through=plan.n_vox - done)
+    return res
+
+
+def denoise_mppca(img, mask, b0_idx, patch=5, ctx=None):
+    """img, mask, b0_idx as `estimate_mppca` takes them -> its dict and 'image': float32 numpy of img's shape and memory order, 'status':
+    int32 numpy [n_vox] in the mask's C order, 'denoised', 'passed_through'.  Uploads, one wait, numpy out."""
+    import torch
+    from .models import get_context
+    patch = check_patch(patch)
+    img = np.asarray(img)
+    if img.ndim != 4:
+        raise ValueError('img must be [X, Y, Z, nS]')
+    if img.dtype != np.float32 or not (img.flags.c_contiguous or img.flags.f_contiguous):
+        img = np.ascontiguousarray(img, dtype=np.float32)
+    sel = np.ones(img.shape[:3], dtype=bool) if mask is None else np.asarray(mask) == 1
+    if sel.shape != img.shape[:3]:
+        raise ValueError('mask geometry does not match the image')
+    check_patch_fits(img.shape[:3], patch)
+    rank = np.full(sel.shape, -1, dtype=np.int32)
+    rank[sel] = np.arange(int(sel.sum()), dtype=np.int32)
+    ctx = ctx if ctx is not None else get_context()
+    plan = _capi.Prep(ctx, img.shape, tuple(s // 4 for s in img.strides), rank, [[i] for i in range(img.shape[3])],
+                      np.asarray(b0_idx, dtype=np.int32).ravel())
+    try:
+        dev = torch.device('cuda', torch.cuda.current_device())
+        d_img = torch.from_numpy(plan._img_buffer(img)).to(dev)
+        res = denoise_mppca_device(plan, d_img.data_ptr(), patch)
+        for k in ('mean', 'sd', 'signal', 'status'):
+            res[k] = res[k].cpu().numpy()
+        res['image'] = np.lib.stride_tricks.as_strided(res['image'].cpu().numpy(), shape=img.shape, strides=img.strides)
     finally:
         plan.close()
     return res

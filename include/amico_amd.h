@@ -670,6 +670,35 @@ int amx_prep_noise_mppca_device(amx_ctx *ctx, const amx_prep *p, const float *d_
 #define AMX_MPPCA_ROUTE_WORDS 10
 int amx_mppca_route(int nS, int patch, int n_cols, const int64_t dims[3], int64_t out[AMX_MPPCA_ROUTE_WORDS]);
 
+/* (f0+++) The image denoised by that Marchenko-Pastur PCA (doDenoise = 'MPPCA'; Veraart et al. 2016: the patch's best approximation of
+ * rank n_signal, written back to its centre voxel; no overlapping-patch averaging; no counterpart in the reference).  Everything up to
+ * and including the rule is (f0++)'s, with the same X (m volumes x n masked columns), r, q, side, ascending lambda and cut;
+ * s = n_signal = r - cut.  c = the index of the voxel itself among its cube's masked columns (the cube is clamped at the volume's border:
+ * "centre" means the voxel the patch belongs to).  The denoised samples of the voxel are column c of the best rank-s approximation of X:
+ *   volumes side (G = X X^T):  x^ = P_s x_c,      P_s = the projector onto the eigenvectors of the s largest eigenvalues of G;
+ *   patch side   (G = X^T X):  x^ = X (P_s e_c),  the patch read once more from the image for the product;
+ *   s = 0:                     x^ = 0 (the rank-0 reconstruction).
+ * With G = Q T Q^T (Q: the Householder reflectors of the tridiagonalisation, kept where G's rows held them) and b = x_c | e_c:
+ * b' = Q^T b; for the smaller of the two sets of eigenvalues (the s largest, or the cut smallest) the eigenvectors of T from the bisected
+ * eigenvalues by the twisted factorisation (forward pivots d+, backward pivots d-, gamma_i = d+_i + d-_i - (T_ii - lambda), the twist at
+ * the smallest |gamma_i|, z from the two recurrences; the pivots kept 2^-104 of the Gershgorin bound away from zero as the Sturm count's
+ * are), made orthonormal by Gram-Schmidt, every vector twice against those before it; z' = sum_j u_j (u_j^T b') for the signal set,
+ * b' - sum_j u_j (u_j^T b') for the noise set; z = Q z'; x^ = z (volumes side) or X z (patch side), all in fp64.  No absolute constant
+ * enters: the outputs of 2^k img are 2^k times those of img, bit for bit.
+ * d_out float32, the plan's image layout and extent, required, and no part of d_img (the patches overlap): (float)x^ for a denoised voxel;
+ * every other sample -- outside the mask, a voxel that is not eligible -- is copied from d_img by a device copy ahead of the kernel on the
+ * same stream.  d_sigma / d_nsignal / d_mean / d_ratio: those of amx_prep_noise_mppca_device, bit for bit.  d_status int32 [n_vox]:
+ * 0 denoised, 1 not eligible (passed through), 2 over a route's cap (passed through; no route has a cap today: amx_mppca_denoise_route).
+ * d_rows64 fp64 [n_vox][nS]: x^ before the float32 rounding, NaN where status != 0 (it exists for the tests).  All but d_out are optional;
+ * no two buffers may overlap.  The refusals are amx_prep_noise_mppca_device's.  Enqueued on `hip_stream`; waits for nothing.         */
+int amx_prep_noise_mppca_denoise_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, int patch, float *d_out, double *d_sigma,
+                                        double *d_nsignal, double *d_mean, double *d_ratio, int *d_status, double *d_rows64, void *hip_stream);
+/* That kernel's launch without a device: out = {1 (0 and AMX_E_BADARG: what amx_mppca_route refuses), r, q, side, wavefronts per patch,
+ * patches per workgroup, LDS bytes per patch, LDS bytes per workgroup, eigenvectors of length r the kernel can hold (never fewer than
+ * r / 2, the most the smaller set has), the cap on min(s, cut) (0: none), 2 n_cols >= w^3}.                                          */
+#define AMX_MPPCA_DENOISE_ROUTE_WORDS 11
+int amx_mppca_denoise_route(int nS, int patch, int n_cols, const int64_t dims[3], int64_t out[AMX_MPPCA_DENOISE_ROUTE_WORDS]);
+
 /* (f0') NaN / Inf samples, load_data(..., replace_bad_voxels): core.py:152-158 on the raw image and core.py:270-276 on the
  * pre-processed one --
  *     if np.isnan(img).any() or np.isinf(img).any():

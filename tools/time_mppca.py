@@ -8,6 +8,9 @@ slowest: nibabel's Fortran order), one process per leg, median of 7, device even
   split               w = 5 at 125, 250 and 500 volumes on 60 000 voxels: r = 125 in all three, so the eigenvalue stage costs the same and the
                       staging + Gram stage grows with q = the volumes -- the line through the three times gives the two parts
 
+  den_v99_w3 .. den_v306_w5   the denoiser on the four images above: k_mppca alone and k_mppca_denoise behind its device copy
+                      of the image, in the same process, and the whole of noise.denoise_mppca_device
+
 Per leg: k_mppca, the b0 estimator's k_noise_b0 on the same image, and the whole estimate as Evaluation.fit() runs it (one launch, two
 medians, the small copy home).  Every line starts with the library's amx_build_id.
 
@@ -22,7 +25,7 @@ import time
 import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
-LEGS = ('v99_w3', 'v99_w5', 'v306_w3', 'v306_w5', 'split')
+LEGS = ('v99_w3', 'v99_w5', 'v306_w3', 'v306_w5', 'split', 'den_v99_w3', 'den_v99_w5', 'den_v306_w3', 'den_v306_w5')
 SHAPE, N_B0 = (100, 100, 60), 9
 SHELLS = {99: ((700.0, 30), (2000.0, 60)), 306: ((700.0, 99), (2000.0, 198)), 125: ((1000.0, 116),), 250: ((1000.0, 241),), 500: ((1000.0, 491),)}
 
@@ -81,6 +84,8 @@ def leg(name, reps):
               f'{1e3 * slope:.2f} ns per voxel and volume (staging and Gram matrix): at q = 125 the second part is {100 * slope * 125 / (icpt + slope * 125):.0f} % '
               f'of the time, at q = 306 {100 * slope * 306 / (icpt + slope * 306):.0f} %')
         return
+    if name.startswith('den_'):
+        return denoise_leg(name, reps)
     nS, w = int(name[1:name.index('_')]), int(name[-1])
     ctx, plan, d_img = setup(nS, 50)
     n = plan.n_vox
@@ -110,6 +115,39 @@ def leg(name, reps):
         ctx.sync()
         tb0.append((time.perf_counter() - t0) * 1e3)
     print(f'{head} the b0 estimator\'s whole estimate: median {np.median(tb0[2:]):.3f} ms; sigma {est0["sigma"]:.3f}, SNR {est0["snr"]:.3f}')
+
+
+def denoise_leg(name, reps):
+    import torch
+    from amico_amd import _capi, noise
+    tag = _capi.build_id()
+    nS, w = int(name[5:name.rindex('_')]), int(name[-1])
+    ctx, plan, d_img = setup(nS, 50)
+    n = plan.n_vox
+    rt = _capi.mppca_denoise_route(nS, w, w ** 3, SHAPE)
+    head = f'{tag} | {name}: {n} masked voxels of {int(np.prod(SHAPE))}, {nS} volumes, w {w}, r {rt["r"]}, q {rt["q"]}, Gram over the {rt["side"]} |'
+    out = torch.empty((4, n), dtype=torch.float64, device='cuda')
+    image = torch.empty(plan.extent, dtype=torch.float32, device='cuda')
+    status = torch.empty(n, dtype=torch.int32, device='cuda')
+    t, lo, hi = events(lambda: plan.noise_mppca_device(d_img.data_ptr(), w, *[out[i].data_ptr() for i in range(4)]), reps)
+    print(f'{head} k_mppca<{w}> alone: median {t:.2f} ms (min {lo:.2f}, max {hi:.2f}), {1e3 * t / n:.3f} us per voxel')
+    td, lo, hi = events(lambda: plan.noise_mppca_denoise_device(d_img.data_ptr(), w, image.data_ptr(), *[out[i].data_ptr() for i in range(4)],
+                                                                status.data_ptr()), reps)
+    signal = out[1][~torch.isnan(out[1])]
+    print(f'{head} the image copy + k_mppca_denoise<{w}> [{rt["lds"]} B LDS, {rt["capacity"]} vectors, cap {rt["cap"]}]: median {td:.2f} ms (min {lo:.2f}, '
+          f'max {hi:.2f}), {1e3 * td / n:.3f} us per voxel; over k_mppca {td / t:.3f}; n_signal {int(signal.min())}..{int(signal.max())}, '
+          f'{int((status == 0).sum())} voxels denoised')
+    tc, lo, hi = events(lambda: image.copy_(d_img), reps)
+    print(f'{head} the copy of the image alone ({4 * plan.extent / 1e6:.0f} MB): median {tc:.2f} ms')
+    s = []
+    for _ in range(reps + 2):
+        ctx.sync()
+        t0 = time.perf_counter()
+        den = noise.denoise_mppca_device(plan, d_img.data_ptr(), w)
+        ctx.sync()
+        s.append((time.perf_counter() - t0) * 1e3)
+    print(f'{head} the whole of denoise_mppca_device (host clock: buffers, copy, launch, two medians, the copies home): median {np.median(s[2:]):.2f} ms; '
+          f'sigma {den["sigma"]:.3f} (made at 45), {den["denoised"]} denoised, {den["passed_through"]} passed through')
 
 
 def main():
