@@ -36,6 +36,7 @@ SYMBOLS = ['amx_version', 'amx_build_id', 'amx_device_count', 'amx_set_call_voxe
            'amx_prep_set_debias_mask', 'amx_prep_debias', 'amx_prep_debias_device', 'amx_debias_last_unconverged',
            'amx_noise_b0_rows_device', 'amx_noise_b0_rows_device_f32', 'amx_prep_noise_b0_device', 'amx_nanmedian_device',
            'amx_prep_noise_mppca_device', 'amx_mppca_route', 'amx_prep_noise_mppca_denoise_device', 'amx_mppca_denoise_route',
+           'amx_prep_unring_device', 'amx_unring_route',
            'amx_prep_sanitize', 'amx_prep_sanitize_device', 'amx_sanitize_device_f32', 'amx_sanitize_device', 'amx_sanitize', 'amx_sanitize_last', 'amx_sanitize_previous',
            'amx_prep_ingest', 'amx_prep_ingest_device',
            'amx_lut_resample', 'amx_lut_rotate_resample', 'amx_lut_route',
@@ -236,6 +237,8 @@ def lib():
     L.amx_mppca_route.argtypes = [C.c_int, C.c_int, C.c_int, c_i64p, c_i64p]                         # nS, patch, n_cols, dims[3], out[10]
     L.amx_prep_noise_mppca_denoise_device.argtypes = [c_vp, c_vp, c_vp, C.c_int] + [c_vp] * 8      # ctx, plan, img, patch, out, sigma, n_signal, mean, ratio, status, rows64, stream
     L.amx_mppca_denoise_route.argtypes = [C.c_int, C.c_int, C.c_int, c_i64p, c_i64p]                 # nS, patch, n_cols, dims[3], out[11]
+    L.amx_prep_unring_device.argtypes = [c_vp, c_vp, c_vp, c_vp, C.c_int, C.c_int, c_i64p, c_i64p, c_vp]   # ctx, plan, img, out, axis_a, axis_b, slices, passed_through, stream
+    L.amx_unring_route.argtypes = [C.c_int, C.c_int, c_i64p]                                         # n_a, n_b, out[14]
     L.amx_prep_sanitize.argtypes = [c_vp, c_vp, c_fp, C.c_int, C.c_float, C.POINTER(C.c_int64)]
     L.amx_prep_sanitize_device.argtypes = [c_vp, c_vp, c_vp, C.c_int, C.c_float, c_vp]
     L.amx_sanitize_device_f32.argtypes = [c_vp, c_vp, C.c_int64, C.c_int, C.c_float, c_vp]
@@ -1060,6 +1063,16 @@ class Prep:
         self.ctx.check(lib().amx_prep_noise_mppca_device(self.ctx._h, self._h, c_vp(d_img), int(patch), c_vp(d_sigma or 0), c_vp(d_nsignal or 0),
                                                          c_vp(d_mean or 0), c_vp(d_ratio or 0), c_vp(d_eig or 0), c_vp(stream or 0)))
 
+    def unring_device(self, d_img, d_out, axes=(0, 1), stream=None):
+        """device pointers (ints): the image's element buffer -> d_out, float32 in the image's layout and extent (no part of d_img): every
+        slice along `axes` (two different axes out of 0, 1, 2 of the plan's shape, each extent 8 .. 256) with its Gibbs ringing removed by
+        local sub-voxel shifts; a slice with a NaN / Inf sample is copied through (amx_prep_unring_device).  Enqueued on `stream`; waits
+        for the last chunk -> (slices, passed_through)"""
+        out = np.zeros(2, dtype=np.int64)
+        self.ctx.check(lib().amx_prep_unring_device(self.ctx._h, self._h, c_vp(d_img), c_vp(d_out), int(axes[0]), int(axes[1]),
+                                                    _p(out[0:1], c_i64p), _p(out[1:2], c_i64p), c_vp(stream or 0)))
+        return int(out[0]), int(out[1])
+
     def noise_mppca_denoise_device(self, d_img, patch, d_out, d_sigma=None, d_nsignal=None, d_mean=None, d_ratio=None, d_status=None,
                                    d_rows64=None, stream=None):
         """device pointers (ints): the image's element buffer -> d_out, float32 in the image's layout and extent (no part of d_img): per
@@ -1188,6 +1201,19 @@ def mppca_route(nS, patch, n_cols, dims):
         raise ValueError('amx_mppca_route: refused (patch 3 or 5, at most 512 volumes, no axis shorter than the patch)')
     return {'r': int(out[1]), 'q': int(out[2]), 'side': MPPCA_SIDES[int(out[3])], 'gram': int(out[4]), 'chunk': int(out[5]),
             'waves': int(out[6]), 'patches': int(out[7]), 'lds': int(out[8]), 'eligible': bool(out[9])}
+
+
+def unring_route(n_a, n_b):
+    """what the unringing kernels ask for a slice of n_a x n_b pixels, without a device (amx_unring_route; ValueError for an extent outside
+    8 .. 256) -> {'tile': (rows, lines, depth) of the MFMA tile, 'pad': the extents rounded up to it, 'groups': workgroups per slice for
+    the lines along a / along b, 'lds_dft', 'lds_shift': LDS bytes per workgroup, 'table_bytes', 'slice_bytes', 'chunk': slices per
+    chunk, 'cap': the scratch cap in bytes}"""
+    out = np.zeros(14, dtype=np.int64)
+    if lib().amx_unring_route(int(n_a), int(n_b), _p(out, c_i64p)) != 0:
+        raise ValueError('amx_unring_route: refused (each in-plane extent must be 8 to 256 pixels)')
+    return {'tile': (int(out[1]), int(out[2]), int(out[3])), 'pad': (int(out[4]), int(out[5])), 'groups': (int(out[6]), int(out[7])),
+            'lds_dft': int(out[8]), 'lds_shift': int(out[9]), 'table_bytes': int(out[10]), 'slice_bytes': int(out[11]),
+            'chunk': int(out[12]), 'cap': int(out[13])}
 
 
 def mppca_denoise_route(nS, patch, n_cols, dims):

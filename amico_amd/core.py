@@ -10,6 +10,7 @@ in-memory volumes, every per-voxel step on the GPU:
              with doEstimateNoise: SNR and sigma from the spread of the b0 repeats (amx_prep_noise_b0, amx_nanmedian; not the reference's),
              or with doEstimateNoise = 'MPPCA' a sigma per voxel from its local patch (amx_prep_noise_mppca);
              with doDenoise the image denoised by that patch PCA, which everything below then reads (amx_prep_noise_mppca_denoise);
+             with doUnring the Gibbs ringing of every slice removed by local sub-voxel shifts, behind the denoising (amx_prep_unring);
              Rician debias of the image when doDebiasSignal is set (core.py:201-206) (amx_prep_debias);
              CONFIG['debias_unconverged'] = samples that reached the root search's trip cap
              b0 normalisation / b0 merge / shell average + mask gather + clip  -> ``y``      (amx_prep_gather)
@@ -31,6 +32,7 @@ from . import prep as _prep
 from . import dti as _dti
 from . import bootstrap as _bootstrap
 from . import noise as _noise
+from . import unring as _unring
 from .synthetic import SimpleScheme
 
 
@@ -78,6 +80,10 @@ class Evaluation:
         self._noise_patch = None                       # 'MPPCA': the patch edge as set_data() read it; None: the b0 repeats
         self.set_config('doDenoise', False)            # not a key of the reference: see fit()
         self.set_config('doSaveDenoisedDWI', False)
+        self.set_config('doUnring', False)             # not a key of the reference: see fit()
+        self.set_config('unring_axes', (0, 1))
+        self.set_config('doSaveUnringedDWI', False)
+        self._unring_axes = None                       # doUnring: the in-plane axes as set_data() read them; None: no unringing
         self._denoise_patch = None                     # doDenoise: the patch edge as set_data() read it; None: no denoising
         self._b0_estimate = False                      # doEstimateNoise asks for the b0 estimator (with doDenoise: it runs first)
         self._debias_estimated = False                 # doDebiasSignal without DWI-SNR: fit() fills the estimate in
@@ -163,6 +169,9 @@ class Evaluation:
         if _noise.is_denoise(self.get_config('doDenoise')):                      # (ValueError for anything but 'MPPCA' / True / False)
             denoise_patch = _noise.check_patch(self.get_config('noise_patch'))
             estimate = True                                                      # the denoising launch delivers an estimate as well
+        unring_axes = None
+        if _unring.is_unring(self.get_config('doUnring')):                       # (ValueError for anything but 'kellner' / True / False)
+            unring_axes = _unring.check_axes(self.get_config('unring_axes'))
         debias_snr = None
         if self.get_config('doDebiasSignal'):                                    # core.py:201-206, before anything touches the GPU
             debias_snr = self.get_config('DWI-SNR')
@@ -190,6 +199,8 @@ class Evaluation:
         if noise_patch is not None or denoise_patch is not None:
             # (RuntimeError naming the key, before anything is uploaded)
             _noise.check_patch_fits(img.shape[:3], noise_patch if noise_patch is not None else denoise_patch)
+        if unring_axes is not None:
+            _unring.check_extents(img.shape[:3], unring_axes)                    # (RuntimeError naming the key and the limit)
         self.niiMASK_img = np.ones(img.shape[:3], dtype=np.uint8) if mask is None \
             else np.asarray(mask, dtype=np.uint8)
         if self.niiMASK_img.shape != img.shape[:3]:
@@ -208,6 +219,7 @@ class Evaluation:
         self._estimate_noise = estimate
         self._noise_patch = noise_patch
         self._denoise_patch = denoise_patch
+        self._unring_axes = unring_axes
         self._b0_estimate = b0_estimate
         self._debias_estimated = bool(self.get_config('doDebiasSignal')) and debias_snr is None      # (only with the key: see above)
         if self._debias_estimated:
@@ -331,6 +343,15 @@ class Evaluation:
             RESULTS['DWI_denoised'] float32 [X, Y, Z, nS] in image units (before the debias).  No voxel with a patch at all is the
             RuntimeError of 'MPPCA'.  The volume pipelines (pipeline.py), SignalPreparation.gather and models.X().fit(evaluation) do not
             take it.
+        doUnring                (default False; 'kellner' in any letter case or True; anything else is a ValueError in set_data) the Gibbs
+            ringing of every slice removed by local sub-voxel shifts (Kellner et al. 2016; amico_amd.unring.unring_device):
+            one launch behind the denoising block and before the debias, on the slices along unring_axes (default (0, 1): two different
+            axes out of 0, 1, 2; each extent 8 to 256, anything else is a RuntimeError in set_data).  The mask plays no part; a slice
+            with a NaN / Inf sample is passed through.  Debias, mean_b0, gather, directions, fit, corrected and predicted DWI all read
+            the unringed image; `niiDWI_img` keeps the RAW one.  The noise estimators run before it, on the image they always saw.  It
+            leaves CONFIG['unring_slices'] / ['unring_passed_through'], and with doSaveUnringedDWI RESULTS['DWI_unringed'] float32
+            [X, Y, Z, nS] in image units (before the debias).  The volume pipelines (pipeline.py), SignalPreparation.gather and
+            models.X().fit(evaluation) do not take it.
         doSaveTensorMaps       (default False) the tensor fit that gives `DIRs` also leaves RESULTS['DTI_MAPs'] float32 [X, Y, Z, 4] =
             FA, MD, AD, RD and RESULTS['DTI_evals'] float32 [X, Y, Z, 3] (descending, clipped at dipy's min_diffusivity), zero outside
             the mask: `dti.TensorDirections.fit_maps` of `y`, with DTI_fit_method and the table doMergeB0 gives.  The fit runs as
@@ -405,6 +426,8 @@ class Evaluation:
         self.CONFIG.pop('noise_method', None)                     # (set below by 'MPPCA' only: an earlier fit()'s does not linger)
         self.CONFIG.pop('denoise_voxels', None)                   # (doDenoise only)
         self.CONFIG.pop('denoise_passed_through', None)
+        self.CONFIG.pop('unring_slices', None)                    # (doUnring only)
+        self.CONFIG.pop('unring_passed_through', None)
         den = None
         # doDenoise with doEstimateNoise = True: the b0 estimator below on the raw image as always, the denoising launch after it
         b0_estimate = self._b0_estimate
@@ -461,6 +484,16 @@ class Evaluation:
             if self.get_config('doSaveDenoisedDWI'):
                 d_denoised = d_img.clone() if debias_snr is not None else d_img      # (the debias works in place)
             den = None
+        d_unringed = None
+        if self._unring_axes is not None:
+            # doUnring: a new image (the launch never works in place); everything below reads it
+            unr = _unring.unring_device(plan, d_img.data_ptr(), self._unring_axes)
+            self.set_config('unring_slices', unr['slices'])
+            self.set_config('unring_passed_through', unr['passed_through'])
+            d_img = unr['image']
+            if self.get_config('doSaveUnringedDWI'):
+                d_unringed = d_img.clone() if debias_snr is not None else d_img      # (the debias works in place)
+            unr = None
         if debias_snr is not None:
             # core.py:201-206: in place in HBM, float32(E) where mask != 0 and 0 elsewhere; everything below reads the debiased image
             self._prep._plan.debias_device(d_img.data_ptr(), debias_snr)
@@ -562,6 +595,10 @@ class Evaluation:
             self.RESULTS['DWI_denoised'] = np.lib.stride_tricks.as_strided(d_denoised.cpu().numpy(), shape=plan.shape,
                                                                            strides=tuple(4 * st for st in plan.strides))
             d_denoised = None
+        if d_unringed is not None:
+            self.RESULTS['DWI_unringed'] = np.lib.stride_tricks.as_strided(d_unringed.cpu().numpy(), shape=plan.shape,
+                                                                           strides=tuple(4 * st for st in plan.strides))
+            d_unringed = None
         if self.get_config('doComputeRMSE'):
             self.RESULTS['RMSE'] = sc('rmse', results['rmse'])
         if self.get_config('doComputeNRMSE'):

@@ -103,7 +103,7 @@ void amx_ctx_destroy(amx_ctx *ctx)
     auto release = [](DevBuf &b) { if (b.p) hipFree(b.p); };
     ctx->for_each(release);
     ctx->alt.for_each(release);
-    for (DevBuf *b : {&ctx->big, &ctx->hy, &ctx->hdirs, &ctx->hest, &ctx->hrmse, &ctx->hnrmse, &ctx->hextra, &ctx->hy32, &ctx->wy, &ctx->pred_idx, &ctx->debias_sigma, &ctx->debias_b0, &ctx->median_ws}) release(*b);
+    for (DevBuf *b : {&ctx->big, &ctx->hy, &ctx->hdirs, &ctx->hest, &ctx->hrmse, &ctx->hnrmse, &ctx->hextra, &ctx->hy32, &ctx->wy, &ctx->pred_idx, &ctx->debias_sigma, &ctx->debias_b0, &ctx->median_ws, &ctx->unring_ws}) release(*b);
     if (ctx->debias_stats) hipFree(ctx->debias_stats);
     if (ctx->debias_ev) (void)hipEventDestroy(ctx->debias_ev);
     if (ctx->san_count) hipFree(ctx->san_count);

@@ -108,6 +108,8 @@ struct amx_ctx : WorkSet {
     // exact median (amx_noise.hip): a ring of slots (state + one histogram pair per digit pass); call k takes slot k mod kMedRing
     DevBuf median_ws;
     unsigned median_seq = 0;
+    // Gibbs unringing (amx_unring.hip): the tables and one chunk of slices in float64, never more than amx::kUnringScratchCap bytes
+    DevBuf unring_ws;
 };
 
 // ------------------------------------------------------------------ environment switches
@@ -301,6 +303,7 @@ struct amx_prep {
     long long s[3] = {0, 0, 0};    // element strides of those axes in the image
     long long c[3] = {0, 0, 0};    // strides of those axes in a C-ordered [X][Y][Z] volume
     long long sv = 0;              // element stride of the volume axis
+    int ax[3] = {0, 1, 2};         // the caller's axis (0, 1, 2 of dims) that d[k] / s[k] / c[k] speak of
     long long extent = 0;          // elements spanned by the image (largest offset + 1)
     long long n_total = 0, n_vox = 0;
     int nS = 0, n_out = 0, n_b0 = 0, n_gidx = 0, identity = 0, inplace = 0, hazard = 0, layout = 0;   // layout: 1 planar (s[0]==1), 2 interleaved (sv==1), 0 generic

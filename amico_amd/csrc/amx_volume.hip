@@ -613,7 +613,7 @@ int amx_prep_create(amx_ctx *ctx, const int64_t dims[3], const int64_t strides[4
     for (int j = 0; j < n_out && p->identity; j++)
         if (group_ptr[j + 1] != j + 1 || group_idx[j] != j) p->identity = 0;
     p->n_total = total; p->n_vox = n_vox; p->sv = strides[3];
-    for (int k = 0; k < 3; k++) { p->d[k] = dims[ax[k]]; p->s[k] = strides[ax[k]]; p->c[k] = cstride[ax[k]]; }
+    for (int k = 0; k < 3; k++) { p->d[k] = dims[ax[k]]; p->s[k] = strides[ax[k]]; p->c[k] = cstride[ax[k]]; p->ax[k] = ax[k]; }
     p->layout = p->s[0] == 1 ? 1 : (p->sv == 1 ? 2 : 0);
     p->extent = 1 + (long long)(nS - 1) * strides[3];
     for (int k = 0; k < 3; k++) p->extent += (long long)(dims[k] - 1) * strides[k];

@@ -699,6 +699,39 @@ int amx_prep_noise_mppca_denoise_device(amx_ctx *ctx, const amx_prep *p, const f
 #define AMX_MPPCA_DENOISE_ROUTE_WORDS 11
 int amx_mppca_denoise_route(int nS, int patch, int n_cols, const int64_t dims[3], int64_t out[AMX_MPPCA_DENOISE_ROUTE_WORDS]);
 
+/* (f0+++) Gibbs ringing removed from every slice of the image by local sub-voxel shifts (Kellner, Dhital, Kiselev, Reisert, MRM 2016; no
+ * counterpart in the reference; tests/unring_np.py restates this).  A slice is the image at one position of the third spatial axis and one
+ * volume, I[n_a][n_b] along (axis_a, axis_b); the mask plays no part.  Constants: M = 20 shifts each way, window 1 .. 3.  Shifts, in this
+ * order: s_0 = 0, s_j = j / 40 (j = 1 .. 20), s_(20 + j) = -j / 40 (j = 1 .. 20).
+ *   One line f[0 .. n), cyclic (indices mod n):  g_0 = f;  g_j[x] = sum_x' d_j[(x - x') mod n] f[x'],
+ *     d_j[t] = (1 / n) sum_kappa cos(2 pi kappa (t + s_j) / n),  kappa = -floor((n - 1) / 2) .. floor((n - 1) / 2) (an even n's Nyquist
+ *     term is left out).  Per pixel x and shift j:  TV_L = sum_(t = 1 .. 3) |g_j[x - t] - g_j[x - t - 1]|,
+ *     TV_R = sum_(t = 1 .. 3) |g_j[x + t] - g_j[x + t + 1]|.  Of the 82 candidates in the order (0, L), (0, R), (1, L), (1, R), ... the first
+ *     strict minimum wins (s = 0 wins every exact tie).  With the winner's s = s_j:  U f[x] = (1 - s) g_j[x] + s g_j[x - 1] for s > 0,
+ *     (1 + s) g_j[x] - s g_j[x + 1] otherwise.
+ *   One slice:  a_n(k) = 1 + cos(2 pi k / n);  Gx(ka, kb) = a_nb(kb) / (a_na(ka) + a_nb(kb)), 1/2 where the denominator is 0;
+ *     Ix = Re IDFT2(DFT2(I) Gx),  Iy = I - Ix;  out = U along axis_a of every line of Ix + U along axis_b of every line of Iy.
+ * Everything in fp64 from the float32 samples, one rounding to float32 at the end; the tables in fp64 from integers reduced modulo their
+ * period.  No absolute constant enters: the output of 2^k img is 2^k times that of img, bit for bit; it depends on the slice's samples and
+ * (n_a, n_b) alone, not on the layout, the axes' positions or the chunk.  A slice that holds a NaN or Inf sample is copied through
+ * unchanged, bit for bit, and counted; no other slice is affected.
+ * d_img, d_out: float32 images in the plan's geometry and element strides (any layout a plan takes); d_out is required and no part of
+ * d_img.  (axis_a, axis_b): two different axes out of 0, 1, 2 of the plan's dims; each in-plane extent must be 8 .. 256, anything else is
+ * AMX_E_BADARG.  The call enqueues on `hip_stream`, works through the slices in chunks (amx_unring_route) and waits for the last one:
+ * *slices = slices in the image, *passed_through = those copied through (either may be null).  Scratch is the ctx workspace: the tables
+ * and one chunk of slices, five fp64 planes each -- never more than AMX_UNRING_SCRATCH_CAP bytes, whatever the number of volumes.       */
+#define AMX_UNRING_MIN_EXTENT 8
+#define AMX_UNRING_MAX_EXTENT 256
+#define AMX_UNRING_SCRATCH_CAP (128ll << 20)
+int amx_prep_unring_device(amx_ctx *ctx, const amx_prep *p, const float *d_img, float *d_out, int axis_a, int axis_b, int64_t *slices,
+                           int64_t *passed_through, void *hip_stream);
+/* What a launch asks for, without a device: out = {1 (0 and AMX_E_BADARG: an extent outside 8 .. 256), tile rows, lines per workgroup, tile
+ * depth (the 16 x 16 x 4 fp64 MFMA), n_a and n_b rounded up to the tile, workgroups per slice for the lines along a / along b, LDS bytes
+ * per workgroup of k_unring_dft / of k_unring_shift, bytes of the tables (with the 512-byte head), scratch bytes per slice, slices per
+ * chunk, AMX_UNRING_SCRATCH_CAP}: tables + chunk * per slice, as the grow-only workspace rounds it up, stays under the cap.          */
+#define AMX_UNRING_ROUTE_WORDS 14
+int amx_unring_route(int n_a, int n_b, int64_t out[AMX_UNRING_ROUTE_WORDS]);
+
 /* (f0') NaN / Inf samples, load_data(..., replace_bad_voxels): core.py:152-158 on the raw image and core.py:270-276 on the
  * pre-processed one --
  *     if np.isnan(img).any() or np.isinf(img).any():
