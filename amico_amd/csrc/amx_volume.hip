@@ -5,7 +5,6 @@
 #include "amx_host.hpp"
 #include "amx_tensor.hpp"
 #include "amx_prep_route.hpp"
-#include "amx_lut_route.hpp"
 
 using namespace amx;
 
@@ -40,6 +39,45 @@ __device__ __forceinline__ long long next_live_tile(const PrepArgs &a, int lane)
     return k < a.n_live ? (long long)a.live[k] : -1ll;
 }
 
+// The plan's index lists in LDS: b0 volumes, group pointers, group members.  Scalar loads from global memory would serialise the
+// lane = voxel phases.  The caller orders the stores before the first read (workgroup or wavefront barrier).
+struct PrepLists { int *b0, *gp, *gi; };
+
+template <bool GROUPS>
+__device__ __forceinline__ PrepLists stage_lists(const PrepArgs &a, int *P)
+{
+    PrepLists L;
+    L.b0 = P; L.gp = P + a.n_b0; L.gi = L.gp + a.n_out + 1;
+    for (int i = threadIdx.x; i < a.n_b0; i += blockDim.x) L.b0[i] = a.b0idx[i];
+    if (GROUPS) {
+        for (int i = threadIdx.x; i <= a.n_out; i += blockDim.x) L.gp[i] = a.gptr[i];
+        for (int i = threadIdx.x; i < a.n_gidx; i += blockDim.x) L.gi[i] = a.gidx[i];
+    }
+    return L;
+}
+
+// Tile t = 64 voxels along the fastest axis: where it starts (x0 in row i1 of slab i2); returns this lane's row of y (-1: not masked)
+__device__ __forceinline__ int tile_rank(const PrepArgs &a, long long t, int lane, long long &x0, long long &i1, long long &i2)
+{
+    const long long row = t / a.tiles_per_row;
+    x0 = (t - row * a.tiles_per_row) * 64;
+    i2 = row / a.d1; i1 = row - i2 * a.d1;
+    const long long x = x0 + lane;
+    return x < a.d0 ? a.rank[(i2 * a.d1 + i1) * a.d0 + x] : -1;
+}
+
+// float32 mean of output j's group, summed in index order (core.py:225-227 / 236-252); a group of one is the value itself
+__device__ __forceinline__ float group_mean(const float *row_l, const PrepLists &L, int j)
+{
+    const int g0 = L.gp[j], g1 = L.gp[j + 1];
+    float acc = row_l[L.gi[g0]];
+    if (g1 - g0 > 1) {
+        for (int g = g0 + 1; g < g1; g++) acc = acc + row_l[L.gi[g]];
+        acc = acc / (float)(g1 - g0);
+    }
+    return acc;
+}
+
 // One wavefront per tile of 64 voxels that are consecutive along the image's fastest spatial axis.
 //  (1) the tile's nS values per voxel go to LDS T[voxel][volume] (odd row stride) with coalesced loads in either
 //      memory layout: planar (x fastest, one 256-byte run per volume) or interleaved (volume fastest, one row per voxel);
@@ -48,10 +86,11 @@ __device__ __forceinline__ long long next_live_tile(const PrepArgs &a, int lane)
 //      scaled in place (core.py:221-222) and every output volume = float32 mean of its group in index order
 //      (core.py:225-227 / 236-252); with identity groups the single multiplication is applied on the way out;
 //  (3) rows are written to y[rank][:] as float64 with negative values clipped (core.py:451-452), coalesced per row.
-// The plan's index lists live in LDS (P): scalar loads from global memory would serialise phase 2.
 // DIRS (round 5): the principal direction of the voxel's diffusion tensor (k_dti_dirs' arithmetic: log-linear fit, Jacobi) is taken
 // while the voxel's nS values sit in the tile -- lane = voxel walks them once more --, so the device pipeline reads the image once
 // and y is not read back for the tensor fit.
+// Groups that may not write in place (a scheme whose first volume is a DWI, merged b0) make all n_out outputs in a second tile
+// O[voxel][volume] beside T.
 template <bool IDENTITY, bool DIRECT, bool DIRS = false>
 __global__ __launch_bounds__(64 * kPrepWaves) void k_prep_gather(PrepArgs a)
 {
@@ -61,23 +100,15 @@ __global__ __launch_bounds__(64 * kPrepWaves) void k_prep_gather(PrepArgs a)
     // tile are in flight at once instead of 32 at a time) as T[volume][voxel] with a row stride of kDirectLd = 65 words; the other
     // paths keep T[voxel][volume] (odd stride ldt).  Both are conflict-free for the lane = voxel and the lane = volume accesses.
     constexpr bool direct = IDENTITY && DIRECT;
-    const int per_wave = IDENTITY ? (direct ? a.nS * kDirectLd : 64 * a.ldt) : 64 * a.ldt * (a.inplace ? 1 : 2);
-    int *P = reinterpret_cast<int *>(smf + (size_t)kPrepWaves * per_wave);
-    int *Pb0 = P, *Pgp = P + a.n_b0, *Pgi = Pgp + a.n_out + 1;
-    for (int i = threadIdx.x; i < a.n_b0; i += blockDim.x) Pb0[i] = a.b0idx[i];
-    if (!IDENTITY) {
-        for (int i = threadIdx.x; i <= a.n_out; i += blockDim.x) Pgp[i] = a.gptr[i];
-        for (int i = threadIdx.x; i < a.n_gidx; i += blockDim.x) Pgi[i] = a.gidx[i];
-    }
+    const int tile = direct ? a.nS * kDirectLd : 64 * a.ldt;
+    const int per_wave = (IDENTITY || a.inplace) ? tile : 2 * tile;                              // (prep_route's per_wave)
+    const PrepLists L = stage_lists<!IDENTITY>(a, reinterpret_cast<int *>(smf + (size_t)kPrepWaves * per_wave));
     __syncthreads();
     float *T = smf + (size_t)wave * per_wave;
-    float *O = a.inplace ? T : T + 64 * a.ldt;
+    float *O = a.inplace ? T : T + tile;
     for (long long t = next_live_tile(a, lane); t >= 0; t = next_live_tile(a, lane)) {
-        const long long row = t / a.tiles_per_row;
-        const long long x0 = (t - row * a.tiles_per_row) * 64;
-        const long long i2 = row / a.d1, i1 = row - i2 * a.d1;
-        const long long x = x0 + lane;
-        const int r = x < a.d0 ? a.rank[(i2 * a.d1 + i1) * a.d0 + x] : -1;
+        long long x0, i1, i2;
+        const int r = tile_rank(a, t, lane, x0, i1, i2);
         const unsigned long long live = __ballot(r >= 0);
         if (live == 0ull) continue;
         const long long base = x0 * a.s0 + i1 * a.s1 + i2 * a.s2;
@@ -132,25 +163,18 @@ __global__ __launch_bounds__(64 * kPrepWaves) void k_prep_gather(PrepArgs a)
         if (r >= 0) {
             if (a.normalize) {
                 float m = 0.0f;
-                if (direct) { for (int i = 0; i < a.n_b0; i++) m = m + T[Pb0[i] * kDirectLd + lane]; }
-                else { for (int i = 0; i < a.n_b0; i++) m = m + row_l[Pb0[i]]; }
+                if (direct) { for (int i = 0; i < a.n_b0; i++) m = m + T[L.b0[i] * kDirectLd + lane]; }
+                else { for (int i = 0; i < a.n_b0; i++) m = m + row_l[L.b0[i]]; }
                 m = m / (float)a.n_b0;
                 if (a.mean_b0) a.mean_b0[r] = m;
                 f = (m <= a.thr) ? 0.0f : 1.0f / m;                  // norm_factor[idx] = 0, else 1 / mean_b0
             }
             if (!IDENTITY) {
                 if (a.normalize)
-                    for (int v = 0; v < a.nS; v++) row_l[v] = row_l[v] * f;
+                    for (int v = 0; v < a.nS; v++) row_l[v] = row_l[v] * f;            // rounded (stored) before any group sum reads it
+                // (in place: output j takes volume j's slot of the row, and a later group reads what stands there, core.py:231-245)
                 float *out_l = O + lane * a.ldt;
-                for (int j = 0; j < a.n_out; j++) {
-                    const int g0 = Pgp[j], g1 = Pgp[j + 1];
-                    float acc = row_l[Pgi[g0]];
-                    if (g1 - g0 > 1) {
-                        for (int g = g0 + 1; g < g1; g++) acc = acc + row_l[Pgi[g]];
-                        acc = acc / (float)(g1 - g0);
-                    }
-                    out_l[j] = acc;
-                }
+                for (int j = 0; j < a.n_out; j++) out_l[j] = group_mean(row_l, L, j);
             }
         }
         if (!IDENTITY) WAVE_SYNC();
@@ -359,22 +383,17 @@ __device__ __forceinline__ float scaled(float v, float f)
 __global__ __launch_bounds__(256) void k_prep_stream(PrepArgs a)
 {
     extern __shared__ int P[];
-    int *Pb0 = P, *Pgp = P + a.n_b0, *Pgi = Pgp + a.n_out + 1;
-    for (int i = threadIdx.x; i < a.n_b0; i += blockDim.x) Pb0[i] = a.b0idx[i];
-    for (int i = threadIdx.x; i <= a.n_out; i += blockDim.x) Pgp[i] = a.gptr[i];
-    for (int i = threadIdx.x; i < a.n_gidx; i += blockDim.x) Pgi[i] = a.gidx[i];
+    const PrepLists L = stage_lists<true>(a, P);
+    const int *Pb0 = L.b0, *Pgp = L.gp, *Pgi = L.gi;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const long long wave_id = (long long)blockIdx.x * nwv + wave, n_waves = (long long)gridDim.x * nwv;
     for (long long t = wave_id; t < a.n_tiles; t += n_waves) {
-        const long long row = t / a.tiles_per_row;
-        const long long x0 = (t - row * a.tiles_per_row) * 64;
-        const long long i2 = row / a.d1, i1 = row - i2 * a.d1;
-        const long long x = x0 + lane;
-        const int r = x < a.d0 ? a.rank[(i2 * a.d1 + i1) * a.d0 + x] : -1;
+        long long x0, i1, i2;
+        const int r = tile_rank(a, t, lane, x0, i1, i2);
         if (__ballot(r >= 0) == 0ull) continue;
         if (r < 0) continue;
-        const float *src = a.img + x * a.s0 + i1 * a.s1 + i2 * a.s2;
+        const float *src = a.img + (x0 + lane) * a.s0 + i1 * a.s1 + i2 * a.s2;
         float f = 1.0f;
         if (a.normalize) {
             float m = 0.0f;
@@ -416,10 +435,8 @@ __global__ __launch_bounds__(256) void k_prep_stream(PrepArgs a)
 __global__ __launch_bounds__(256) void k_prep_stream4(PrepArgs a)
 {
     extern __shared__ int P[];
-    int *Pb0 = P, *Pgp = P + a.n_b0, *Pgi = Pgp + a.n_out + 1;
-    for (int i = threadIdx.x; i < a.n_b0; i += blockDim.x) Pb0[i] = a.b0idx[i];
-    for (int i = threadIdx.x; i <= a.n_out; i += blockDim.x) Pgp[i] = a.gptr[i];
-    for (int i = threadIdx.x; i < a.n_gidx; i += blockDim.x) Pgi[i] = a.gidx[i];
+    const PrepLists L = stage_lists<true>(a, P);
+    const int *Pb0 = L.b0, *Pgp = L.gp, *Pgi = L.gi;
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwv = blockDim.x >> 6;
     const long long wave_id = (long long)blockIdx.x * nwv + wave, n_waves = (long long)gridDim.x * nwv;
@@ -706,42 +723,60 @@ int amx_prep_last_launch(const amx_prep *p, char *buf, int cap, int64_t out[3])
     return AMX_OK;
 }
 
-static void note_launch(const amx_prep *p, const char *kernel, long long grid, long long block, size_t lds)
-{
-    p->last_kernel = kernel;
-    p->last_launch[0] = grid; p->last_launch[1] = block; p->last_launch[2] = (long long)lds;
-}
+// A gather kernel, the name amx_prep_last_launch reports for it, and its workgroup size: launched and noted through one row
+struct PrepKernel { void (*fn)(PrepArgs); const char *name; int block; };
+#define PREP_KERNEL(block, ...) {__VA_ARGS__, #__VA_ARGS__, block}
 
-// PREP_ROUTE_LONG: k_prep_long, one workgroup of one wavefront per CU (its tile leaves no room for a second); `a` as prep_gather_dev
-// filled it.  With a tensor helper the directions are fitted from the rows the gather wrote, as for the WLS / NLLS methods.
-static int prep_gather_long(amx_ctx *ctx, const amx_prep *p, PrepArgs a, const PrepRoute &rt, hipStream_t s, const amx_dti *dti, double *d_dirs)
+// instantiations by groups: 0 grouped, 1 identity through T[voxel][volume], 2 identity through the direct-load T[volume][voxel]
+static const PrepKernel kPrepTile[2][3] = {       // [the tensor fit rides on the tile]
+    {PREP_KERNEL(64 * kPrepWaves, k_prep_gather<false,false>), PREP_KERNEL(64 * kPrepWaves, k_prep_gather<true,false>),
+     PREP_KERNEL(64 * kPrepWaves, k_prep_gather<true,true>)},
+    {PREP_KERNEL(64 * kPrepWaves, k_prep_gather<false,false,true>), PREP_KERNEL(64 * kPrepWaves, k_prep_gather<true,false,true>),
+     PREP_KERNEL(64 * kPrepWaves, k_prep_gather<true,true,true>)}};
+static const PrepKernel kPrepLong[3] = {PREP_KERNEL(64, k_prep_long<false,false>), PREP_KERNEL(64, k_prep_long<true,false>),
+                                        PREP_KERNEL(64, k_prep_long<true,true>)};
+static const PrepKernel kPrepStream = PREP_KERNEL(256, k_prep_stream), kPrepStream4 = PREP_KERNEL(256, k_prep_stream4);
+
+// What one gather launches, decided here and nowhere else.
+struct PrepLaunch {
+    const PrepKernel *kernel = nullptr;    // null: refused (more volumes than any tile holds)
+    int direct = 0;                        // PrepArgs::direct
+    long long grid = 0;
+    size_t lds = 0;
+    bool counter_fed = false;              // the wavefronts draw their tiles from the plan's live list: a zeroed counter of the ring
+    bool dirs_ride = false;                // the tensor fit rides on the kernel's tile; with a helper and without this, the directions
+                                           // are fitted afterwards from the rows the kernel wrote
+};
+
+static PrepLaunch prep_decide(const amx_prep *p, const float *d_img, const amx_dti *dti, const amx_ctx *ctx)
 {
-    static bool attr_set[64];                                        // per device, k_prep_long's instantiations only
-    if (!attr_set[ctx->device & 63]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_long<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
-        attr_set[ctx->device & 63] = true;
-    }
-    const int per_cu = (int)(kPrepLdsMax / rt.lds);                  // 1; 2 for groups not in place up to about 245 volumes
-    long long grid = 256LL * per_cu;
-    if (grid > p->n_live64) grid = p->n_live64;
-    int *const my_counter = p->tile_counter + (p->launch_seq++ % amx_prep::kCounterRing);
-    a.live = p->live64; a.n_live = p->n_live64; a.counter = my_counter;
-    a.wt = nullptr; a.dirs = nullptr;
-    HIPCHK(ctx, hipMemsetAsync(my_counter, 0, sizeof(int), s));
-    rec(ctx, 8, s);
+    PrepLaunch L;
     const bool identity = p->identity != 0;
-    if (identity && a.direct) hipLaunchKernelGGL((k_prep_long<true, true>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
-    else if (identity) hipLaunchKernelGGL((k_prep_long<true, false>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
-    else hipLaunchKernelGGL((k_prep_long<false, false>), dim3((unsigned)grid), dim3(64), rt.lds, s, a);
-    note_launch(p, identity ? (a.direct ? "k_prep_long<true,true>" : "k_prep_long<true,false>") : "k_prep_long<false,false>", grid, 64, rt.lds);
-    HIPCHK(ctx, hipGetLastError());
-    rec(ctx, 9, s);
-    if (dti != nullptr)
-        return a.y32 ? amx_dti_directions_device_f32(ctx, dti, a.y32, p->n_vox, d_dirs, (void *)s)
-                     : amx_dti_directions_device(ctx, dti, a.y, p->n_vox, d_dirs, (void *)s);
-    return AMX_OK;
+    L.direct = (identity && p->layout != 2) ? 1 : 0;
+    const PrepRoute rt = prep_route(p->nS, p->n_out, p->n_b0, p->n_gidx, identity, L.direct != 0, p->inplace != 0);
+    if (rt.route == PREP_ROUTE_REFUSED) return L;
+    if (!identity && !p->hazard && p->layout == 1) {
+        // grouped outputs on a planar image whose groups read no earlier output: the streaming kernels, which hold no tile (and so
+        // none a tensor fit could ride on) -- four voxels per lane where the layout is nibabel's and 16-byte loads are aligned
+        const bool contig = p->s[0] == 1 && p->s[1] == p->d[0] && p->s[2] == p->d[0] * p->d[1] && (p->sv & 3) == 0 &&
+                            (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 && (reinterpret_cast<uintptr_t>(p->rank) & 15) == 0;
+        const bool four = contig && !ctx->opt_prep_scalar;
+        const long long tiles = four ? (p->d[0] * p->d[1] * p->d[2] + 255) / 256 : (p->d[0] + 63) / 64 * p->d[1] * p->d[2];
+        L.kernel = four ? &kPrepStream4 : &kPrepStream;
+        L.grid = std::min<long long>((tiles + 3) / 4, 256LL * 16);
+        L.lds = ((size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(int);
+        return L;
+    }
+    // the tile kernels: rt.waves tiles per workgroup, as many workgroups as are resident at once (they draw their tiles from the live
+    // list).  The fused kernel carries the OLS arithmetic only, and only the two-tile route has instantiations of it.
+    L.dirs_ride = dti != nullptr && dti->method == AMX_DTI_OLS && rt.route == PREP_ROUTE_TILE;
+    const int inst = identity ? (L.direct ? 2 : 1) : 0;
+    L.kernel = rt.route == PREP_ROUTE_TILE ? &kPrepTile[L.dirs_ride][inst] : &kPrepLong[inst];
+    L.lds = rt.lds;
+    const long long per_cu = std::min<long long>(8, (long long)(kPrepLdsMax / rt.lds));
+    L.grid = std::min<long long>(256LL * per_cu, (p->n_live64 + rt.waves - 1) / rt.waves);
+    L.counter_fed = true;
+    return L;
 }
 
 static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, int normalize, float b0_threshold,
@@ -756,15 +791,10 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
         if (dti->ctx != ctx || !d_dirs) return amx_bad(ctx, "amx_prep_gather_directions: not a tensor helper of this ctx / null buffer");
         if (dti->nS != p->n_out) return amx_bad(ctx, "amx_prep_gather_directions: the tensor helper's scheme does not match the plan's output volumes");
     }
-    if (dti != nullptr && dti->method != AMX_DTI_OLS) {
-        // the fused kernel carries the OLS arithmetic only: the other methods fit the rows the gather wrote
-        const int rc = prep_gather_dev(ctx, p, d_img, normalize, b0_threshold, d_y, d_y32, d_mean_b0, hip_stream, nullptr, nullptr);
-        if (rc != AMX_OK) return rc;
-        return d_y32 ? amx_dti_directions_device_f32(ctx, dti, d_y32, p->n_vox, d_dirs, hip_stream)
-                     : amx_dti_directions_device(ctx, dti, d_y, p->n_vox, d_dirs, hip_stream);
-    }
     hipStream_t s = (hipStream_t)hip_stream;
     HIPCHK(ctx, hipSetDevice(ctx->device));
+    const PrepLaunch L = prep_decide(p, d_img, dti, ctx);
+    if (!L.kernel) return amx_bad(ctx, "amx_prep_gather: scheme too long for the LDS tile (at most 512 volumes)");
     PrepArgs a;
     memset(&a, 0, sizeof a);
     a.img = d_img; a.rank = p->rank; a.y = d_y; a.y32 = d_y32; a.mean_b0 = normalize ? d_mean_b0 : nullptr;
@@ -772,77 +802,31 @@ static int prep_gather_dev(amx_ctx *ctx, const amx_prep *p, const float *d_img, 
     a.tiles_per_row = (p->d[0] + 63) / 64;
     a.n_tiles = a.tiles_per_row * p->d[1] * p->d[2];
     a.nS = p->nS; a.n_out = p->n_out; a.n_b0 = p->n_b0; a.ldt = p->nS | 1; a.inplace = p->inplace;
-    a.layout = p->layout; a.normalize = normalize ? 1 : 0;
+    a.layout = p->layout; a.normalize = normalize ? 1 : 0; a.direct = L.direct;
     a.gptr = p->gptr; a.gidx = p->gidx; a.b0idx = p->b0idx; a.thr = b0_threshold;
     a.n_gidx = p->n_gidx;
-    if (dti != nullptr) { a.wt = dti->wt; a.min_signal = dti->min_signal; a.dirs = d_dirs; }
-    const bool identity = p->identity != 0;
-    a.direct = (identity && p->layout != 2) ? 1 : 0;
-    // grouped outputs on a planar image whose groups read no earlier output: the streaming kernels, which hold no tile
-    const bool stream = !identity && !p->hazard && p->layout == 1;
-    const PrepRoute rt = prep_route(p->nS, p->n_out, p->n_b0, p->n_gidx, identity, a.direct != 0, p->inplace != 0);
-    if (rt.route == PREP_ROUTE_REFUSED)
-        return amx_bad(ctx, "amx_prep_gather: scheme too long for the LDS tile (at most 512 volumes)");
-    if (rt.route == PREP_ROUTE_LONG && !stream) return prep_gather_long(ctx, p, a, rt, s, dti, d_dirs);
-    const size_t lds = rt.lds;
+    if (L.dirs_ride) { a.wt = dti->wt; a.min_signal = dti->min_signal; a.dirs = d_dirs; }
     static bool attr_set[64];                                        // per device: the attribute belongs to (function, device)
     if (!attr_set[ctx->device & 63]) {
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<true, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-        HIPCHK(ctx, hipFuncSetAttribute((const void *)k_prep_gather<false, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        for (const PrepKernel *k : {&kPrepTile[0][0], &kPrepTile[0][1], &kPrepTile[0][2], &kPrepTile[1][0], &kPrepTile[1][1],
+                                    &kPrepTile[1][2], &kPrepLong[0], &kPrepLong[1], &kPrepLong[2]})
+            HIPCHK(ctx, hipFuncSetAttribute((const void *)k->fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kPrepLdsMax));
         attr_set[ctx->device & 63] = true;
     }
-    const int per_cu = (int)((160 * 1024) / lds) > 8 ? 8 : (int)((160 * 1024) / lds);
-    long long grid = 256LL * per_cu;               // what is resident at once: the wavefronts draw their tiles from the live list
-    const long long need = (p->n_live64 + kPrepWaves - 1) / kPrepWaves;
-    if (grid > need) grid = need;
     // every launch draws its tiles from ITS OWN counter (a ring of kCounterRing, taken in launch order): two gathers of one plan may
     // be in flight together (two streams, double-buffered images sharing a mask) without sharing or resetting each other's ticket
     int *const my_counter = p->tile_counter + (p->launch_seq++ % amx_prep::kCounterRing);
     a.live = p->live64; a.n_live = p->n_live64; a.counter = my_counter;
-    if (stream) {
-        // grouped outputs on a planar image: streaming kernel, no transposition tile
-        const size_t lds_s = ((size_t)p->n_b0 + p->n_out + 1 + p->n_gidx) * sizeof(int);
-        long long g2 = (a.n_tiles + 3) / 4;
-        if (g2 > 256LL * 16) g2 = 256LL * 16;
-        rec(ctx, 8, s);
-        const bool contig = p->s[0] == 1 && p->s[1] == p->d[0] && p->s[2] == p->d[0] * p->d[1] && (p->sv & 3) == 0 &&
-                            (reinterpret_cast<uintptr_t>(d_img) & 15) == 0 && (reinterpret_cast<uintptr_t>(p->rank) & 15) == 0;
-        if (contig && !ctx->opt_prep_scalar) {
-            long long g4 = ((p->d[0] * p->d[1] * p->d[2] + 255) / 256 + 3) / 4;
-            if (g4 > 256LL * 16) g4 = 256LL * 16;
-            hipLaunchKernelGGL(k_prep_stream4, dim3((unsigned)g4), dim3(256), lds_s, s, a);
-            note_launch(p, "k_prep_stream4", g4, 256, lds_s);
-        } else {
-            hipLaunchKernelGGL(k_prep_stream, dim3((unsigned)g2), dim3(256), lds_s, s, a);
-            note_launch(p, "k_prep_stream", g2, 256, lds_s);
-        }
-        HIPCHK(ctx, hipGetLastError());
-        rec(ctx, 9, s);
-        // (the streaming kernels hold no tile a tensor fit could ride on: the directions come from the rows they wrote)
-        if (dti != nullptr)
-            return d_y32 ? amx_dti_directions_device_f32(ctx, dti, d_y32, p->n_vox, d_dirs, hip_stream)
-                         : amx_dti_directions_device(ctx, dti, d_y, p->n_vox, d_dirs, hip_stream);
-        return AMX_OK;
-    }
-    HIPCHK(ctx, hipMemsetAsync(my_counter, 0, sizeof(int), s));
+    if (L.counter_fed) HIPCHK(ctx, hipMemsetAsync(my_counter, 0, sizeof(int), s));
     rec(ctx, 8, s);
-    if (dti != nullptr) {
-        if (identity && a.direct) hipLaunchKernelGGL((k_prep_gather<true, true, true>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-        else if (identity) hipLaunchKernelGGL((k_prep_gather<true, false, true>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-        else hipLaunchKernelGGL((k_prep_gather<false, false, true>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-    }
-    else if (identity && a.direct) hipLaunchKernelGGL((k_prep_gather<true, true>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-    else if (identity) hipLaunchKernelGGL((k_prep_gather<true, false>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-    else hipLaunchKernelGGL((k_prep_gather<false, false>), dim3((unsigned)grid), dim3(64 * kPrepWaves), lds, s, a);
-    note_launch(p, dti != nullptr ? (identity ? (a.direct ? "k_prep_gather<true,true,true>" : "k_prep_gather<true,false,true>") : "k_prep_gather<false,false,true>")
-                                  : (identity ? (a.direct ? "k_prep_gather<true,true>" : "k_prep_gather<true,false>") : "k_prep_gather<false,false>"),
-                grid, 64 * kPrepWaves, lds);
+    hipLaunchKernelGGL(L.kernel->fn, dim3((unsigned)L.grid), dim3(L.kernel->block), L.lds, s, a);
+    p->last_kernel = L.kernel->name;
+    p->last_launch[0] = L.grid; p->last_launch[1] = L.kernel->block; p->last_launch[2] = (long long)L.lds;
     HIPCHK(ctx, hipGetLastError());
     rec(ctx, 9, s);
+    if (dti != nullptr && !L.dirs_ride)
+        return d_y32 ? amx_dti_directions_device_f32(ctx, dti, d_y32, p->n_vox, d_dirs, hip_stream)
+                     : amx_dti_directions_device(ctx, dti, d_y, p->n_vox, d_dirs, hip_stream);
     return AMX_OK;
 }
 
@@ -936,407 +920,3 @@ int amx_prep_scatter(amx_ctx *ctx, const amx_prep *p, const double *values, int 
 }
 
 }  // extern "C"
-
-// ============================================================================ LUT resampling (SURVEY section 8 f, row 4)
-// lut.pyx:274-311 `resample_kernel`:  KR = ones(ndirs, nS);  KR[i, idx_out] = dot(Ylm_out, KRlm[i, :])  for every
-// orientation i -- batched over all atoms as ONE float32 GEMM  C[M x N] = L[M x K] * Ylm^T[K x N]  (M = atoms * ndirs rows
-// of rotated SH coefficients, K = nSH * shells, N = number of DWI volumes) on the matrix cores.
-namespace amx {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-__global__ void k_fill_ones(float *out, long long n)
-{
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) out[i] = 1.0f;
-}
-
-// Shapes whose SH -> signal operator fits the LDS (K <= 256 reduction indices; NODDI / FreeWater: K = 182, N = 90).
-// One wavefront = 32 rows of L against all N columns, 32 at a time, with v_mfma_f32_32x32x2_f32.  The reduction index is
-// split in two halves, one per half-wavefront (lane l works on k = (l / 32) * 2 KH2 + j): every lane owns a contiguous
-// half row of L, held in registers for all column tiles, and a half row of Ylm in LDS (N x K floats staged once per
-// workgroup, read with ds_read_b64; the row stride has an odd number of 8-byte words: 32 rows hit all 64 banks).
-// KH2 = pairs per half-wavefront, a compile-time bound: the loops carry no conditions (indices beyond K read zeros).
-// The order of a sum does not matter to the GEMM.  Measured for 72 000 x 182 x 90 (profiles/): 0.093 ms = 25 TFLOP/s, 16 %
-// of the f32 matrix peak (0.35 ms before); variants that did NOT help: the rows of L through a coalesced per-wavefront
-// LDS tile (0.13 ms at one workgroup per CU), three independent accumulators (0.10 ms, one wavefront per SIMD).
-// (kLutKhMax and the arithmetic that picks one of the three kernels: amx_lut_route.hpp)
-
-// Fused mode (Z != nullptr, amx_lut_rotate_resample): row (atom, orientation) of L is never materialised --
-// L[atom * ndirs + dir][k] = Z[atom][k] * R[dir][k mod n_sh]  (rotate_kernel, lut.pyx:262-264: const * Klm[idx_m0] * Ylm_rot).
-template <int KH2>
-__global__ __launch_bounds__(256) void k_lut_resample(const float *__restrict__ L, const float *__restrict__ Y,
-                                                      const int *__restrict__ idx_out, long long M, int K, int N, int nS,
-                                                      float *__restrict__ out, const float *__restrict__ Z = nullptr,
-                                                      const float *__restrict__ R = nullptr, int ndirs = 1, int n_sh = 1)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_l[];
-    constexpr int Kp = 4 * KH2;                                      // padded K
-    constexpr int Ks = Kp + 2;                                       // Ylm row stride (floats): Ks / 2 odd
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int half = lane >> 5, l32 = lane & 31;
-    const int Npad = (N + 31) & ~31;
-    float *Ys = reinterpret_cast<float *>(smem_l);                    // [Npad][Ks], zero padded
-    // (rows by wavefront, columns by lane, eight rows of loads in flight)
-    for (int nb = wave * 8; nb < Npad; nb += 32) {
-        for (int k = lane; k < Ks; k += 64) {
-            float t[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const int n = nb + u;
-                t[u] = (n < N && k < K) ? Y[(long long)n * K + k] : 0.0f;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++)
-                if (nb + u < Npad) Ys[(size_t)(nb + u) * Ks + k] = t[u];
-        }
-    }
-    __syncthreads();
-    const bool even = (K & 1) == 0;                                  // rows of L start 8-byte aligned
-    for (long long m0 = ((long long)blockIdx.x * 4 + wave) * 32; m0 < M; m0 += (long long)gridDim.x * 128) {
-        // this lane's half row of L, loaded once with 8-byte loads (rows beyond M repeat the last one; masked at the store)
-        const long long row = m0 + l32 < M ? m0 + l32 : M - 1;
-        float2 a2[KH2];
-        if (Z == nullptr) {
-            const float *lrow = L + row * K;
-#pragma unroll
-            for (int j = 0; j < KH2; j++) {
-                const int k = 2 * half * KH2 + 2 * j;
-                if (even && 2 * KH2 + 2 * j + 1 < K) {               // (holds for both halves: no condition per lane)
-                    a2[j] = *reinterpret_cast<const float2 *>(lrow + k);
-                } else {
-                    a2[j].x = (k < K) ? lrow[k] : 0.0f;
-                    a2[j].y = (k + 1 < K) ? lrow[k + 1] : 0.0f;
-                }
-            }
-        } else {
-            // rotation by the addition theorem, formed in registers: per-(l, m) factor of the atom x basis value of the orientation
-            const float *zrow = Z + (row / ndirs) * K, *rrow = R + (row % ndirs) * n_sh;
-            int c = (2 * half * KH2) % n_sh;                          // position inside the shell's block of coefficients
-#pragma unroll
-            for (int j = 0; j < KH2; j++) {
-                const int k = 2 * half * KH2 + 2 * j;
-                const int c1 = (c + 1 == n_sh) ? 0 : c + 1;
-                a2[j].x = (k < K) ? zrow[k] * rrow[c] : 0.0f;
-                a2[j].y = (k + 1 < K) ? zrow[k + 1] * rrow[c1] : 0.0f;
-                c = (c1 + 1 == n_sh) ? 0 : c1 + 1;
-            }
-        }
-        for (int n0 = 0; n0 < N; n0 += 32) {
-            const float2 *yrow = reinterpret_cast<const float2 *>(Ys + (size_t)(n0 + l32) * Ks + 2 * half * KH2);
-            floatx16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < KH2; j++) {
-                const float2 b2 = yrow[j];
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j].x, b2.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[j].y, b2.y, acc, 0, 0, 0);
-            }
-            const int n = n0 + l32;
-            if (n < N) {
-                const int col = idx_out[n];
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const long long r = m0 + 8 * (i / 4) + 4 * half + (i % 4);
-                    if (r < M) out[r * nS + col] = acc[i];
-                }
-            }
-        }
-    }
-}
-
-// The same GEMM with BOTH operands in LDS (plain `lm` input, K even, operator + four row tiles <= 160 KB): what limited
-// k_lut_resample was not the matrix pipe but its left operand -- every lane walking its own 728-byte row of L with 8-byte
-// loads (64 cache lines per load instruction: 59 % of the wavefronts' time, matrix pipe 18 % busy).  32 consecutive rows of L
-// are ONE contiguous 23 KB block, so a wavefront streams its tile global -> LDS with direct 16-byte loads (23 instructions,
-// all in flight at once) and reads the MFMA operand from there; the row stride K = 182 floats puts 32 consecutive rows into
-// 32 different even banks, for the tile and for the operator alike, so neither needs padding or a swizzle.  A row is read up
-// to 4 KH2 - K floats beyond its end (the next row: finite values); the left operand is forced to zero there.
-#ifdef AMX_LUT_PHASES
-__device__ unsigned long long g_lut_ph[8];
-#define LPH_T() __builtin_readcyclecounter()
-#define LPH_ADD(k, t0) ph[k] += __builtin_readcyclecounter() - (t0)
-#else
-#define LPH_T() 0ull
-#define LPH_ADD(k, t0) (void)(t0)
-#endif
-template <int KH2>
-__global__ __launch_bounds__(256) void k_lut_resample_tile(const float *__restrict__ L, const float *__restrict__ Y,
-                                                           const int *__restrict__ idx_out, long long M, int K, int N, int nS,
-                                                           float *__restrict__ out)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_t[];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int half = lane >> 5, l32 = lane & 31;
-#ifdef AMX_LUT_PHASES
-    unsigned long long ph[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const unsigned long long t_all = LPH_T();
-#endif
-    unsigned long long t0 = LPH_T();
-    // LDS: Ys [N][K] (+ a zeroed tail of 1056 B) | per wavefront: Lt [32][K]
-    float *Ys = reinterpret_cast<float *>(smem_t);
-    const long long ybytes = (long long)N * K * 4;
-    const long long yzone = ((ybytes + 1023) & ~1023LL) + 2048;      // the copy's last piece ends inside; rows N .. N + 31 start inside or behind
-    const long long tile_bytes = 32LL * K * 4, tile_stride = (tile_bytes + 1023) & ~1023LL;      // whole 1 KB pieces per wavefront
-    float *Lt = reinterpret_cast<float *>(smem_t + yzone + wave * tile_stride);
-    {
-        const int pieces = (int)((ybytes + 1023) >> 10);
-        for (int p = wave; p < pieces; p += 4) {
-            long long off = ((long long)p << 10) + lane * 16;
-            if (off > ybytes - 16) off = ybytes - 16;                 // (the tail lanes of the last piece repeat its last 16 bytes)
-            __builtin_amdgcn_global_load_lds(reinterpret_cast<const char *>(Y) + off,
-                                             (__attribute__((address_space(3))) void *)(smem_t + ((long long)p << 10)), 16, 0, 0);
-        }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        // A repeating lane still writes at ITS OWN LDS position (destination = base + 16 * lane).  With N * K / 2 odd the copy ends
-        // 8 bytes into a lane's slot: that lane has put bytes [ybytes - 16, ybytes - 8) where the last two floats belong.  They are
-        // read again with an ordinary load (nothing is read beyond the operator's end).
-        if ((ybytes & 8) && threadIdx.x == 0)
-            *reinterpret_cast<float2 *>(Ys + ybytes / 4 - 2) = *reinterpret_cast<const float2 *>(Y + ybytes / 4 - 2);
-        // behind the last row of the operator: zeros (the over-read of row N - 1 and the rows N .. of the last column block)
-        for (long long pos = ybytes / 4 + threadIdx.x; pos < yzone / 4; pos += blockDim.x) Ys[pos] = 0.0f;
-        __syncthreads();
-    }
-    LPH_ADD(0, t0);
-    // the tile of rows m0 .. m0 + 31 -> this wavefront's LDS block (whole 1 KB pieces; the tail lanes of the last piece repeat
-    // its last 16 bytes, which land behind the tile's rows -- but for the one lane that straddles their end: process() below)
-    auto load_tile = [&](long long m0) {
-        const long long rows = (M - m0) < 32 ? (M - m0) : 32;
-        const long long bytes = rows * K * 4;
-        const char *src = reinterpret_cast<const char *>(L + m0 * K);
-        const int pieces = (int)(tile_stride >> 10);
-#pragma unroll 4
-        for (int p = 0; p < pieces; p++) {
-            long long off = ((long long)p << 10) + lane * 16;
-            if (off > bytes - 16) off = bytes - 16;
-            __builtin_amdgcn_global_load_lds(src + off, (__attribute__((address_space(3))) void *)(reinterpret_cast<char *>(Lt) + ((long long)p << 10)),
-                                             16, 0, 0);
-        }
-    };
-    // (measured alternatives, both slower than this plain order: issuing the next tile's loads behind the last block's MFMAs so
-    //  that they overlap the stores -- 0.064 instead of 0.053 ms; advancing all column blocks together with one read of the left
-    //  operand per K-step -- 0.060 ms: the stores of a block then no longer overlap the MFMAs of the next one)
-    auto process = [&](long long m0, int c_begin, int c_end) {
-        unsigned long long t1 = LPH_T();
-        load_tile(m0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");             // (also: the previous tile's stores are out)
-        // a last tile with an odd number of rows and K / 2 odd ends 8 bytes into a lane's 16-byte slot: as for the operator above, the
-        // repeating lane has shifted the last two floats of the last row; an ordinary load puts them right (wavefront-uniform test)
-        if (M - m0 < 32 && (((M - m0) * K) & 2)) {
-            const long long last = (M - m0) * K - 2;
-            if (lane == 0) *reinterpret_cast<float2 *>(Lt + last) = *reinterpret_cast<const float2 *>(L + m0 * K + last);
-        }
-        LPH_ADD(1, t1);
-        const float2 *arow = reinterpret_cast<const float2 *>(Lt + (size_t)l32 * K + 2 * half * KH2);
-        for (int c = c_begin; c < c_end; c++) {
-            t1 = LPH_T();
-            const int n0 = 32 * c;
-            const float2 *yrow = reinterpret_cast<const float2 *>(Ys + (size_t)(n0 + l32) * K + 2 * half * KH2);
-            floatx16 acc;
-#pragma unroll
-            for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-#pragma unroll
-            for (int j = 0; j < KH2; j++) {
-                const int k = 2 * half * KH2 + 2 * j;
-                float2 a2 = arow[j];
-                const float2 b2 = yrow[j];
-                if (2 * KH2 + 2 * j >= K) {                          // (compile-time position: only the last columns of the second half)
-                    a2.x = (k < K) ? a2.x : 0.0f;
-                    a2.y = (k + 1 < K) ? a2.y : 0.0f;
-                }
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2.x, b2.x, acc, 0, 0, 0);
-                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2.y, b2.y, acc, 0, 0, 0);
-            }
-            LPH_ADD(2, t1); t1 = LPH_T();
-            const int n = n0 + l32;
-            if (n < N) {
-                const int col = idx_out[n];
-#pragma unroll
-                for (int i = 0; i < 16; i++) {
-                    const long long r = m0 + 8 * (i / 4) + 4 * half + (i % 4);
-                    if (r < M) out[r * nS + col] = acc[i];
-                }
-            }
-            LPH_ADD(3, t1);
-        }
-#ifdef AMX_LUT_PHASES
-        ph[5] += 1;
-#endif
-    };
-    // Whole tiles first, the same number for every wavefront; the tiles that are left over (2250 tiles over 1024 wavefronts: 202)
-    // are cut into their column blocks, so that the launch ends after 2 1/3 tiles' worth of work instead of 3.
-    const int nb = (N + 31) >> 5;
-    const long long T = (M + 31) >> 5, W = (long long)gridDim.x * 4, wid = (long long)blockIdx.x * 4 + wave;
-    const long long F = T / W;
-    for (long long f = 0; f < F; f++) process((wid + f * W) * 32, 0, nb);
-    for (long long u = wid; u < (T - F * W) * nb; u += W) process((F * W + u / nb) * 32, (int)(u % nb), (int)(u % nb) + 1);
-#ifdef AMX_LUT_PHASES
-    ph[7] = LPH_T() - t_all;
-    if (lane == 0) for (int k = 0; k < 8; k++) atomicAdd(&g_lut_ph[k], ph[k]);
-#endif
-}
-
-// Generic shapes (more than 256 reduction indices, or an SH -> signal operator beyond the LDS: SANDI's 5 shells x 91
-// coefficients x 300 volumes): one wavefront = 32 rows of L against 32 columns at a time, operands straight from L2.  The reduction
-// index is split in two halves, one per half-wavefront (lane l works on k = (l / 32) * Kh + j), so that every lane
-// streams a contiguous piece of its row of L and of its row of Ylm; the order of a sum does not matter to the GEMM.
-__global__ __launch_bounds__(256) void k_lut_resample_generic(const float *__restrict__ L, const float *__restrict__ Y,
-                                                      const int *__restrict__ idx_out, long long M, int K, int N, int nS,
-                                                      float *__restrict__ out)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int half = lane >> 5, l32 = lane & 31;
-    const int Kh = (K + 1) / 2;
-    const long long m0 = ((long long)blockIdx.x * 4 + wave) * 32;
-    if (m0 >= M) return;
-    const long long row = m0 + l32;
-    const float *lrow = L + (row < M ? row : M - 1) * K + (long long)half * Kh;
-    const int kcnt = half == 0 ? Kh : K - Kh;                        // elements of this lane's half
-    for (int n0 = 0; n0 < N; n0 += 32) {
-        const int n = n0 + l32;
-        const float *yrow = Y + (long long)(n < N ? n : N - 1) * K + (long long)half * Kh;
-        floatx16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; i++) acc[i] = 0.0f;
-        for (int j = 0; j < Kh; j++) {
-            const float av = (j < kcnt && row < M) ? lrow[j] : 0.0f;
-            const float bv = (j < kcnt && n < N) ? yrow[j] : 0.0f;
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bv, acc, 0, 0, 0);
-        }
-        if (n < N) {
-            const int col = idx_out[n];
-#pragma unroll
-            for (int i = 0; i < 16; i++) {
-                const long long r = m0 + 8 * (i / 4) + 4 * half + (i % 4);
-                if (r < M) out[r * nS + col] = acc[i];
-            }
-        }
-    }
-}
-
-}  // namespace amx
-
-// shared by amx_lut_resample (lm given) and amx_lut_rotate_resample (zonal factors + basis values given): device buffers
-// d_lm or (d_z, d_r) -> ctx->hextra (f32 [n_rows][nS], ones outside idx_out)
-static int lut_gemm(amx_ctx *ctx, const float *d_lm, const float *d_z, const float *d_r, int ndirs, int n_sh1, int64_t n_rows,
-                    int n_sh, const float *d_ylm, const int *d_idx, int n_out, int nS)
-{
-    int rc = AMX_OK;
-    hipLaunchKernelGGL(amx::k_fill_ones, dim3(2048), dim3(256), 0, nullptr, (float *)ctx->hextra.p, (long long)n_rows * nS);
-    const amx::LutRoute rt = amx::lut_route(n_sh, n_out, d_lm == nullptr);      // (amx_lut_route.hpp: the one place that decides)
-    const int kh2t = rt.kh2;
-    const size_t lds = rt.lds;
-    if (rt.route == amx::LUT_ROUTE_REFUSED)
-        return amx_bad(ctx, "amx_lut_rotate_resample: shape beyond the fused kernel (K <= 256, operator <= 80 KB)");
-    if (rt.route == amx::LUT_ROUTE_TILE) {                           // both operands in LDS
-        auto launch = [&](auto kern) -> int {
-            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            long long blocks = (n_rows + 127) / 128;
-            if (blocks > ctx->n_cu) blocks = ctx->n_cu;              // persistent, one workgroup per CU: the operator is staged once
-            rec(ctx, 8, nullptr);
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, nullptr, d_lm, d_ylm, d_idx, (long long)n_rows, n_sh,
-                               n_out, nS, (float *)ctx->hextra.p);
-            return AMX_OK;
-        };
-        if (kh2t == 23) rc = launch(amx::k_lut_resample_tile<23>);
-        else if (kh2t == 46) rc = launch(amx::k_lut_resample_tile<46>);
-        else rc = launch(amx::k_lut_resample_tile<64>);
-        if (rc) return rc;
-    } else if (rt.route == amx::LUT_ROUTE_GENERIC) {                 // operands from L2
-        rec(ctx, 8, nullptr);
-        hipLaunchKernelGGL(amx::k_lut_resample_generic, dim3((unsigned)((n_rows + 127) / 128)), dim3(256), 0, nullptr, d_lm, d_ylm,
-                           d_idx, (long long)n_rows, n_sh, n_out, nS, (float *)ctx->hextra.p);
-    } else {
-        auto launch = [&](auto kern) -> int {
-            HIPCHK(ctx, hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            long long blocks = (n_rows + 127) / 128;                  // persistent: the Ylm tile is staged once per workgroup
-            const long long cap = 2LL * ctx->n_cu;
-            if (blocks > cap) blocks = cap;
-            rec(ctx, 8, nullptr);
-            hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), lds, nullptr, d_lm, d_ylm, d_idx, (long long)n_rows, n_sh,
-                               n_out, nS, (float *)ctx->hextra.p, d_z, d_r, ndirs, n_sh1);
-            return AMX_OK;
-        };
-        if (kh2t == 23) rc = launch(amx::k_lut_resample<23>);
-        else if (kh2t == 46) rc = launch(amx::k_lut_resample<46>);
-        else rc = launch(amx::k_lut_resample<64>);
-        if (rc) return rc;
-    }
-    HIPCHK(ctx, hipGetLastError());
-    rec(ctx, 9, nullptr);
-    return AMX_OK;
-}
-
-extern "C" int amx_lut_route(int n_sh, int n_out, int fused, int64_t out[3])
-{
-    if (n_sh < 1 || n_out < 1 || !out) return AMX_E_BADARG;
-    const amx::LutRoute rt = amx::lut_route(n_sh, n_out, fused != 0);
-    out[0] = rt.route; out[1] = rt.kh2; out[2] = (int64_t)rt.lds;
-    return AMX_OK;
-}
-
-extern "C" int amx_lut_resample(amx_ctx *ctx, const float *lm, int64_t n_rows, int n_sh, const float *ylm_out,
-                                const int32_t *idx_out, int n_out, int nS, float *out)
-{
-    if (!ctx) return AMX_E_BADARG;
-    if (!lm || !ylm_out || !idx_out || !out || n_rows < 1 || n_sh < 1 || n_out < 1 || nS < n_out)
-        return amx_bad(ctx, "amx_lut_resample: bad argument");
-    for (int k = 0; k < n_out; k++) if (idx_out[k] < 0 || idx_out[k] >= nS) return amx_bad(ctx, "amx_lut_resample: idx_out out of range");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const size_t lb = (size_t)n_rows * n_sh * sizeof(float), yb = (size_t)n_out * n_sh * sizeof(float);
-    const size_t ob = (size_t)n_rows * nS * sizeof(float);
-    if ((rc = amx_ensure(ctx, ctx->hy, lb))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hdirs, yb))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hrmse, (size_t)n_out * sizeof(int)))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hextra, ob))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hy.p, lm, lb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hdirs.p, ylm_out, yb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hrmse.p, idx_out, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, nullptr));
-    if ((rc = lut_gemm(ctx, (const float *)ctx->hy.p, nullptr, nullptr, 1, 1, n_rows, n_sh, (const float *)ctx->hdirs.p,
-                       (const int *)ctx->hrmse.p, n_out, nS))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->hextra.p, ob, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(ctx, hipStreamSynchronize(nullptr));
-    return AMX_OK;
-}
-
-extern "C" int amx_lut_rotate_resample(amx_ctx *ctx, const float *zonal, int n_atoms, const float *ylm_rot, int ndirs,
-                                       int n_sh_shell, int n_shells, const float *ylm_out, const int32_t *idx_out, int n_out,
-                                       int nS, float *out)
-{
-    if (!ctx) return AMX_E_BADARG;
-    if (!zonal || !ylm_rot || !ylm_out || !idx_out || !out || n_atoms < 1 || ndirs < 1 || n_sh_shell < 1 || n_shells < 1 ||
-        n_out < 1 || nS < n_out)
-        return amx_bad(ctx, "amx_lut_rotate_resample: bad argument");
-    for (int k = 0; k < n_out; k++) if (idx_out[k] < 0 || idx_out[k] >= nS) return amx_bad(ctx, "amx_lut_rotate_resample: idx_out out of range");
-    HIPCHK(ctx, hipSetDevice(ctx->device));
-    int rc;
-    const int K = n_sh_shell * n_shells;
-    const int64_t n_rows = (int64_t)n_atoms * ndirs;
-    const size_t zb = (size_t)n_atoms * K * sizeof(float), rb = (size_t)ndirs * n_sh_shell * sizeof(float);
-    const size_t yb = (size_t)n_out * K * sizeof(float), ob = (size_t)n_rows * nS * sizeof(float);
-    if ((rc = amx_ensure(ctx, ctx->hy, zb + rb + 64))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hdirs, yb))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hrmse, (size_t)n_out * sizeof(int)))) return rc;
-    if ((rc = amx_ensure(ctx, ctx->hextra, ob))) return rc;
-    float *d_z = (float *)ctx->hy.p, *d_r = (float *)((char *)ctx->hy.p + ((zb + 15) & ~(size_t)15));
-    HIPCHK(ctx, hipMemcpyAsync(d_z, zonal, zb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(d_r, ylm_rot, rb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hdirs.p, ylm_out, yb, hipMemcpyHostToDevice, nullptr));
-    HIPCHK(ctx, hipMemcpyAsync(ctx->hrmse.p, idx_out, (size_t)n_out * sizeof(int), hipMemcpyHostToDevice, nullptr));
-    if ((rc = lut_gemm(ctx, nullptr, d_z, d_r, ndirs, n_sh_shell, n_rows, K, (const float *)ctx->hdirs.p, (const int *)ctx->hrmse.p,
-                       n_out, nS))) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(out, ctx->hextra.p, ob, hipMemcpyDeviceToHost, nullptr));
-    HIPCHK(ctx, hipStreamSynchronize(nullptr));
-    return AMX_OK;
-}
-
-#ifdef AMX_LUT_PHASES
-extern "C" int amx_debug_lut_phases(unsigned long long *out, int reset)
-{
-    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(amx::g_lut_ph), sizeof(unsigned long long) * 8) != hipSuccess) return -1;
-    if (reset) { unsigned long long z[8] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(amx::g_lut_ph), z, sizeof z) != hipSuccess) return -1; }
-    return 0;
-}
-#endif

@@ -1,4 +1,4 @@
-"""The LUT resampling GEMM (amx_lut_resample / amx_lut_rotate_resample, csrc/amx_volume.hip) held to its float64 reference on all three
+"""The LUT resampling GEMM (amx_lut_resample / amx_lut_rotate_resample, csrc/amx_lut_gemm.hip) held to its float64 reference on all three
 kernels: every case first asserts the kernel it is about (amx_lut_route), then
 
  * bound: EVERY element within (K + 2) 2^-24 (|L| |Y|^T) of the float64 product (tests/lut_gemm_np.py; K + 3 for the fused call), the

@@ -297,6 +297,135 @@ def test_gather_with_directions_equals_gather_then_tensor_fit(order, opts, f32):
         c.check(fused(c._h, sp._plan._h, other._dti._h, d_img.data_ptr(), norm, 0.0, y_b.data_ptr(), mb_b.data_ptr(), d_b.data_ptr(), None))
 
 
+# ----------------------------------------------------------------------------- the two-tile route, branch by branch
+# k_prep_long runs k_prep_gather's three phases with one wavefront per workgroup, and tests/test_gpu_prep_long.py walks their hard
+# cases at 150-512 volumes; these are the smallest shapes that reach the same branches of k_prep_gather itself: the ragged
+# (70, 9, 5) volume, a mask with holes, every result bit for bit against the numpy statements.
+def _flat(img):
+    return np.lib.stride_tricks.as_strided(img, shape=(1 + sum((d - 1) * s // 4 for d, s in zip(img.shape, img.strides)),), strides=(4,))
+
+
+def _gather_device_f32(sp, img, fused_with=None):
+    """amx_prep_gather_device_f32 (or the _directions_ form with the helper `fused_with`) on a device copy -> (y, mean_b0[, dirs])"""
+    import torch
+    from amico_amd import _capi
+    L, c = _capi.lib(), sp.ctx
+    dev = torch.device('cuda', 0)
+    d_img = torch.from_numpy(_flat(img).copy()).to(dev)
+    y = torch.zeros((sp.n_vox, sp.n_out), dtype=torch.float32, device=dev)
+    mb = torch.zeros(sp.n_vox, dtype=torch.float32, device=dev)
+    thr = float(sp.b0_threshold(img))
+    if fused_with is None:
+        c.check(L.amx_prep_gather_device_f32(c._h, sp._plan._h, d_img.data_ptr(), int(sp.do_normalize), thr, y.data_ptr(),
+                                             mb.data_ptr(), None))
+        c.sync(None)
+        return y, mb
+    dirs = torch.zeros((sp.n_vox, 3), dtype=torch.float64, device=dev)
+    c.check(L.amx_prep_gather_directions_device_f32(c._h, sp._plan._h, fused_with._dti._h, d_img.data_ptr(), int(sp.do_normalize),
+                                                    thr, y.data_ptr(), mb.data_ptr(), dirs.data_ptr(), None))
+    c.sync(None)
+    return y, mb, dirs
+
+
+def _check_two_tile(sp, img, ref, mb0, mask, kernel):
+    """float64 rows through the host call, twice on one plan (the ring of tile counters), the kernel that ran, then float32 rows on
+    the device"""
+    for _ in range(2):
+        y, m = sp.gather(img)
+        assert y.shape == ref.shape and np.array_equal(y, ref)
+        assert np.array_equal(m, mb0[mask == 1])
+    name, _, block, lds = sp._plan.last_launch()
+    assert (name, block) == (kernel, 128) and lds <= 160 * 1024, (name, block, lds)
+    y32, m32 = _gather_device_f32(sp, img)
+    assert sp._plan.last_launch()[0] == kernel
+    assert np.array_equal(y32.cpu().numpy().astype(np.float64), ref)
+    assert np.array_equal(m32.cpu().numpy(), mb0[mask == 1])
+
+
+def _scheme_dwi_first():
+    """9 b0 + 30 + 6 = 45 volumes with the last DWI volume moved to the front: with the b0 merged, output 1 (volume 0) would replace
+    a volume the b0 group still reads, so the 37 outputs are made beside the tile.  45 = 32 + 3 * 4 + 1 volumes also walk all three
+    loops of the loader that goes through registers"""
+    sc = S.make_scheme(n_b0=9, shells=((700.0, 30), (2000.0, 6)), seed=0)
+    sc = S.SimpleScheme(np.vstack([sc.raw[-1:], sc.raw[:-1]]))
+    assert sc.nS == 45 and list(sc.b0_idx) == list(range(1, 10)) and sc.dwi_idx[0] == 0
+    return sc
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('order', ['F', 'C'])
+def test_two_tile_groups_not_in_place(order):
+    """planar and interleaved: the hazard keeps the planar image off the streaming kernels"""
+    from amico_amd import prep
+    sc = _scheme_dwi_first()
+    assert prep.volume_groups(sc, do_merge_b0=True)[:3] == [list(range(1, 10)), [0], [10]]
+    img, mask = _volume((70, 9, 5), sc, order, seed=3)
+    ref, mb0 = signal_np.prepare_signal(img, mask, sc.b0_idx, sc.dwi_idx, do_merge_b0=True)
+    assert ref.shape == (int((mask == 1).sum()), 37)
+    sp = prep.SignalPreparation(sc, img, mask, do_merge_b0=True)
+    _check_two_tile(sp, img, ref, mb0, mask, 'k_prep_gather<false,false>')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('order', ['F', 'C'])
+def test_two_tile_in_place_overwrite(order):
+    """3 shells x 12 directions + 2 b0 = 38 volumes with the b0 volumes at the END: every shell's group reads volumes that earlier
+    outputs replaced, and the tile is overwritten in place like the view the numpy statements write into"""
+    from amico_amd import prep
+    sc = S.make_sandi_scheme(bvals=(4000.0, 1000.0, 2500.0), ndir_per_shell=12, n_b0=2)
+    sc = S.SimpleScheme(np.roll(sc.raw, -2, axis=0))
+    assert sc.nS == 38 and list(sc.b0_idx) == [36, 37]
+    img, mask = _volume((70, 9, 5), sc, order, seed=5)
+    ref, mb0 = signal_np.prepare_signal(img, mask, sc.b0_idx, sc.dwi_idx, shells=sc.shells, do_directional_average=True)
+    assert ref.shape == (int((mask == 1).sum()), 4)
+    sp = prep.SignalPreparation(sc, img, mask, do_directional_average=True)
+    _check_two_tile(sp, img, ref, mb0, mask, 'k_prep_gather<false,false>')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('merged', [False, True])
+def test_two_tile_generic_strides(merged):
+    """every second x of a planar image twice as long: neither the voxels nor the volumes are contiguous (the plan's layout 0)"""
+    from amico_amd import prep
+    sc = S.make_scheme()
+    img, mask = _volume((70, 9, 5), sc, 'F', seed=7)
+    big = np.zeros((140, 9, 5, sc.nS), dtype=np.float32, order='F')
+    big[::2] = img
+    big[1::2] = -3.0                               # never read
+    view = big[::2]
+    assert view.strides[0] == 8 and view.strides[3] != 4 and not view.flags.f_contiguous
+    opts = dict(do_merge_b0=True) if merged else {}
+    ref, mb0 = signal_np.prepare_signal(view, mask, sc.b0_idx, sc.dwi_idx, **opts)
+    sp = prep.SignalPreparation(sc, view, mask, **opts)
+    _check_two_tile(sp, view, ref, mb0, mask, 'k_prep_gather<false,false>' if merged else 'k_prep_gather<true,true>')
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('order', ['F', 'C'])
+def test_two_tile_fused_tensor_fit_with_groups_not_in_place(order):
+    """amx_prep_gather_directions_device_f32 on the 45-volume scheme against the plain gather followed by
+    amx_dti_directions_device_f32: y and mean_b0 bit for bit, the directions within 1e-12 wherever the axis is defined"""
+    import torch
+    from amico_amd import prep, dti
+    sc = _scheme_dwi_first()
+    img, mask = _volume((70, 9, 5), sc, order, seed=3)
+    sp = prep.SignalPreparation(sc, img, mask, do_merge_b0=True)
+    td = dti.TensorDirections.from_scheme(sc, do_merge_b0=True, ctx=sp.ctx)
+    y_a, mb_a = _gather_device_f32(sp, img)
+    d_a = torch.zeros((sp.n_vox, 3), dtype=torch.float64, device=y_a.device)
+    td.fit_device(y_a.data_ptr(), sp.n_vox, d_a.data_ptr(), None, f32=True)
+    sp.ctx.sync(None)
+    y_b, mb_b, d_b = _gather_device_f32(sp, img, fused_with=td)
+    assert sp._plan.last_launch()[0] == 'k_prep_gather<false,false,true>'
+    assert torch.equal(y_a, y_b) and torch.equal(mb_a, mb_b)
+    a, b = d_a.cpu().numpy(), d_b.cpu().numpy()
+    assert np.isfinite(b).all() == np.isfinite(a).all()
+    yv = y_a.cpu().numpy().astype(np.float64)
+    flat_row = np.ptp(np.log(np.maximum(yv, 1e-4)), axis=1) == 0.0          # (norm factor 0 -> a constant row: a zero tensor, any direction)
+    ok = np.isfinite(a).all(axis=1) & ~flat_row
+    assert ok.sum() > 0.9 * sp.n_vox and np.abs(a[ok] - b[ok]).max() < 1e-12
+
+
 @pytest.mark.gpu
 def test_prepare_signal_errors_and_edges():
     from amico_amd import prep
