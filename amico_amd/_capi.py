@@ -1232,7 +1232,7 @@ def mppca_denoise_route(nS, patch, n_cols, dims):
 NODDI_BUILDS = ('none', 'small', 'f32_8', 'f64_12', 'f64_nw', 'f32_nw', 'global', 'gram', 'gram_left', 'qr', 'big_all')      # NoddiBuild (csrc/amx_noddi_route.hpp)
 NODDI_ROUTE_WORDS = ('seeds', 'global', 'gemm_ks', 'gemm_passes', 'gemm_window', 'gcert', 'repair', 'rescue', 'tile_in_lds', 'seeds2', 'gcert2', 'wide',
                      'third', 'min_items', 'seed2_max_atoms', 'seed2_trip_add', 'left2_second_half', 'left2_count', 'seed_occ2', 'seed2_occ2',
-                     'seed_chunk', 'seed_waves', 'seed1_waves', 'seed2_waves', 's1', 's2', 's2_gram', 's3', 'n_launch', 'gemm', 'NR')
+                     'seed_chunk', 'seed_waves', 'seed1_waves', 'seed2_waves', 's1', 's2', 's2_gram', 's3', 'n_launch', 'gemm', 'NR', 'gcert2_wide_lds')
 NODDI_GEMMS = ('none', 'windows', '25_9', '25', '40')      # NoddiGemm
 
 

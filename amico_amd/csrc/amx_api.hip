@@ -389,7 +389,7 @@ int amx_noddi_route(int nS, int n_wm, int n_dwi, int ndirs, int is_exvivo, int64
     const amx::NoddiRoute r = amx::noddi_route(sh, {n_vox, call_vox > n_vox ? call_vox : n_vox, lambda1, lambda2}, noddi_switches(&defaults));
     const int64_t words[] = {r.seeds, r.global, r.gemm_ks, r.gemm_n_pass, r.gemm_win, r.gcert, r.repair, r.rescue, r.tile_in_lds, r.seeds2, r.gcert2, r.wide, r.third,
                              r.min_items, r.seed2_max_atoms, r.seed2_trip_add, r.left2_second_half, r.left2_count, r.seed_occ2, r.seed2_occ2, r.seed_chunk,
-                             r.seed_waves, r.seed1_waves, r.seed2_waves, r.s1.build, r.s2.build, r.s2.gram, r.s3.build, r.n_launch, r.gemm, r.NR};
+                             r.seed_waves, r.seed1_waves, r.seed2_waves, r.s1.build, r.s2.build, r.s2.gram, r.s3.build, r.n_launch, r.gemm, r.NR, (int64_t)r.gcert2_wide_lds};
     static_assert(sizeof words / sizeof words[0] + 3 * (sizeof r.launch / sizeof r.launch[0]) <= AMX_ROUTE_WORDS, "amx_noddi_route: out[] too short");
     int k = 0;
     for (int64_t w : words) out[k++] = w;

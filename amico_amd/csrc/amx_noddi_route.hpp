@@ -32,9 +32,10 @@ enum { ZC_CERT1 = 0, ZC_RESC1, ZC_CLIP, ZC_CERT2, ZC_CERT2W, ZC_CERT2W3, ZC_CERT
 // screen2 stands for screen2_S, screen2_kappa0 and u2iso together: amx_build_basis makes the three in one block, and the route sizes the
 // LASSO stage's LDS and switches its certificates on by the one flag -- a build that made only some of them would have to split it.
 struct NoddiTables { bool basis, gram, gram_dwi, basis2, screen2; };
+constexpr int kSeedMaxWm = 144;      // white-matter atoms a seeded LASSO stage holds: nine tiles of 16 in the seed solver's scan
 inline NoddiTables noddi_tables(int n_atoms, int n_wm)
 {
-    const bool basis = n_atoms <= 160 && n_wm <= 144;
+    const bool basis = n_atoms <= 160 && n_wm <= kSeedMaxWm;
     return {basis, true, true, basis, basis};
 }
 
@@ -84,7 +85,7 @@ struct NoddiRoute {
     size_t seed1_lds, seed3_lds, gcert_lds, rescue_lds;
     bool seeds2, gcert2, wide, third;                           // the LASSO stage: seed solver, certificate passes
     int min_items, seed2_max_atoms, seed2_trip_add;
-    size_t seed2_lds, gcert2_lds;
+    size_t seed2_lds, gcert2_lds, gcert2_wide_lds;               // (wide: the second and third certificate pass, the chunk's Gram triangle beside the rest)
     bool left2_second_half; int left2_count;                    // where the certificate passes leave their lists: half of ctx->rlist, Plan::zcount
     bool fork1, fork2;           // AMX_FORK
     NoddiKernel s1, s2, s3, s3_fork;      // the stage kernels (s3_fork: AMX_FORK bit 1, stage 3 without seeds on the LASSO left-overs)
@@ -182,6 +183,16 @@ inline NoddiKernel noddi_lasso_kernel(const NoddiShape &sh, const NoddiCall &c, 
     if (left && seeded) return noddi_kernel(NB_GRAM_LEFT, NR, true, note, sh, 4, 3, 8, 32, 64, true, scr);
     return noddi_kernel(NB_GRAM, NR, true, note, sh, 4, 3, 16, 20, 64, true, scr);
 }
+
+// LDS of the LASSO certificates: S rows, column scales, G[.][iso], S in MFMA operand order, a block per wavefront; the wide passes (one
+// workgroup per CU) add the packed lower triangle of the orientation's white-matter Gram block, tri(i, j) = i (i + 1) / 2 + j.
+// Every shape with a seeded LASSO stage fits -- 144 atoms: 65 040 + 83 520 B of 163 840 -- so the wide passes have this one path.
+constexpr size_t gcert2_lds_bytes(int n_wm)
+{
+    return ((size_t)n_wm * kSeedLd + 2 + 2 * ((n_wm + 1) & ~1) + (size_t)9 * (kSeedKD / 4) * 64 + (size_t)4 * 64 * 16) * sizeof(double);
+}
+constexpr size_t gcert2_wide_lds_bytes(int n_wm) { return gcert2_lds_bytes(n_wm) + (size_t)n_wm * (n_wm + 1) / 2 * sizeof(double); }
+static_assert(gcert2_wide_lds_bytes(kSeedMaxWm) <= kLdsPerCU, "the wide LASSO certificate passes hold the Gram triangle of every seeded shape in LDS");
 
 inline NoddiRoute noddi_route(const NoddiShape &sh, const NoddiCall &c, const NoddiSwitches &sw)
 {
@@ -300,12 +311,13 @@ inline NoddiRoute noddi_route(const NoddiShape &sh, const NoddiCall &c, const No
         r.left2_second_half = r.wide && !r.third;      // (an even number of passes after the first ends in the first half again)
         r.left2_count = !r.wide ? ZC_CERT2 : (r.third ? ZC_CERT2W3 : ZC_CERT2W);
         r.seed2_lds = ((size_t)sh.n_wm * (kSeed2KD + 1) + 8 + (size_t)9 * (kSeed2KD / 4) * 64 + (size_t)4 * (64 * (kSeed2KD + 1) + 64 * 3)) * sizeof(double);
-        r.gcert2_lds = ((size_t)sh.n_wm * kSeedLd + 2 + 2 * ((sh.n_wm + 1) & ~1) + (size_t)9 * (kSeedKD / 4) * 64 + (size_t)4 * 64 * 16) * sizeof(double);
+        r.gcert2_lds = gcert2_lds_bytes(sh.n_wm);
+        r.gcert2_wide_lds = r.wide ? gcert2_wide_lds_bytes(sh.n_wm) : 0;      // (seeds2 asks for the basis tables: n_wm <= kSeedMaxWm, noddi_tables)
         if (r.gcert2) { note("k_s2_prep", 4, 0); note("k_noddi_gemm<lasso> (clipped voxels)", 8, r.gemm_lds2); }      // (else k_noddi_project2<NR>, no note)
         note(r.seed2_occ2 ? "k_lasso_seed<occ2>" : "k_lasso_seed", r.seed2_waves, r.seed2_lds);
         if (r.gcert2) note("k_lasso_gcert<11>", r.seed_waves, r.gcert2_lds);
-        if (r.wide) note("k_lasso_gcert<18,wide>", r.seed_waves, r.gcert2_lds);
-        if (r.third) note("k_lasso_gcert<24,wide,18>", r.seed_waves, r.gcert2_lds);
+        if (r.wide) note("k_lasso_gcert<18,wide>", r.seed_waves, r.gcert2_wide_lds);
+        if (r.third) note("k_lasso_gcert<24,wide,18>", r.seed_waves, r.gcert2_wide_lds);
         // AMX_FORK bit 1: the voxels these certificates left over do not come back to the lane kernels (noddi_fit_dev)
         r.fork2 = r.gcert2 && (sw.fork & 2) && (sw.seed_stages & 2) && r.gcert;
     }

@@ -194,13 +194,14 @@ int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a
     HIPCHK(ctx, hipGetLastError());
     if (wide) {
         // second pass: supports of 12 .. 18 atoms from the left-over lists; its own left-overs in the second half of the buffer
+        // (the wide passes hold the orientation's Gram triangle in LDS: rt.gcert2_wide_lds)
         g.rlist_in = g.rlist; g.rcount_in = g.rcount;
         g.rlist = (int *)ctx->rlist.p + amx_rlist_half(pl); g.rcount = pl.zcount(ZC_CERT2W);
         if (third) { g.qcount = pl.zcount(ZC_CERT2Q); g.q_hi = kGcert2Wide3; }
 #ifdef AMX_STATS
         g.stats = a.c.status + ST_SEED + 48;
 #endif
-        if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide, true>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g))) return rc;
+        if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide, true>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), rt.gcert2_wide_lds, s, g))) return rc;
         amx_note(ctx, "k_lasso_gcert<18,wide>");
         AMX_TRACE(ctx, s, "Gram-space certificates of the LASSO seeds, supports of 12 .. 18 atoms");
         HIPCHK(ctx, hipGetLastError());
@@ -213,7 +214,7 @@ int amx_launch_noddi_gcert2(amx_ctx *ctx, const amx_lut *lut, const NoddiArgs &a
 #ifdef AMX_STATS
             g.stats = nullptr;
 #endif
-            if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide3, true, kGcert2Wide>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), lds, s, g))) return rc;
+            if ((rc = launch_lds(ctx, (k_lasso_gcert<kGcert2Wide3, true, kGcert2Wide>), dim3(((pl.max_schunks + 7) / 8) * 8), dim3(64 * pl.seed_waves), rt.gcert2_wide_lds, s, g))) return rc;
             amx_note(ctx, "k_lasso_gcert<24,wide,18>");
             AMX_TRACE(ctx, s, "Gram-space certificates of the LASSO seeds, supports beyond the second pass");
             HIPCHK(ctx, hipGetLastError());

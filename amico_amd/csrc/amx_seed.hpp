@@ -2104,6 +2104,7 @@ struct Gcert2Args {
 // WIDE = false: every voxel of the chunk, supports of up to 11 atoms, two wavefronts per SIMD.  WIDE = true: second pass over the
 // left-over lists of the first for the supports of 12 .. 18 atoms (another 22 % of the voxels at the default lambdas), one
 // wavefront per SIMD -- the triangle lives in the whole register file (18: 121 spilled registers); what it cannot settle goes on to k_noddi<4>.
+// The wide passes read G_PP and the flagged atoms' G_tP from the packed triangle of the orientation's Gram block in LDS (Gt below).
 constexpr int kGcert2Occ = 2;
 template <int MS, bool WIDE, int LOW = kGcert2Max>
 __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(const Gcert2Args a)
@@ -2116,6 +2117,12 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
     double *giso = scl + ((n_wm + 1) & ~1);                        // [n_wm] G_dwi[j][iso]: what x_iso takes out of a_j,dwi'y
     double *Aop = giso + ((n_wm + 1) & ~1);                        // [MT][KS][64]
     double *Rb = Aop + MT * KS * 64 + (threadIdx.x >> 6) * (64 * RBW);
+    // WIDE: the packed lower triangle of the orientation's white-matter Gram block, Gt[i (i + 1) / 2 + j] = G_dwi[i][j], i >= j -- 83.5 KB at 144
+    // atoms, which fit beside the rest because this pass runs one workgroup per CU anyway (NoddiRoute::gcert2_wide_lds).  A lane gathered its
+    // 18 x 19 / 2 = 171 entries of G_PP, and 18 more per flagged atom, as one 128-byte line each from L2 / HBM with nothing to hide the round trip.
+    // (behind the Rb blocks of the wavefronts at work: at most four -- AMX_SEED_WAVES takes 1, 2 or 4 -- and gcert2_lds_bytes sizes four, so
+    //  the triangle ends at or before the end of the allocation)
+    double *Gt = Aop + MT * KS * 64 + ((int)blockDim.x >> 6) * (64 * RBW);
     const int n_sch = *a.n_schunks;
     const int own = xcd_chunk((int)blockIdx.x, n_sch);
     if (own < 0) return;
@@ -2144,6 +2151,27 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
     stage_rows<KD, LD>(Sl, Sg, n_wm, KD);
     for (int e = threadIdx.x; e < n_wm; e += blockDim.x) { scl[e] = a.colscale[e]; giso[e] = Gd[(size_t)e * a.ldG + a.iso_atom]; }
     stage_operand<KS, MT>(Aop, Sg, n_wm, KD);
+    if (WIDE) {
+        // (many elements of a thread in flight, as the rescue pass stages its tile -- 21: 144 atoms are two round trips of four wavefronts,
+        //  and the registers are idle here; with eight, the five round trips cost what the LDS reads saved: profiles/lasso_wide_lds_ab.txt,
+        //  first phase 59 000 -> 117 000 kcycles with eight, 108 000 with 21.  Consecutive threads read along a
+        //  row of G.  Row of packed element e: the float root of 8 e + 1 -- exact operand, e < 2^21 -- is off by one at most, mended either way)
+        constexpr int UB = 21;
+        const int NE = n_wm * (n_wm + 1) / 2;
+        for (int e0 = threadIdx.x; e0 < NE; e0 += UB * (int)blockDim.x) {
+            double v[UB];
+#pragma unroll
+            for (int u = 0; u < UB; u++) {
+                const int e = e0 + u * (int)blockDim.x < NE ? e0 + u * (int)blockDim.x : NE - 1;
+                int i = (int)((sqrtf(8.f * (float)e + 1.f) - 1.f) * 0.5f);
+                i += ((i + 1) * (i + 2) / 2 <= e) ? 1 : 0;
+                i -= (i * (i + 1) / 2 > e) ? 1 : 0;
+                v[u] = Gd[(size_t)i * a.ldG + (e - i * (i + 1) / 2)];
+            }
+#pragma unroll
+            for (int u = 0; u < UB; u++) { const int e = e0 + u * (int)blockDim.x; if (e < NE) Gt[e] = v[u]; }
+        }
+    }
     __syncthreads();
     const double kap = a.kappa0[ck.dir], lam1 = a.lam1, lam2 = a.lam2;
     const double gii = Gd[(size_t)a.iso_atom * a.ldG + a.iso_atom];      // ||iso_dwi||^2
@@ -2207,21 +2235,42 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
             // Every entry lands in the register it will live in, under the lane's own mask (s < np), and is USED outside that guard.
             // As `(s < np) ? sc sc Gd[..] + .. : 0` each load sat in a branch of its own with a wait behind it: 77 (wide pass: 189)
             // memory round trips one after the other per block of 64 voxels -- the whole kernel (SQ_WAIT_ANY 76 - 81 % of its cycles).
-            const unsigned ldg = (unsigned)a.ldG;
-            unsigned rowo[MS];
+            if (WIDE) {
+                // the c gathers first, all in flight together (the table is per voxel: global); then the triangle from LDS, row by row --
+                // slots ascend, so idx[s] is the packed row and idx[t], t <= s, a column of it
 #pragma unroll
-            for (int s = 0; s < MS; s++) rowo[s] = (unsigned)V.idx[s] * ldg;
-#pragma unroll
-            for (int s = 0; s < MS; s++) {
-#pragma unroll
-                for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = 0.0;
-                V.c[s] = 0.0;
-                if (s < V.np) {                     // (loads under the lane's mask, used outside it: see k_nnls_gcert's exact dual values)
-#pragma unroll
-                    for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = Gd[rowo[s] + (unsigned)V.idx[t]];
-                    V.c[s] = Crow[(size_t)V.idx[s] * 64];
+                for (int s = 0; s < MS; s++) {
+                    V.c[s] = 0.0;
+                    if (s < V.np) V.c[s] = Crow[(size_t)V.idx[s] * 64];
                 }
-                if (WIDE) __builtin_amdgcn_sched_barrier(0);      // row by row: 171 addresses computed ahead of their loads were 342 registers of their own
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int s = 0; s < MS; s++) {
+#pragma unroll
+                    for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = 0.0;
+                    if (s < V.np) {
+                        const double *Gr = Gt + (((unsigned)V.idx[s] * ((unsigned)V.idx[s] + 1u)) >> 1);
+#pragma unroll
+                        for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = Gr[V.idx[t]];
+                    }
+                    __builtin_amdgcn_sched_barrier(0);      // row by row: 171 addresses computed ahead of their reads are registers of their own
+                }
+            } else {
+                const unsigned ldg = (unsigned)a.ldG;
+                unsigned rowo[MS];
+#pragma unroll
+                for (int s = 0; s < MS; s++) rowo[s] = (unsigned)V.idx[s] * ldg;
+#pragma unroll
+                for (int s = 0; s < MS; s++) {
+#pragma unroll
+                    for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = 0.0;
+                    V.c[s] = 0.0;
+                    if (s < V.np) {                     // (loads under the lane's mask, used outside it: see k_nnls_gcert's exact dual values)
+#pragma unroll
+                        for (int t = 0; t <= s; t++) V.T[stri<MS>(s, t)] = Gd[rowo[s] + (unsigned)V.idx[t]];
+                        V.c[s] = Crow[(size_t)V.idx[s] * 64];
+                    }
+                }
             }
 #pragma unroll
             for (int s = 0; s < MS; s++) {
@@ -2269,8 +2318,21 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
         {
             double rt[KD];
             const double *Cu = Crow + (size_t)(a.aux0 + (clip ? kAuxU : kAuxU2)) * 64;
+            if (WIDE && MS <= kGcert2Wide) {
+                // (all twelve rows in flight, then the arithmetic: left to itself the compiler waited for each load before it issued the
+                //  next -- twelve memory round trips one after the other: the screening phase 160 000 -> 105 000 kcycles
+                //  (profiles/lasso_wide_lds_ab.txt, which also times the kernel with and without this branch).  The third pass, whose triangle
+                //  lives in scratch, has no registers for them: 2 564 -> 2 640 B of scratch)
+                double cu[KD];
 #pragma unroll
-            for (int d = 0; d < KD; d++) rt[d] = Cu[(size_t)d * 64] - xq * u2[d];
+                for (int d = 0; d < KD; d++) cu[d] = Cu[(size_t)d * 64];
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int d = 0; d < KD; d++) rt[d] = cu[d] - xq * u2[d];
+            } else {
+#pragma unroll
+                for (int d = 0; d < KD; d++) rt[d] = Cu[(size_t)d * 64] - xq * u2[d];
+            }
 #pragma unroll
             for (int s = 0; s < MS; s++) {
                 const double *col = Sl + V.idx[s] * LD;
@@ -2309,9 +2371,17 @@ __global__ void __launch_bounds__(256, WIDE ? 1 : kGcert2Occ) k_lasso_gcert(cons
                 for (int s = 0; s < MS; s++) gv[s] = 0.0;
                 if (on) {
                     ct = Crow[(size_t)tc * 64];
-                    const double *gt = Gd + (size_t)tc * a.ldG;
+                    if (WIDE) {
+                        // G[t][idx] from the packed triangle: row = the larger index (k_build_gram's G is symmetric to the bit: exact
+                        // products of floats, summed in the same order on both sides of the diagonal)
+                        const unsigned ut = (unsigned)tc, tri_t = (ut * (ut + 1u)) >> 1;
 #pragma unroll
-                    for (int s = 0; s < MS; s++) if (s < V.np) gv[s] = gt[V.idx[s]];
+                        for (int s = 0; s < MS; s++) if (s < V.np) { const unsigned us = (unsigned)V.idx[s]; gv[s] = Gt[ut > us ? tri_t + us : ((us * (us + 1u)) >> 1) + ut]; }
+                    } else {
+                        const double *gt = Gd + (size_t)tc * a.ldG;
+#pragma unroll
+                        for (int s = 0; s < MS; s++) if (s < V.np) gv[s] = gt[V.idx[s]];
+                    }
                 }
                 double g = on ? (clip ? 1.0 : st) * (ct - sub - xq * giso[tc]) - lam1 : -1.0;
 #pragma unroll
